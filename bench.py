@@ -4,17 +4,28 @@ configs[2] at N=1; configs[3] = the same sharded over N GPUs, weak scaling).
 
     python bench.py --gpus N --steps K --warmup W           (N > 1 without WORLD_SIZE: starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py ... --full                              (+ every secondary measurement below)
+    python bench.py ... --dump-outputs DIR                  (+ the last timed step's outputs as DIR/*.npy)
 
 A "step" is one env.step() for every env of the rank: action processing, one physics step (4 sub-steps of
 dynamics + PGS contact solve), fused obs/reward/termination, in-step resets and the reference's conditional
 extra physics step -- nothing is skipped.  Synthetic data: random actions 2*U(0,1)-1 (the law of the
 reference's random-action mode, dexhand_base.py:856), pre-generated in HBM before the timed region.
 
-Besides the contract line's `value` the JSON carries three secondary regimes that are never `value`:
-`staggered_resets` (episode clocks de-synchronised: some env resets in almost every step, as in training),
-`contact_rich` (every hand lowered onto its box: the regime a grasping policy lives in, with the contact-solve
-roofline measured there; `us_per_physics_step` = round 1's window right after the teleport, `settled` = the 100 steps
-after it) and `cpu_baseline` (the CPU oracle on the host cores).
+A plain run sets up, warms up, times the K steps and prints the contract line: `value`, `ms_per_step`, the headline
+launch's roofline from the timed region's own HIP events, and the contact / reset counts of the timed run.  Everything that
+takes runs of its own is measured only with --full: the stand-alone kernels (`kernel_us`, `roofline_substep`,
+`roofline_dynamics`, `roofline_contact_solve_isolated_kernel`), the blocking end-of-rollout collective (N > 1), and four
+secondary figures that are never `value`: `staggered_resets` (episode clocks de-synchronised: some env resets in almost
+every step, as in training), `contact_rich` (every hand lowered onto its box: the regime a grasping policy lives in, with
+the contact-solve roofline measured there; `us_per_physics_step` = round 1's window right after the teleport, `settled` =
+the 100 steps after it), `training_like` (make_env().step() with hands on their boxes and reset churn) and `cpu_baseline` (the CPU oracle
+on the host cores).  The --no-* options switch single legs of a --full run off.
+
+--dump-outputs DIR writes what the timed path handed its caller in its last timed step -- obs_buf, rew_buf, reset_buf -- as
+DIR/{obs,rew,reset}.npy in float32 (suffix _rank<r> when N > 1).  The inputs are seeded (reset stream, actions), so two builds
+run with the same arguments can be compared output for output.  Above 64 MB in all, a fixed seeded sample of the envs is
+written, with their indices in env_index.npy.
 """
 import argparse
 import json
@@ -29,6 +40,7 @@ sys.path.insert(0, ROOT)
 
 PEAK_HBM_GBS = 8000.0                      # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 STEP_BYTES = 2560.0                        # algorithmic bytes of a whole env-step
+DUMP_LIMIT_BYTES = 64 << 20                # --dump-outputs: at most this much in all
 
 
 def parse_args():
@@ -45,6 +57,11 @@ def parse_args():
                     help="BaseTask + --control-mode position + --num-envs 1024 = BASELINE configs[1] (articulated FD only, no object)")
     ap.add_argument("--control-mode", default=None, choices=["position", "position_delta"])
     ap.add_argument("--rollout", action="store_true", help="fill the rollout buffer also when --gpus 1 (the multi-GPU code path minus the collective)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: stand-alone kernels, the blocking collective (gpus > 1), "
+                         "staggered_resets, contact_rich, training_like and cpu_baseline (off: only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's obs_buf / rew_buf / reset_buf as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stagger", action="store_true", help="skip the secondary staggered-episode measurement")
     ap.add_argument("--no-contact-rich", action="store_true", help="skip the secondary contact-rich measurement")
@@ -71,6 +88,23 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.exit(subprocess.call(cmd))
+
+
+def dump_outputs(out_dir, core, suffix="", limit=DUMP_LIMIT_BYTES):
+    """What the timed path's last step handed its caller (obs_buf, rew_buf, reset_buf) as float32 .npy files in out_dir; when
+    they exceed `limit` bytes, the rows of a fixed seeded sample of the envs, whose indices go to env_index.npy."""
+    import numpy as np
+    arrays = {name: t.float().cpu().numpy() for name, t in (("obs", core.obs_buf), ("rew", core.rew_buf), ("reset", core.reset_buf))}
+    n = core.N
+    row_bytes = sum(a.nbytes for a in arrays.values()) // n
+    if n * row_bytes > limit:
+        k = limit // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(sim_cfg_factory, n, seconds_budget=24.0):
@@ -280,6 +314,8 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, core, f"_rank{rank}" if world > 1 else "", DUMP_LIMIT_BYTES // world)
     resets = float(core.field("reset_count").sum().item()) - resets0
     kbar = float(core.stats[_abi.STAT["MEAN_CONTACTS"]].item())
     kbar_hand = float(core.stats[_abi.STAT["MEAN_HAND_CONTACTS"]].item())
@@ -287,26 +323,29 @@ def main():
     collective = None
     if world > 1:
         gstats = last_handle[0].stats() if last_handle[0] is not None else None     # whole-population statistics of the last rollout (all ranks)
-        # the end-of-rollout collective on its own (not overlapped), next to the simulation time of one rollout
-        tms = []
-        for _ in range(5):
-            rollout.t = rollout.T
-            torch.cuda.synchronize()
-            dist.barrier()
-            c0 = time.perf_counter()
-            rollout.gather()
-            torch.cuda.synchronize()
-            tms.append((time.perf_counter() - c0) * 1e3)
-        tt = torch.tensor([sorted(tms)[len(tms) // 2]], device=device, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        collective_ms = None
+        if args.full:
+            # the end-of-rollout collective on its own (not overlapped), next to the simulation time of one rollout
+            tms = []
+            for _ in range(5):
+                rollout.t = rollout.T
+                torch.cuda.synchronize()
+                dist.barrier()
+                c0 = time.perf_counter()
+                rollout.gather()
+                torch.cuda.synchronize()
+                tms.append((time.perf_counter() - c0) * 1e3)
+            tt = torch.tensor([sorted(tms)[len(tms) // 2]], device=device, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            collective_ms = float(tt.item())
         per_rank_mb = args.horizon * N * (sc.num_obs * 4 + 4 + 1) / 1e6
-        collective = {"mode": args.gather, "collective_ms": float(tt.item()),
+        collective = {"mode": args.gather, "collective_ms": collective_ms,
                       "global_stats_last_rollout": None if gstats is None else {
                           k: float(gstats[k].mean()) for k in ("success_rate", "failure_rate", "timeout_rate", "num_resets", "mean_contacts")},
                       "simulation_ms_per_rollout": dt / args.steps * 1e3 * args.horizon,
                       "payload_mb_per_rank": per_rank_mb, "rccl_ranks": dist.get_world_size(),
-                      "note": "collective_ms = blocking gather alone (median of 5, max over ranks); in the timed region it is "
-                              "issued asynchronously and overlaps the next rollout (double-buffered slots)"}
+                      "note": "collective_ms = blocking gather alone (median of 5, max over ranks; --full only); in the timed region "
+                              "it is issued asynchronously and overlaps the next rollout (double-buffered slots)"}
 
     if rank == 0:
         total_envs = N * world
@@ -316,14 +355,15 @@ def main():
         # contains the device-gated no-op launch (~3 us) and the dispatch gaps -- an upper bound.  A hipEvent pair around
         # each single launch is NOT used: the events' release/acquire fences make the kernel start from a cold L2.
         t_step = ev0.elapsed_time(ev1) * 1e3 / args.steps
-        t_sub = core.time_stage(_abi.STAGE["SUBSTEP"], 50)     # a single sub-step (dynamics + solve + integrate + publish) as its own launch
-        if args.joint_limit_rows:      # (the un-fused test kernels do not build joint-limit rows)
-            t_solve = t_dyn = float("nan")
-        else:
-            t_solve = core.time_stage(_abi.STAGE["SOLVE"], 50)     # the same sweeps as a stand-alone kernel
-            t_dyn = core.time_stage(_abi.STAGE["DYNAMICS"], 50)
-        t_post = core.time_stage(_abi.STAGE["POST"], 20)
-        t_pub = core.time_stage(_abi.STAGE["PUBLISH"], 20)
+        if args.full:
+            t_sub = core.time_stage(_abi.STAGE["SUBSTEP"], 50)     # a single sub-step (dynamics + solve + integrate + publish) as its own launch
+            if args.joint_limit_rows:      # (the un-fused test kernels do not build joint-limit rows)
+                t_solve = t_dyn = float("nan")
+            else:
+                t_solve = core.time_stage(_abi.STAGE["SOLVE"], 50)     # the same sweeps as a stand-alone kernel
+                t_dyn = core.time_stage(_abi.STAGE["DYNAMICS"], 50)
+            t_post = core.time_stage(_abi.STAGE["POST"], 20)
+            t_pub = core.time_stage(_abi.STAGE["PUBLISH"], 20)
         b_sub = (632.0 + 204.0) * N                    # q, qd, targets, box in; q, qd, box out; cforce (last sub-step)
         b_dyn = (500.0 + 36.0 * kbar) * N
         pmc = {}
@@ -353,7 +393,7 @@ def main():
                                     if args.task == "BlindGrasping" and N == 4096 and not args.dr else "")),
                        "control_mode": args.control_mode or "task default",
                        "num_envs_per_gpu": N, "sim_dt": float(sc.dt), "substeps": int(sc.substeps), "pgs_iterations": int(sc.num_position_iterations),
-                       "preroll_steps": args.preroll,
+                       "preroll_steps": args.preroll, "full": bool(args.full),
                        "obs_dict": ("policy keys only (env.obsDict = policy: the 392 SoA rows behind get_observations_dict() are not materialised)"
                                     if args.obs_dict == "policy" else "all 392 rows materialised every step (env.obsDict = all, the product default)"),
                        "contact_solver": "warm-started block-parallel PGS with mass splitting (HIP: csrc/dexsim_physics.hip.inc, phases 3-4 of substep_body)",
@@ -367,19 +407,22 @@ def main():
             # dominant kernel = the one launch that carries a whole control step (k_physics4<false> with the action and
             # post-physics blocks); algorithmic bytes = SURVEY 8d's whole-env-step figure
             "roofline": roof("k_physics4", STEP_BYTES * N, t_step),
-            "roofline_substep": roof("k_substep", b_sub, t_sub),
+        }
+        if args.full:
+            out["roofline_substep"] = roof("k_substep", b_sub, t_sub)
             # (the stand-alone k_solve in the headline state: 4 box/ground contacts, no hand contact -- kept for continuity with
             # rounds 1-2; the BASELINE sub-metric on the PRODUCTION kernel is roofline_contact_solve below, filled by the
             # contact_rich leg from the kernel's own phase stamps)
-            "roofline_contact_solve_isolated_kernel": roof("k_solve", (256.0 + 60.0 * kbar) * N, t_solve),
-            "roofline_dynamics": roof("k_dynamics", b_dyn, t_dyn),
-            "roofline_whole_step": {"bound": "hbm", "achieved": STEP_BYTES * value / world / 1e9, "peak": PEAK_HBM_GBS,
-                                    "unit": "GB/s", "frac": STEP_BYTES * value / world / 1e9 / PEAK_HBM_GBS, "traffic": None},
-            "kernel_us": {"k_physics4_step": t_step, "k_substep": t_sub, "k_dynamics": t_dyn, "k_solve": t_solve, "k_post": t_post, "k_publish": t_pub},
-        }
+            out["roofline_contact_solve_isolated_kernel"] = roof("k_solve", (256.0 + 60.0 * kbar) * N, t_solve)
+            out["roofline_dynamics"] = roof("k_dynamics", b_dyn, t_dyn)
+        out["roofline_whole_step"] = {"bound": "hbm", "achieved": STEP_BYTES * value / world / 1e9, "peak": PEAK_HBM_GBS,
+                                      "unit": "GB/s", "frac": STEP_BYTES * value / world / 1e9 / PEAK_HBM_GBS, "traffic": None}
+        out["kernel_us"] = {"k_physics4_step": t_step}
+        if args.full:
+            out["kernel_us"].update({"k_substep": t_sub, "k_dynamics": t_dyn, "k_solve": t_solve, "k_post": t_post, "k_publish": t_pub})
         if collective is not None:
             out["rollout_gather"] = collective
-        if world == 1 and not args.no_stagger:
+        if world == 1 and args.full and not args.no_stagger:
             # Secondary figure, NOT `value`: the timed region above starts from a fresh env, like the reference's own run,
             # so all episodes end in the same control step and the conditional second physics step of
             # reset_manager.py:180 runs once per ~200 steps.  In training the episodes de-synchronise and some env
@@ -403,7 +446,7 @@ def main():
             ds = time.perf_counter() - ts
             out["staggered_resets"] = {"value": N * 200 / ds, "unit": "env-steps/s", "ms_per_step": ds / 200 * 1e3,
                                        "resets_per_step": (float(core.field("reset_count").sum().item()) - r0) / 205}
-        if world == 1 and not args.no_contact_rich and args.task == "BlindGrasping":
+        if world == 1 and args.full and not args.no_contact_rich and args.task == "BlindGrasping":
             # Secondary figure, NOT `value`: every hand lowered onto its box (scripts/contact_regime.py's state) -- the
             # regime a policy that has learnt to grasp lives in.  Timed: back-to-back physics steps (4 sub-steps each,
             # general contact path in every workgroup), HIP events around the region; and the stand-alone contact-solve
@@ -493,9 +536,9 @@ def main():
                                                  "limited_by": "per-contact update chains of the block solver (17 passes x ~300 dependent instructions) and their exchange barriers",
                                                  "note": "upper bound on the solver's share: the whole physics step's time is charged to it"},
             }
-        if world == 1 and not args.no_training_like and args.task == "BlindGrasping":
+        if world == 1 and args.full and not args.no_training_like and args.task == "BlindGrasping":
             out["training_like"] = training_like(args, N, device, gen, keep_busy=keep_busy)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(factory, N)
         print(json.dumps(out))
     if world > 1:

@@ -21,7 +21,8 @@ InitializationManager) is reference code executing unmodified.
 The orchestration the fake parent performs (step / reset / reset_idx call order) restates
 dexhand_env/tasks/dexhand_base.py:743-942, which cannot be imported (it pulls in the viewer/video stack).
 
-Output: tests/golden/l2_<scenario>.npz  (+ the cfg overrides as JSON inside the npz).
+Output: tests/golden/l2_<scenario>.npz  (+ the cfg overrides as JSON inside the npz), and
+tests/golden/reference_cfg_<task>.json (the reference's cfg tree as composed; `generate_golden.py cfg` writes only these).
 """
 import copy
 import json
@@ -683,10 +684,26 @@ def pin_quaternion_standins():
     return buf.getvalue().count("PASSED")
 
 
+def record_composed_cfg():
+    """The reference's YAML tree composed for each task at numEnvs = 4096 (by the product's composer): the recorded settings
+    tests/test_cfg_compose.py compares the shipped defaults with."""
+    from dexrobot_isaac_amd.cfg_compose import compose
+    for task in ("BaseTask", "BlindGrasping"):
+        c = compose(os.path.join(REF, "dexhand_env", "cfg"), overrides=[f"task={task}", "env.numEnvs=4096"])
+        path = os.path.join(HERE, f"reference_cfg_{task}.json")
+        with open(path, "w") as f:
+            json.dump(c, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(f"cfg {task}: wrote {path}")
+
+
 def main():
     if not os.path.isdir(REF):
         print("reference not present; nothing generated")
         return 0
+    only = set(sys.argv[1:])
+    if not only or "cfg" in only:
+        record_composed_cfg()
     install_standins()
     sys.path.insert(0, REF)
     n = pin_quaternion_standins()
@@ -698,7 +715,6 @@ def main():
              ("blind_wide", 70, 26, 15, {9: [3, 17, 65, 69], 20: [0, 64]}, (2, 6, 8, 13, 17, 21, 25)),
              ("base_wide", 70, 10, 16, {4: [1, 66]}, (0, 5, 9)),
              ("blind_long", 6, 345, 17, None, (197, 198, 199, 226, 227, 228, 327, 328, 344))]
-    only = set(sys.argv[1:])
     for name, N, T, seed, events, snap in table:
         if only and name not in only:
             continue

@@ -1,13 +1,13 @@
-"""The Hydra-free composer against (a) a miniature cfg tree using every feature and (b), when the reference checkout
-is present, the reference's real YAML tree -- whose composition must equal the literal defaults the product ships."""
+"""The Hydra-free composer against (a) a miniature cfg tree using every feature and (b) the reference's real YAML tree --
+whose composition (recorded per task in tests/golden/reference_cfg_<task>.json by tests/golden/generate_golden.py) must
+equal the literal defaults the product ships."""
+import json
 import os
 
 import pytest
 
 from dexrobot_isaac_amd.cfg_compose import compose
 from dexrobot_isaac_amd.config import build_sim_config, default_cfg
-
-REF_CFG = "/root/reference/dexhand_env/cfg"
 
 
 def _write(root, rel, text):
@@ -40,10 +40,10 @@ def test_composer_semantics(tmp_path):
         compose(d, overrides=["task=C"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference checkout not present")
 @pytest.mark.parametrize("task", ["BaseTask", "BlindGrasping"])
-def test_reference_yaml_tree_equals_shipped_defaults(task):
-    composed = compose(REF_CFG, overrides=[f"task={task}", "env.numEnvs=4096"])
+def test_reference_yaml_tree_equals_shipped_defaults(golden_dir, task):
+    with open(os.path.join(golden_dir, f"reference_cfg_{task}.json")) as f:
+        composed = json.load(f)                    # compose(<reference cfg tree>, ["task=<task>", "env.numEnvs=4096"])
     shipped = default_cfg(task)
     shipped["env"]["numEnvs"] = 4096
     a, _ = build_sim_config(composed)
