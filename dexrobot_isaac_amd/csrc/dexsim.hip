@@ -263,15 +263,12 @@ int dexsim_create(const DexSimConfig* cfg, const DexHandModel* model, int device
     for (int i = 3; i < 6; i++) if (model->inertia[j][i] != 0.f) hp.inertia_diag = 0;
   HIP_TRY(hipMalloc(&h->d_params, sizeof(DevParams)));
   HIP_TRY(hipMemcpy(h->d_params, &hp, sizeof(DevParams), hipMemcpyHostToDevice));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_substep<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_substep<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_substep<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_substep<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_post), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics1<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics1<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIP_TRY(hipEventCreate(&h->ev0));
   HIP_TRY(hipEventCreate(&h->ev1));
   cleanup.armed = false;
@@ -324,9 +321,8 @@ int dexsim_bind(dexsim_t h, const DexSimBuffers* b) {
 #define GRID(h) dim3((h)->NS / 64), dim3(64), 0, (hipStream_t)stream
 #define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
 
-static int launch_publish(dexsim_t h, int gate, int full, void* stream) {
-  if (gate) k_publish<true><<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, full, h->NS, h->N);
-  else k_publish<false><<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, full, h->NS, h->N);
+static int launch_publish(dexsim_t h, int full, void* stream) {
+  k_publish<<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, full, h->NS, h->N);
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
@@ -336,29 +332,15 @@ static int launch_publish(dexsim_t h, int gate, int full, void* stream) {
 static int solve_kstage(const DexSim* h) { return h->NS <= 64 * 256 ? 4 : 2; }   // 4: (60 + 7 KMAX + 4 x 84) words x 256 B = 141 KiB
 static size_t solve_lds_bytes(int kstage) { return (size_t)SOLVE_LDS_WORDS(kstage) * 64 * sizeof(float); }
 
-static int launch_solve(dexsim_t h, int gate, int last, void* stream) {
+static int launch_solve(dexsim_t h, int last, void* stream) {
   const int ks = solve_kstage(h);
   const size_t lds = solve_lds_bytes(ks);
-  if (gate) k_solve<true><<<dim3(h->NS / 64), dim3(64), lds, (hipStream_t)stream>>>(h->arena, h->d_params, h->api.counters, h->api.stamp, last, ks, h->NS, h->N);
-  else k_solve<false><<<dim3(h->NS / 64), dim3(64), lds, (hipStream_t)stream>>>(h->arena, h->d_params, h->api.counters, h->api.stamp, last, ks, h->NS, h->N);
+  k_solve<<<dim3(h->NS / 64), dim3(64), lds, (hipStream_t)stream>>>(h->arena, h->d_params, h->api.counters, h->api.stamp, last, ks, h->NS, h->N);
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
-// one fused sub-step; `last` adds the contact-force accumulation and the publication
-static int launch_substep(dexsim_t h, int gate, int last, void* stream) {
-  const size_t lds = (size_t)FS_WORDS * 64 * sizeof(float);
-  const dim3 grid(h->NS / 64), block(448);
-  hipStream_t st = (hipStream_t)stream;
-  if (gate && last) k_substep<true, true><<<grid, block, lds, st>>>(h->arena, h->api, h->d_params, h->api.counters, h->NS, h->N);
-  else if (gate) k_substep<true, false><<<grid, block, lds, st>>>(h->arena, h->api, h->d_params, h->api.counters, h->NS, h->N);
-  else if (last) k_substep<false, true><<<grid, block, lds, st>>>(h->arena, h->api, h->d_params, h->api.counters, h->NS, h->N);
-  else k_substep<false, false><<<grid, block, lds, st>>>(h->arena, h->api, h->d_params, h->api.counters, h->NS, h->N);
-  LAUNCH_CHECK();
-  return DEXSIM_OK;
-}
-static int launch_dynamics(dexsim_t h, int gate, void* stream) {
-  if (gate) k_dynamics<true><<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, h->d_params, h->api.counters, h->api.stamp, h->NS);
-  else k_dynamics<false><<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, h->d_params, h->api.counters, h->api.stamp, h->NS);
+static int launch_dynamics(dexsim_t h, void* stream) {
+  k_dynamics<<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, h->d_params, h->api.counters, h->api.stamp, h->NS);
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
@@ -375,7 +357,7 @@ int dexsim_init_state(dexsim_t h, void* stream) {
   h->api.stamp = 1;
   k_init<<<GRID(h)>>>(h->arena, h->api, h->d_params, h->NS, h->N);
   LAUNCH_CHECK();
-  return launch_publish(h, 0, 0, stream);
+  return launch_publish(h, 0, stream);
 }
 
 int dexsim_process_actions(dexsim_t h, const float* actions, int zero_targets, void* stream) {
@@ -389,33 +371,21 @@ int dexsim_process_actions(dexsim_t h, const float* actions, int zero_targets, v
   return DEXSIM_OK;
 }
 
-// tail != 0 (gated launch of the step path only): the launch also applies phase 1 of the in-step reset and finalises
-// the step statistics, so that a control step is k_actions, k_physics4, k_post, k_physics4<gated> and nothing else
+// One physics step: substeps / 4 launches of k_physics4, then substeps % 4 of k_physics1.  The action block rides on the first
+// launch, `tail` (TAIL_POST: the post-physics block, ungated; TAIL_RESET: phase 1 of the in-step reset + the step statistics, gated)
+// on the last; the launches before the last carry TAIL_NOT_FINAL (their last body does not add to the contact statistics).
 static int physics_step(dexsim_t h, int gate_on_reset, int tail, void* stream, const float* actions = nullptr) {
-  if (h->cfg.substeps % 4 == 0) {
-    // the reference's setting (4): the whole sim.dt in one launch.  Multiples of 4 (round 3: cfg/physics/accurate.yaml = 32): one
-    // launch per four sub-steps -- the action block rides on the first launch, the post-physics block / the reset tail on the
-    // last; launches before the last carry tail bit 2 ("not final": their fourth body does not add to the contact statistics)
-    const size_t lds = (size_t)FS_WORDS * 64 * sizeof(float);
-    const dim3 grid(h->NS / 64), block(448);
-    const int n4 = h->cfg.substeps / 4;
-    for (int i = 0; i < n4; i++) {
-      const int t = i == n4 - 1 ? tail : 4;
-      const float* act = i == 0 ? actions : nullptr;
-      if (gate_on_reset) k_physics4<true><<<grid, block, lds, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, nullptr, t, h->NS, h->N);
-      else {
-        ApiPtrs api = h->api;
-        if (api.actions_copy == act) api.actions_copy = nullptr;   // `act` is __restrict__: never alias it with the copy sink
-        k_physics4<false><<<grid, block, lds, (hipStream_t)stream>>>(h->arena, api, h->d_params, h->api.counters, act, t, h->NS, h->N);
-      }
-      LAUNCH_CHECK();
-    }
-    return DEXSIM_OK;
-  }
-  // other sub-step counts: `substeps` fused launches (dynamics + contact solve + integrate); the last one also publishes
-  for (int s = 0; s < h->cfg.substeps; s++) {
-    int rc = launch_substep(h, gate_on_reset, s == h->cfg.substeps - 1, stream);
-    if (rc) return rc;
+  const size_t lds = (size_t)FS_WORDS * 64 * sizeof(float);
+  const dim3 grid(h->NS / 64), block(448);
+  const int n4 = h->cfg.substeps / 4, n = n4 + h->cfg.substeps % 4;
+  for (int i = 0; i < n; i++) {
+    const int t = i == n - 1 ? tail : TAIL_NOT_FINAL;
+    const float* act = i == 0 ? actions : nullptr;
+    ApiPtrs api = h->api;
+    if (api.actions_copy == act) api.actions_copy = nullptr;   // `act` is __restrict__: never alias it with the copy sink
+    auto* k = i < n4 ? (gate_on_reset ? k_physics4<true> : k_physics4<false>) : (gate_on_reset ? k_physics1<true> : k_physics1<false>);
+    k<<<grid, block, lds, (hipStream_t)stream>>>(h->arena, api, h->d_params, h->api.counters, act, t, h->NS, h->N);
+    LAUNCH_CHECK();
   }
   return DEXSIM_OK;
 }
@@ -427,43 +397,29 @@ int dexsim_physics_step(dexsim_t h, int gate_on_reset, void* stream) {
 
 int dexsim_post_physics(dexsim_t h, int obs_only, void* stream) {
   NEED_BOUND(h);
-  const int fused = h->cfg.substeps % 4 == 0 && !obs_only;
-  k_post<<<dim3(h->NS / 64), dim3(512), POST_LDS_BYTES, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, obs_only, fused, h->NS, h->N);
+  // fold_reset: phase 0 of the in-step reset runs inside k_post
+  k_post<<<dim3(h->NS / 64), dim3(512), POST_LDS_BYTES, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, obs_only, !obs_only, h->NS, h->N);
   LAUNCH_CHECK();
   if (obs_only) return DEXSIM_OK;
   // reset_idx(nonzero(reset_buf)) incl. the extra physics step for ALL envs (step_processor.py:109-111,
-  // reset_manager.py:180), gated on the device-side flag instead of torch.any() on the host
-  if (fused) return physics_step(h, 1, 1, stream);   // phase 0 ran inside k_post, phase 1 + statistics run in the gated launch
-  k_reset<<<GRID(h)>>>(h->arena, h->api, h->d_params, h->api.counters, nullptr, 0, 0, 0, h->NS, h->N);
-  LAUNCH_CHECK();
-  int rc = physics_step(h, 1, 0, stream);
-  if (rc) return rc;
-  // phase 1 of the masked reset; its first thread also finalises the step statistics (k_finalize folded in)
-  k_reset<<<GRID(h)>>>(h->arena, h->api, h->d_params, h->api.counters, nullptr, 0, 0, 3, h->NS, h->N);
-  LAUNCH_CHECK();
-  return DEXSIM_OK;
+  // reset_manager.py:180), gated on the device-side flag instead of torch.any() on the host; phase 1 + statistics run in its
+  // last launch
+  return physics_step(h, 1, TAIL_RESET, stream);
 }
 
 int dexsim_step(dexsim_t h, const float* actions, void* stream) {
   NEED_BOUND(h);
-  if (h->cfg.substeps % 4 == 0) {
-    // actions + physics + post-physics (+ phase 0 of the in-step reset) in one launch, then the device-gated extra
-    // physics step with phase 1 of the reset and the step statistics: a control step is 2 launches
-    if (!actions) return fail(DEXSIM_ERR_ARG, "Actions cannot be None");   // action_processor.py:296-297
-    next_stamp(h);
-    h->last_actions = actions;
-    const int slot = h->timing ? ((h->timing - 1) & 63) : -1;
-    if (slot >= 0) HIP_TRY(hipEventRecord(h->tev[2 * slot], (hipStream_t)stream));
-    int rc = physics_step(h, 0, 2, stream, actions);
-    if (rc) return rc;
-    if (slot >= 0) { HIP_TRY(hipEventRecord(h->tev[2 * slot + 1], (hipStream_t)stream)); h->timing++; }
-    return physics_step(h, 1, 1, stream);
-  }
-  int rc = dexsim_process_actions(h, actions, 0, stream);   // also clears the per-step device flags
+  // actions + physics + post-physics (+ phase 0 of the in-step reset) in the ungated half, then the device-gated extra
+  // physics step with phase 1 of the reset and the step statistics: with substeps == 4 a control step is 2 launches
+  if (!actions) return fail(DEXSIM_ERR_ARG, "Actions cannot be None");   // action_processor.py:296-297
+  next_stamp(h);
+  h->last_actions = actions;
+  const int slot = h->timing ? ((h->timing - 1) & 63) : -1;
+  if (slot >= 0) HIP_TRY(hipEventRecord(h->tev[2 * slot], (hipStream_t)stream));
+  int rc = physics_step(h, 0, TAIL_POST, stream, actions);
   if (rc) return rc;
-  rc = dexsim_physics_step(h, 0, stream);
-  if (rc) return rc;
-  return dexsim_post_physics(h, 0, stream);
+  if (slot >= 0) { HIP_TRY(hipEventRecord(h->tev[2 * slot + 1], (hipStream_t)stream)); h->timing++; }
+  return physics_step(h, 1, TAIL_RESET, stream);
 }
 
 int dexsim_reset_idx(dexsim_t h, const int64_t* env_ids, int k, void* stream) {
@@ -472,11 +428,11 @@ int dexsim_reset_idx(dexsim_t h, const int64_t* env_ids, int k, void* stream) {
   if (k < 0 || (!env_ids && k != h->N)) return fail(DEXSIM_ERR_ARG, "dexsim_reset_idx: bad env_ids");
   const int mode = env_ids ? 1 : 2;
   dim3 grid((k + 63) / 64);
-  k_reset<<<grid, 64, 0, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, env_ids, k, mode, 0, h->NS, h->N);
+  k_reset<<<grid, 64, 0, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, env_ids, k, mode, 0, h->NS, h->N);
   LAUNCH_CHECK();
   int rc = dexsim_physics_step(h, 0, stream);
   if (rc) return rc;
-  k_reset<<<grid, 64, 0, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, env_ids, k, mode, 1, h->NS, h->N);
+  k_reset<<<grid, 64, 0, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, env_ids, k, mode, 1, h->NS, h->N);
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
@@ -496,7 +452,7 @@ int dexsim_reset(dexsim_t h, void* stream) {
 int dexsim_refresh_body_states(dexsim_t h, void* stream) {
   NEED_BOUND(h);
   if (!h->api.rigid_body_states || !h->api.contact_forces_all) return fail(DEXSIM_ERR_NOT_BOUND, "rigid_body_states / contact_forces_all not bound");
-  return launch_publish(h, 0, 1, stream);
+  return launch_publish(h, 1, stream);
 }
 
 static int ingest(dexsim_t h, const int64_t* ids, int k, int what, void* stream) {
@@ -505,7 +461,7 @@ static int ingest(dexsim_t h, const int64_t* ids, int k, int what, void* stream)
   if (!ids || k < 0) return fail(DEXSIM_ERR_ARG, "indexed set: bad env_ids");
   k_ingest<<<dim3((k + 63) / 64), 64, 0, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, ids, k, what, h->NS, h->N);
   LAUNCH_CHECK();
-  return launch_publish(h, 0, 0, stream);
+  return launch_publish(h, 0, stream);
 }
 int dexsim_set_dof_state_indexed(dexsim_t h, const int64_t* env_ids, int k, void* stream) { return ingest(h, env_ids, k, 0, stream); }
 int dexsim_set_root_state_indexed(dexsim_t h, const int64_t* env_ids, int k, void* stream) { return ingest(h, env_ids, k, 1, stream); }
@@ -514,19 +470,22 @@ static int launch_stage(dexsim_t h, int stage, void* stream) {
   if (h->cfg.joint_limit_rows && (stage == DEXSIM_STAGE_DYNAMICS || stage == DEXSIM_STAGE_SOLVE))
     return fail(DEXSIM_ERR_ARG, "the un-fused k_dynamics / k_solve test kernels do not build joint-limit rows (joint_limit_rows): use the fused path");
   switch (stage) {
-    case DEXSIM_STAGE_DYNAMICS: return launch_dynamics(h, 0, stream);
-    case DEXSIM_STAGE_SOLVE: return launch_solve(h, 0, 1, stream);
-    case DEXSIM_STAGE_PUBLISH: return launch_publish(h, 0, 0, stream);
-    case DEXSIM_STAGE_SUBSTEP: return launch_substep(h, 0, 1, stream);
+    case DEXSIM_STAGE_DYNAMICS: return launch_dynamics(h, stream);
+    case DEXSIM_STAGE_SOLVE: return launch_solve(h, 1, stream);
+    case DEXSIM_STAGE_PUBLISH: return launch_publish(h, 0, stream);
+    case DEXSIM_STAGE_SUBSTEP:   // one sub-step as its own launch, counting its contacts
+      k_physics1<false><<<dim3(h->NS / 64), dim3(448), (size_t)FS_WORDS * 64 * sizeof(float), (hipStream_t)stream>>>(
+          h->arena, h->api, h->d_params, h->api.counters, nullptr, 0, h->NS, h->N);
+      break;
     case DEXSIM_STAGE_PHYSICS: return physics_step(h, 0, 0, stream);
-    case DEXSIM_STAGE_STEP:   // the production launch of dexsim_step: actions + 4 sub-steps + post-physics, same arguments
-      if (h->cfg.substeps != 4 || !h->last_actions) return fail(DEXSIM_ERR_ARG, "DEXSIM_STAGE_STEP needs substeps == 4 and a previous dexsim_step");
-      return physics_step(h, 0, 2, stream, h->last_actions);
+    case DEXSIM_STAGE_STEP:   // the ungated half of dexsim_step: actions + all sub-steps + post-physics, same arguments
+      if (!h->last_actions) return fail(DEXSIM_ERR_ARG, "DEXSIM_STAGE_STEP needs a previous dexsim_step");
+      return physics_step(h, 0, TAIL_POST, stream, h->last_actions);
     case DEXSIM_STAGE_POST: k_post<<<dim3(h->NS / 64), dim3(512), POST_LDS_BYTES, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, 0, 0, h->NS, h->N); break;
     case DEXSIM_STAGE_POST + 100: k_post<<<dim3(h->NS / 64), dim3(512), POST_LDS_BYTES, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, 1, 0, h->NS, h->N); break;
     case DEXSIM_STAGE_RESET:   // both phases for the flagged envs, without the device-side gate and without physics
-      k_reset<<<GRID(h)>>>(h->arena, h->api, h->d_params, h->api.counters, nullptr, 0, 3, 0, h->NS, h->N);
-      k_reset<<<GRID(h)>>>(h->arena, h->api, h->d_params, h->api.counters, nullptr, 0, 3, 1, h->NS, h->N);
+      k_reset<<<GRID(h)>>>(h->arena, h->api, h->d_params, nullptr, 0, 3, 0, h->NS, h->N);
+      k_reset<<<GRID(h)>>>(h->arena, h->api, h->d_params, nullptr, 0, 3, 1, h->NS, h->N);
       break;
     case DEXSIM_STAGE_FINALIZE:   // closes a staged control step and opens the next one
       k_finalize<<<1, 64, 0, (hipStream_t)stream>>>(h->api, h->d_params, h->N);

@@ -81,7 +81,7 @@ struct DevParams {
   unsigned obs_div_magic; // ceil(2^32 / num_obs): idx / num_obs == umulhi(idx, magic) for idx < 2^16 (obs_buf flush)
   int inertia_diag;  // every finger link's inertia is diagonal in its joint frame (host-side check of the model): rotate_inertia_diag
   float hand_reach;  // bound on |x - o5| over every point x of every hand capsule, for any joint configuration
-                     // (o5 = origin of the palm joint frame): the hand-level broadphase of k_substep
+                     // (o5 = origin of the palm joint frame): the hand-level broadphase of substep_body
   int obs_col_row[DEXSIM_OBS_ALL_DIM]; // obs_buf column -> obs_all row (flattened policy_observation_keys)
   JC jc[DEXSIM_NJ];  // packed copy of the per-joint model constants
   Arena arena;       // field pointers (filled by dexsim_bind): kernels with long live ranges read them on demand

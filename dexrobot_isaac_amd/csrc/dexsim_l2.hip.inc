@@ -702,7 +702,7 @@ __constant__ int c_post_task_wave[POST_NTASK] = {0, 1, 2, 3, 4, 4, 6, 2, 3, 5, 5
 __constant__ int c_post_task_wave7[POST_NTASK] = {0, 0, 3, 0, 4, 5, 1, 1, 2, 3, 4, 5};
 
 // W wavefronts per 64 envs (8 in the stand-alone launch).  fold_reset: the step path applies phase 0 of the in-step
-// reset (k_reset mode 0) to the flagged envs right here, after the observations of the terminal state are assembled,
+// reset to the flagged envs right here, after the observations of the terminal state are assembled,
 // instead of in a launch of its own.
 DI void post_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, int* __restrict__ cnt, float* s_ob,
                    int obs_only, int fold_reset, int N, int NR, int done_mask) {
@@ -848,8 +848,8 @@ DI void finalize_stats(const ApiPtrs& T, const DevParams* __restrict__ P, int NR
 }
 
 // ------------------------------------------------------------------------------------------------- reset
-// mode 0: reset envs whose reset_flag is set (in-step reset);  mode 1: reset the envs listed in ids[0..k);
-// mode 2: reset envs 0..k;  mode 3: like 0 without the device-side gate
+// mode 1: reset the envs listed in ids[0..k);  mode 2: reset envs 0..k;  mode 3: reset envs whose reset_flag is set, without the
+// device-side gate (staged tests; the step path runs the in-step reset inside k_post and the gated physics launch)
 // phase 0: TerminationManager.reset_tracking + ResetManager.reset_idx up to reset_targets;
 // phase 1: ObservationEncoder.reset_observer_state (after the extra physics step).
 // ObservationEncoder.reset_observer_state (after the extra physics step)
@@ -927,14 +927,10 @@ DI void reset_phase0(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   }
 }
 
-__global__ __launch_bounds__(64) void k_reset(Arena A, ApiPtrs T, const DevParams* __restrict__ P, const int* __restrict__ cnt,
-                                              const int64_t* __restrict__ ids, int k, int mode, int phase, int N, int NR) {
+__global__ __launch_bounds__(64) void k_reset(Arena A, ApiPtrs T, const DevParams* __restrict__ P, const int64_t* __restrict__ ids, int k,
+                                              int mode, int phase, int N, int NR) {
   int e = blockIdx.x * 64 + threadIdx.x;
-  // phase bit 1: the statistics finalisation (k_finalize) folded into this launch
-  if ((phase & 2) && blockIdx.x == 0 && threadIdx.x == 0) finalize_stats(T, P, NR);
-  phase &= 1;
-  if (mode == 0 || mode == 3) {   // 3: flagged envs without the device-side gate (staged tests)
-    if (mode == 0 && cnt[CNT_ANY_RESET] != T.stamp) return;
+  if (mode == 3) {
     if (e >= NR || FLD(reset_flag, 0) == 0) return;
   } else {
     if (e >= k) return;

@@ -3,9 +3,10 @@
 // Replaces gym.simulate + gym.fetch_results (reference components/physics/physics_manager.py:92-99) for the
 // 26-DOF fixed-base DexHand + free box + ground plane.  One env per lane, 64 envs per wavefront, lockstep.
 //
-//   k_physics4 / k_substep (substep_body): the production path -- a whole sim.dt (4 sub-steps) or one sub-step in one launch,
-//                seven wavefronts per 64 envs: articulated dynamics in block / Schur form (CRBA in momentum form finger by
-//                finger, RNEA bias, implicit-PD factorisation
+//   k_physics4 / k_physics1 (substep_body): the production path -- four sub-steps or one sub-step in one launch (a physics
+//                step is substeps / 4 launches of k_physics4, then substeps % 4 of k_physics1), seven wavefronts per 64 envs:
+//                articulated dynamics in block / Schur form (CRBA in momentum form finger by finger, RNEA bias, implicit-PD
+//                factorisation
 //                  Mhat = [B C; C^T F] = L^T diag(S, F_0..F_4) L ,  L = [I 0; G I],  G_f = Fhat_f^-1 C_f^T),
 //                free velocity in the decoupled coordinates u = L qd, capsule / box / plane narrowphase, contact rows in
 //                u-space (t = j_B - G_f^T j_f, S^-1 t, Fhat_f^-1 j_f, 1/D), the warm-started block solver (every hand
@@ -1043,15 +1044,12 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
   }
 }
 
-// GATED = the reference's conditional extra physics step (reset_manager.py:180): the launch is a no-op unless the
-// device-side "some env reset in this control step" flag is set -- no host synchronisation.
-template <bool GATED>
+// (cnt, stamp: not read -- the stand-alone kernels never run gated -- but kept, so the kernel-argument layout stays as it was)
 __global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __restrict__ P, const int* __restrict__ cnt, int stamp, int N) {
   __shared__ __attribute__((aligned(16))) float sh[(DL_WORDS + 1) * 64];   // + 1: the env's split counts (wave 5 -> the row builders); 16-byte aligned: S^-1 is stored as quads
   constexpr int dlb = DL_PERSIST;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int e = blockIdx.x * 64 + lane;   // N is the padded stride: every lane owns a (possibly dummy) env
-  if (GATED && cnt[CNT_ANY_RESET] != stamp) return;
   const DexHandModel& M = P->model;
   const DexSimConfig& C = P->cfg;
   const V3 grav = v3p(C.gravity);
@@ -1451,15 +1449,13 @@ DI void integrate_box(const Arena& A, float h, const float* vb, const float* wb,
   FLD(box_quat, 0) = qn.x / l; FLD(box_quat, 1) = qn.y / l; FLD(box_quat, 2) = qn.z / l; FLD(box_quat, 3) = qn.w / l;
 }
 
-// Stand-alone contact-solve kernel (profiling / staged tests; production runs the fused k_substep below):
+// Stand-alone contact-solve kernel (profiling / staged tests; production runs the fused k_physics4 / k_physics1 below):
 // reads u_free, headers and rows from the arena, stages them in LDS, sweeps, integrates.
-template <bool GATED>
 __global__ __launch_bounds__(64) void k_solve(Arena A, const DevParams* __restrict__ P, int* __restrict__ cnt, int stamp, int last,
                                               int kstage, int N, int NR) {
   extern __shared__ float lds[];
   const int lane = threadIdx.x;
   const int e = blockIdx.x * 64 + lane;
-  if (GATED && cnt[CNT_ANY_RESET] != stamp) return;
   float* s_uf = lds;                         // [20][64]  finger velocities in u-space (+ [20] block copy, [20] block changes)
   float* s_lam = lds + 60 * 64;              // [KMAX*3][64]  impulses
   float* s_hdr = lds + (60 + DEXSIM_KMAX * 3) * 64;   // [KMAX*4][64]  per contact: code, finger offset, mu, bias
@@ -1611,7 +1607,7 @@ __global__ __launch_bounds__(64) void k_solve(Arena A, const DevParams* __restri
     FLD(wgen, 0) = DEXSIM_WGEN_NEXT(gen);
   }
 
-  if (last) solve_forces(A, P, GATED ? nullptr : cnt + (stamp & 1), s_hdr, s_lam, s_row /* dead by now */, nc, lane, N, e, NR);
+  if (last) solve_forces(A, P, cnt + (stamp & 1), s_hdr, s_lam, s_row /* dead by now */, nc, lane, N, e, NR);
 
   // back-substitution qd = L^-1 u, semi-implicit Euler, joint-limit clamp
 #pragma unroll
@@ -1794,10 +1790,8 @@ DI void publish_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   if (real && w5 && root_wave == 5) put_roots();
 }
 
-template <bool GATED>
 __global__ __launch_bounds__(384) void k_publish(Arena A, ApiPtrs T, const DevParams* __restrict__ P, const int* __restrict__ cnt,
                                                  int full_bodies_req, int N, int NR) {
-  if (GATED && cnt[CNT_ANY_RESET] != T.stamp) return;
   publish_body(A, T, P, full_bodies_req, N, NR);
 }
 
@@ -2876,43 +2870,52 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
 #undef PH2_STAMP
 }
 
-template <bool GATED, bool LAST>
-__global__ __launch_bounds__(448) void k_substep(Arena A, ApiPtrs T, const DevParams* __restrict__ P, int* __restrict__ cnt, int N, int NR) {
-  extern __shared__ float sh[];
-  if (GATED && cnt[CNT_ANY_RESET] != T.stamp) return;
-  if (threadIdx.x < 6) sh[(FS_FLAG + threadIdx.x) * 64] = 0.f;
-  if (threadIdx.x == 6) sh[FS_COMPCNT * 64] = 0.f;
-  __syncthreads();
-  SubstepCarry K;   // (a single body: nothing carried)
-  substep_body<LAST>(A, T, P, cnt, N, NR, sh, 1, 0, false, !GATED, K, false, false);
-}
-
 DI void reset_phase1(const Arena& A, int N, int e);                                      // dexsim_l2.hip.inc
 DI void finalize_stats(const ApiPtrs& T, const DevParams* __restrict__ P, int NR);
 DI void post_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, int* __restrict__ cnt, float* s_ob,
                    int obs_only, int fold_reset, int N, int NR, int done_mask);
 DI void actions_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, const float* __restrict__ act, int N, int NR);
 
+// `tail` of a physics launch (host and kernels): what runs behind its last sub-step body
+enum {
+  TAIL_RESET = 1,       // gated launch: phase 1 of the in-step reset (after the extra physics step) + step statistics
+  TAIL_POST = 2,        // ungated launch of dexsim_step: the whole post-physics block (observations, termination, rewards, phase 0
+                        // of the in-step reset; k_post's body on the same 6 waves and the same LDS) runs right behind the last
+                        // sub-step -- the state it reads is still in this CU's L1/L2 and one more kernel boundary disappears
+  TAIL_NOT_FINAL = 4,   // not the last launch of a physics step: its last body does not add to the contact statistics
+};
+
+// The two ends that k_physics4 and k_physics1 share.  The big blocks between them -- actions_block, post_block -- are called by
+// the kernels themselves: inlined through a helper of their own, they change k_physics4's code (post_block: 36 B of scratch).
+// Prologue: start of the probe's launch time, the broadphase tokens (waves 0-5 -> wave 6, see substep_body).
+template <bool GATED>
+DI unsigned long long physics_prologue(const ApiPtrs& T, float* sh) {
+  unsigned long long pr_k0 = 0;
+  if (T.probe && threadIdx.x == 0) pr_k0 = __builtin_amdgcn_s_memtime();
+  if (threadIdx.x < 6) sh[(FS_FLAG + threadIdx.x) * 64] = 0.f;
+  if (threadIdx.x == 6) sh[FS_COMPCNT * 64] = 0.f;
+  return pr_k0;
+}
+// Epilogue: the gated launch closes the control step with the statistics of TerminationManager.evaluate (was k_finalize); the
+// ungated one adds its launch time to the probe.
+template <bool GATED>
+DI void physics_epilogue(const ApiPtrs& T, const DevParams* __restrict__ P, int tail, unsigned long long pr_k0, int NR) {
+  if (GATED && (tail & TAIL_RESET) && blockIdx.x == 0 && threadIdx.x == 0) finalize_stats(T, P, NR);
+  if (!GATED && T.probe && threadIdx.x == 0) atomicAdd(T.probe + blockIdx.x * 4 + 1, (unsigned)(__builtin_amdgcn_s_memtime() - pr_k0));
+}
+
 // One sim.dt (4 sub-steps, the reference's and BASELINE's setting) in ONE launch: the four bodies are inlined back to
 // back (straight-line code, no loop-carried registers -- unlike the rejected runtime loop), separated by workgroup
 // barriers; envs are private to their workgroup, so no grid-wide ordering is needed.  Versus four launches this
 // removes three kernel boundaries (~2.7 us each on this part: dispatch + the L2 writeback / invalidate that makes
 // every first touch of the next kernel an Infinity-Cache / HBM miss, ~4k cycles).
-template <bool GATED>
-// tail (bit 2: not the last launch of a physics step of 8, 12, ... sub-steps: no contact statistics).
-// tail (bit 0, gated launch): phase 1 of the in-step reset + step statistics.  tail (bit 1, ungated launch of
-// dexsim_step): the whole post-physics block (observations, termination, rewards, phase 0 of the in-step reset; k_post's
-// body on the same 6 waves and the same LDS) runs right behind the last sub-step -- the state it reads is still in this
-// CU's L1/L2 and one more kernel boundary disappears.
-// act != nullptr (ungated launch of dexsim_step): ActionProcessor.process_actions runs first, three action channels per
+// act != nullptr (ungated first launch of dexsim_step): ActionProcessor.process_actions runs first, three action channels per
 // wavefront (k_actions' arithmetic, channel by channel), so that the whole control step up to the reset gate is ONE launch.
+template <bool GATED>
 __global__ __launch_bounds__(448) void k_physics4(Arena A, ApiPtrs T, const DevParams* __restrict__ P, int* __restrict__ cnt,
                                                   const float* __restrict__ act, int tail, int N, int NR) {
   extern __shared__ float sh[];
-  unsigned long long pr_k0 = 0;
-  if (T.probe && threadIdx.x == 0) pr_k0 = __builtin_amdgcn_s_memtime();
-  if (threadIdx.x < 6) sh[(FS_FLAG + threadIdx.x) * 64] = 0.f;
-  if (threadIdx.x == 6) sh[FS_COMPCNT * 64] = 0.f;   // broadphase tokens (waves 0-5 -> wave 6), see substep_body
+  const unsigned long long pr_k0 = physics_prologue<GATED>(T, sh);
   if (!GATED && act) actions_block(P->arena, T, P, act, N, NR);
   __syncthreads();   // targets are read by every wave of the first sub-step
   if (!GATED || cnt[CNT_ANY_RESET] == T.stamp) {
@@ -2923,18 +2926,39 @@ __global__ __launch_bounds__(448) void k_physics4(Arena A, ApiPtrs T, const DevP
     __syncthreads();
     substep_body<false>(P->arena, T, P, cnt, N, NR, sh, 3, 192, false, true, K, true, true);
     __syncthreads();
-    substep_body<true>(P->arena, T, P, cnt, N, NR, sh, 4, 256, !GATED && (tail & 2), !GATED && !(tail & 4), K, true, false);
-    if (!GATED && (tail & 2)) {
+    substep_body<true>(P->arena, T, P, cnt, N, NR, sh, 4, 256, !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, true, false);
+    if (!GATED && (tail & TAIL_POST)) {
       __syncthreads();     // publication (site poses, hand twist) -> observations; LDS changes hands
       post_block(P->arena, T, P, cnt, sh, 0, 1, N, NR, POST_PRE_MASK);
     }
-    if (GATED && (tail & 1)) {   // phase 1 of the in-step reset (after the extra physics step)
+    if (GATED && (tail & TAIL_RESET)) {   // phase 1 of the in-step reset (after the extra physics step)
       const int e = blockIdx.x * 64 + (threadIdx.x & 63);
       if (threadIdx.x < 64 && e < NR && A.reset_flag[e] != 0) reset_phase1(A, N, e);
     }
   }
-  // the gated launch closes the control step: statistics of TerminationManager.evaluate (was k_finalize)
-  if (GATED && (tail & 1) && blockIdx.x == 0 && threadIdx.x == 0) finalize_stats(T, P, NR);
-  if (!GATED && T.probe && threadIdx.x == 0) atomicAdd(T.probe + blockIdx.x * 4 + 1, (unsigned)(__builtin_amdgcn_s_memtime() - pr_k0));
+  physics_epilogue<GATED>(T, P, tail, pr_k0, NR);
 }
 
+// One sub-step in one launch, the same launch otherwise: the substeps % 4 sub-steps at the end of a physics step, and
+// DEXSIM_STAGE_SUBSTEP.
+template <bool GATED>
+__global__ __launch_bounds__(448) void k_physics1(Arena A, ApiPtrs T, const DevParams* __restrict__ P, int* __restrict__ cnt,
+                                                  const float* __restrict__ act, int tail, int N, int NR) {
+  extern __shared__ float sh[];
+  const unsigned long long pr_k0 = physics_prologue<GATED>(T, sh);
+  if (!GATED && act) actions_block(P->arena, T, P, act, N, NR);
+  __syncthreads();
+  if (!GATED || cnt[CNT_ANY_RESET] == T.stamp) {
+    SubstepCarry K;   // (a single body: nothing carried)
+    substep_body<true>(P->arena, T, P, cnt, N, NR, sh, 1, 0, !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, false, false);
+    if (!GATED && (tail & TAIL_POST)) {
+      __syncthreads();
+      post_block(P->arena, T, P, cnt, sh, 0, 1, N, NR, POST_PRE_MASK);
+    }
+    if (GATED && (tail & TAIL_RESET)) {
+      const int e = blockIdx.x * 64 + (threadIdx.x & 63);
+      if (threadIdx.x < 64 && e < NR && A.reset_flag[e] != 0) reset_phase1(A, N, e);
+    }
+  }
+  physics_epilogue<GATED>(T, P, tail, pr_k0, NR);
+}

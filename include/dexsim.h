@@ -340,9 +340,10 @@ int dexsim_physics_step(dexsim_t h, int gate_on_reset, void* stream);
 int dexsim_post_physics(dexsim_t h, int obs_only, void* stream);
 
 /* DexHandBase.step (dexhand_base.py:893-942): process_actions, physics, post-physics, in-step resets,
- * conditional extra physics step, extras statistics.  No host synchronisation.  With substeps == 4 this is two
- * launches: one kernel carrying the whole control step up to the reset gate, and its device-gated twin (the extra
- * physics step + reset phase 1 + statistics); other sub-step counts go through the three staged calls above. */
+ * conditional extra physics step, extras statistics.  No host synchronisation.  Two halves of substeps / 4 + substeps % 4
+ * launches each (with substeps == 4: two launches): the ungated half carries the whole control step up to the reset gate
+ * (actions on its first launch, post-physics on its last), its device-gated twin the extra physics step, with reset
+ * phase 1 and the statistics on its last launch.  Same results as the three staged calls above. */
 int dexsim_step(dexsim_t h, const float* actions, void* stream);
 
 /* DexHandBase.reset_idx (dexhand_base.py:743-803) for caller-chosen envs: env_ids is a device array
@@ -384,8 +385,8 @@ int dexsim_set_stats_sink(dexsim_t h, float* dst);
 int dexsim_set_obs_dict_mode(dexsim_t h, int mode);
 
 /* Phase probe (measurement, SURVEY.md 8d: the contact-solve sub-metric on the PRODUCTION kernel): with `buf` set --
- * 4 x ceil(num_envs / 64) uint32 on the device, zeroed by the caller -- every following physics launch of the 4-sub-step path
- * adds, per workgroup, shader-clock ticks (s_memtime) to buf[4 w + 0] = phases 3 + 4 of the general contact path (contact rows +
+ * 4 x ceil(num_envs / 64) uint32 on the device, zeroed by the caller -- every following physics launch adds, per workgroup,
+ * shader-clock ticks (s_memtime) to buf[4 w + 0] = phases 3 + 4 of the general contact path (contact rows +
  * the block solver's sweeps), [4 w + 1] = the whole launch (ungated launches), [4 w + 3] = phase 4 alone, and counts in
  * [4 w + 2] the sub-steps that ran the general path.  Solver time = launch time (HIP events) x buf[0] / buf[1].  NULL switches it
  * off (the default; the probe then costs two scalar branches per sub-step). */
@@ -403,10 +404,10 @@ int dexsim_set_action_copy(dexsim_t h, float* dst);
 #define DEXSIM_STAGE_POST     3  /* fused obs + FSM + termination + reward                          */
 #define DEXSIM_STAGE_RESET    4  /* masked reset of envs whose reset_buf is set                     */
 #define DEXSIM_STAGE_FINALIZE 5  /* statistics                                                      */
-#define DEXSIM_STAGE_SUBSTEP  6  /* one sub-step (DYNAMICS + SOLVE + integration + publication) as its own launch */
-#define DEXSIM_STAGE_PHYSICS  7  /* physics step alone: all `substeps` of a sim.dt (one launch when substeps == 4)      */
-#define DEXSIM_STAGE_STEP     8  /* the launch dexsim_step issues: actions + 4 sub-steps + post-physics (re-uses the    */
-                                 /* action pointer of the last dexsim_step; advances the simulation)                    */
+#define DEXSIM_STAGE_SUBSTEP  6  /* one sub-step (DYNAMICS + SOLVE + integration + publication, contact statistics) as its own launch */
+#define DEXSIM_STAGE_PHYSICS  7  /* physics step alone: all `substeps` of a sim.dt (substeps / 4 + substeps % 4 launches) */
+#define DEXSIM_STAGE_STEP     8  /* the ungated half of dexsim_step: actions + all sub-steps + post-physics (re-uses  */
+                                 /* the action pointer of the last dexsim_step; advances the simulation)                */
 int dexsim_run_stage(dexsim_t h, int stage, void* stream);
 
 /* Time `launches` launches of one stage, each bracketed by a hipEvent pair and a host synchronisation, and return the
@@ -414,9 +415,9 @@ int dexsim_run_stage(dexsim_t h, int stage, void* stream);
  * (bench.py uses them for the stand-alone kernels only). */
 int dexsim_time_stage(dexsim_t h, int stage, int launches, void* stream, float* mean_us);
 
-/* In-situ timing of the main launch of dexsim_step (k_physics4 with the action and post-physics blocks when
- * substeps == 4): enable != 0 starts recording a hipEvent pair around that launch on every following dexsim_step
- * (ring of 64, no host synchronisation, so the launches stay back to back as in production); enable == 0 stops,
+/* In-situ timing of the ungated half of dexsim_step (the launches that carry the actions, the sub-steps and the
+ * post-physics block; one launch when substeps == 4): enable != 0 starts recording a hipEvent pair around it on every
+ * following dexsim_step (ring of 64, no host synchronisation, so the launches stay back to back as in production); enable == 0 stops,
  * synchronises and returns the mean duration in microseconds over the *n recorded steps.  (The event fences still
  * cost the kernel its warm L2: +30 % on MI355X; bench.py therefore times the whole region instead.) */
 int dexsim_step_timing(dexsim_t h, int enable, float* mean_us, int* n);

@@ -10,7 +10,7 @@ from dexrobot_isaac_amd.core import DexSimCore
 
 class HipBackend:
     def __init__(self, sim_cfg, model_struct, device="cuda:0", fused=True):
-        self.fused = fused        # True: production k_substep; False: stand-alone k_dynamics + k_solve
+        self.fused = fused        # True: the production sub-step (k_physics1); False: stand-alone k_dynamics + k_solve
         self.core = DexSimCore(sim_cfg, model_struct, device)
         self.n = self.core.N
         self._posted = False

@@ -485,7 +485,7 @@ def test_step_timing_and_step_stage_entry_points():
 
 @pytest.mark.parametrize("near_box", [False, True], ids=["hand_clear", "contacts"])
 def test_fused_physics_launch_equals_four_single_substep_launches(near_box):
-    """k_physics4 inlines the sub-step body four times; four k_substep launches run the same body once each.  State after
+    """k_physics4 inlines the sub-step body four times; four k_physics1 launches run the same body once each.  State after
     one sim.dt must be bit-identical (the early box solve splits its sweeps around a barrier but performs the same
     arithmetic sequence; contact forces do not feed back)."""
     import torch
@@ -700,16 +700,20 @@ def test_hip_error_is_a_small_multiple_of_fp32_roundoff():
         assert r[3] <= c * r[2] + 1e-6, (f, r)
 
 
-@pytest.mark.parametrize("task", ["BlindGrasping", "BaseTask"])
-def test_fused_step_equals_staged_step_bitwise(task):
-    """dexsim_step (one fused launch: action block + 4 sub-steps + post block on 7 waves, then the gated twin) against the
-    three staged calls (k_actions, k_physics4 without the blocks, k_post on 8 waves + gated launch) from identical state,
-    over steps that include in-step resets: every output and the whole carried state must be BIT-identical -- the fused
-    production post block is thereby tied to the stand-alone stages that the golden replays exercise."""
+@pytest.mark.parametrize("task,substeps", [("BlindGrasping", 4), ("BaseTask", 4), ("BlindGrasping", 2), ("BaseTask", 2),
+                                            ("BlindGrasping", 6), ("BaseTask", 6)],
+                         ids=["BlindGrasping", "BaseTask", "BlindGrasping-2", "BaseTask-2", "BlindGrasping-6", "BaseTask-6"])
+def test_fused_step_equals_staged_step_bitwise(task, substeps):
+    """dexsim_step (the physics launches with the action block on the first and the post block on 7 waves on the last, then
+    the gated twin; with 4 sub-steps one launch each) against the three staged calls (k_actions, the physics launches without
+    the blocks, k_post on 8 waves + the gated physics step) from identical state, over steps that include in-step resets:
+    every output and the whole carried state must be BIT-identical -- the fused production post block is thereby tied to the
+    stand-alone stages that the golden replays exercise."""
     import torch
     from tests.hip_backend import HipBackend
     n = 200                                                  # 4 workgroups, the last one padded
-    sc, model = _mk(task, n, **{"env.episodeLength": 7})
+    sc, model = _mk(task, n, **{"env.episodeLength": 7, "sim.substeps": substeps})
+    assert int(sc.substeps) == substeps
     ms = model.to_struct()
     a, b = HipBackend(sc, ms), HipBackend(sc, ms)
     a.reset(); b.reset()
@@ -876,14 +880,13 @@ def test_generic_sweep_variants_match_oracle(z):
 
 @pytest.mark.parametrize("substeps,iters", [(2, 8), (6, 16), (8, 32), (32, 32)],
                          ids=["physics=fast", "6 sub-steps (staged)", "8 sub-steps / 32 iterations", "physics=accurate"])
-def test_other_substep_counts_use_the_staged_path(substeps, iters):
+def test_other_substep_counts_match_oracle(substeps, iters):
     """cfg/physics/fast.yaml (substeps 2, 8 position iterations), a heavier setting in the direction of
     cfg/physics/accurate.yaml, and accurate.yaml itself at its real 32 sub-steps x 32 iterations (round 3; timed by
-    `bench.py --substeps 32 --iterations 32`).  Multiples of 4 run as one fused launch per four sub-steps (round 3: the action
-    block on the first launch, the post-physics block / reset tail on the last; 32 sub-steps = 8 + 8 launches instead of 32 + 32
-    + the stage kernels); the other counts run dexsim_step as
-    the staged launches (k_actions, `substeps` x k_substep, k_post, k_reset, gated physics, k_reset).  Whole control steps
-    with in-step resets against the oracle; the integer bookkeeping must agree exactly."""
+    `bench.py --substeps 32 --iterations 32`).  A physics step is substeps / 4 k_physics4 launches, then substeps % 4 k_physics1
+    launches: the action block on the first launch, the post-physics block / reset tail on the last (32 sub-steps = 8 + 8
+    launches, 2 sub-steps = 2 + 2, 6 = 3 + 3).  Whole control steps with in-step resets against the oracle; the integer
+    bookkeeping must agree exactly."""
     from oracle.oracle import Oracle
     from tests.hip_backend import HipBackend
     n = 130
