@@ -15,6 +15,11 @@
 #include "dexsim_l2.hip.inc"
 // clang-format on
 
+// The post block runs in the sub-step kernels' LDS behind their last body (TAIL_POST); the box wave starts its tile during the
+// publication (post_pre_tasks).
+static_assert(lds_map_conflict({0, (int)((POST_LDS_BYTES + 64 * sizeof(float) - 1) / (64 * sizeof(float))), LIVE_PUB | LIVE_POST}) < 0,
+              "the post block's LDS does not fit into the sub-step kernels' or overlaps a region live during the publication / post block");
+
 static thread_local std::string g_last_error;
 
 static int fail(int code, const char* what) {
@@ -263,12 +268,12 @@ int dexsim_create(const DexSimConfig* cfg, const DexHandModel* model, int device
     for (int i = 3; i < 6; i++) if (model->inertia[j][i] != 0.f) hp.inertia_diag = 0;
   HIP_TRY(hipMalloc(&h->d_params, sizeof(DevParams)));
   HIP_TRY(hipMemcpy(h->d_params, &hp, sizeof(DevParams), hipMemcpyHostToDevice));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_post), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics1<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics1<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_post), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics1<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics1<true>), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
   HIP_TRY(hipEventCreate(&h->ev0));
   HIP_TRY(hipEventCreate(&h->ev1));
   cleanup.armed = false;
@@ -375,7 +380,7 @@ int dexsim_process_actions(dexsim_t h, const float* actions, int zero_targets, v
 // launch, `tail` (TAIL_POST: the post-physics block, ungated; TAIL_RESET: phase 1 of the in-step reset + the step statistics, gated)
 // on the last; the launches before the last carry TAIL_NOT_FINAL (their last body does not add to the contact statistics).
 static int physics_step(dexsim_t h, int gate_on_reset, int tail, void* stream, const float* actions = nullptr) {
-  const size_t lds = (size_t)FS_WORDS * 64 * sizeof(float);
+  const size_t lds = FS_LDS_BYTES;
   const dim3 grid(h->NS / 64), block(448);
   const int n4 = h->cfg.substeps / 4, n = n4 + h->cfg.substeps % 4;
   for (int i = 0; i < n; i++) {
@@ -474,7 +479,7 @@ static int launch_stage(dexsim_t h, int stage, void* stream) {
     case DEXSIM_STAGE_SOLVE: return launch_solve(h, 1, stream);
     case DEXSIM_STAGE_PUBLISH: return launch_publish(h, 0, stream);
     case DEXSIM_STAGE_SUBSTEP:   // one sub-step as its own launch, counting its contacts
-      k_physics1<false><<<dim3(h->NS / 64), dim3(448), (size_t)FS_WORDS * 64 * sizeof(float), (hipStream_t)stream>>>(
+      k_physics1<false><<<dim3(h->NS / 64), dim3(448), FS_LDS_BYTES, (hipStream_t)stream>>>(
           h->arena, h->api, h->d_params, h->api.counters, nullptr, 0, h->NS, h->N);
       break;
     case DEXSIM_STAGE_PHYSICS: return physics_step(h, 0, 0, stream);

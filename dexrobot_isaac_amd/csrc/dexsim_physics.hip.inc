@@ -66,9 +66,9 @@ DI int code_info(const DexHandModel& M, int cap) {
 // constraint J = +-e_j on finger joint j = (CODE_FINGER, CODE_LEVEL), CODE_SAMPLE = side (0 lower: +e_j, 1 upper: -e_j), gap = distance
 // to the limit, no friction, no geometry (p = n = 0).  It is a hand block of its finger like a contact; it is not a contact in the
 // statistics and exerts no body force.
-// Split counts of a lane's env, packed (wave 5, phase 2 -> FS_SPLIT): bits [3:0] nB = solver blocks with hand contacts (<= 12),
-// [7:4] nX = blocks touching the box, [11:8] .. [27:24] nF of finger 0 .. 4 = blocks holding contacts of that finger, [28] log2 of
-// the run length (0: every hand contact its own block, 1: pairs)
+// Split counts of a lane's env, packed (phase 2: wave 0 -> FS_SPLIT; k_dynamics: wave 5 -> DL_SPLIT): bits [3:0] nB = solver blocks
+// with hand contacts (<= 12), [7:4] nX = blocks touching the box, [11:8] .. [27:24] nF of finger 0 .. 4 = blocks holding contacts of
+// that finger, [28] log2 of the run length (0: every hand contact its own block, 1: pairs)
 #define SPLIT_NB(s) ((s) & 15)
 #define SPLIT_NX(s) (((s) >> 4) & 15)
 #define SPLIT_NF(s, f) (((s) >> (8 + 4 * (f))) & 15)
@@ -257,18 +257,7 @@ DI void collide_capsules3(const Arena& A, int N, int e, int& nc, const DexSimCon
 // Version 1 ran the five fingers sequentially in one wave (64 us at N=4096, a single wave per CU); the fingers
 // are independent sub-trees given the base chain, so they map onto separate wavefronts without changing the
 // arithmetic.  Every wave recomputes the 6-joint base chain (cheap) instead of synchronising on it.
-// persistent words first, then the per-finger hand-off block at word offset `dlb` (dead after phase 2)
-#define DL_SINV 0                          /* 36: Schur complement inverse (hand-clear fused sub-step: the helpers' shares of S, bias, sum G^T tau) */
-#define DL_PALM 36                         /* 16: palm composite (comp_put form) + wrench */
-#define DL_NC 52                           /*  1: contact count                    */
-#define DL_PERSIST 53
-#define DL_SSUB(f) (dlb + (f) * 43)        /* 21: C_f G_f, lower triangle          */
-#define DL_GSUM(f) (dlb + (f) * 43 + 21)   /*  6: G_f^T tau_f                      */
-#define DL_COMP(f) (dlb + (f) * 43 + 27)   /* 10: composite of the finger: m, c - o5, I about o5 (comp_put) */
-#define DL_WRENCH(f) (dlb + (f) * 43 + 37) /*  6: RNEA wrench about o5             */
-#define DL_CAPS(f) (dlb + 215 + (f) * 18)  /* 18: 3 capsules x (e0, e1)            */
-#define DL_HANDOFF 305
-#define DL_WORDS (DL_PERSIST + DL_HANDOFF)
+// (LDS words: the LDS map below.)
 
 struct BaseChain {
   V3 ab[6], ob[6];
@@ -394,13 +383,138 @@ DI void bch_get2(const float* s_bch, int lane, int i2, V3& a0, V3& o0, V3& a1, V
   a0 = {q0.x, q0.y, q0.z}; o0 = {q0.w, q1.x, q1.y}; a1 = {q1.z, q1.w, q2.x}; o1 = {q2.y, q2.z, q2.w};
 }
 
+// ---- LDS map of the sub-step kernels
+// The waves of a workgroup hand data to each other through LDS laid out [word][lane]: word w of lane l is sh[w * 64 + l] (bank =
+// lane: conflict-free for any per-lane index).  k_dynamics holds the persistent words, the per-finger hand-off at DL_PERSIST and
+// its split word.  k_physics4 / k_physics1 own the CU's whole LDS (FS_WORDS words; one workgroup per CU, which the LDS token waits
+// rely on, see substep_body), and most of their words serve two regions in turn.  LDS_MAP below lists every region of theirs with
+// the phases in which it is live, from its first write to its last read on any path, and the compiler checks that no two regions
+// live in a common phase share a word.  Sub-fields (DL_SCHUR_*, DL_PALM_WRENCH, FS_SPRE_BIAS, the hand-off's DL_*) lie inside
+// their region.
+
+// persistent words (k_dynamics and the fused kernels)
+#define DL_SINV 0            /* 36: S^-1, 9 quads (ROWADDR layout) for the row builders; the hand-clear fused sub-step holds instead: */
+#define DL_SCHUR_S 0         /*     21: S, lower triangle, from the split Schur phase (schur_helper, schur_row) */
+#define DL_SCHUR_GSUM 27     /*      6: sum of G_f^T tau_f (schur_helper, job 1) */
+#define DL_PALM 36           /* 16: the palm's composite (comp_put form, 10 words) and: */
+#define DL_PALM_WRENCH 46    /*      6: its RNEA wrench about o5 */
+#define DL_NC 52             /*  1: contact count (fused: | box/ground contacts << 8) */
+#define DL_PERSIST 53
+// per-finger hand-off of phases 1-2 at word b (k_dynamics: DL_PERSIST, fused: FS_ROW)
+#define DL_SSUB(b, f) ((b) + (f) * 43)         /* 21: C_f G_f, lower triangle */
+#define DL_GSUM(b, f) ((b) + (f) * 43 + 21)    /*  6: G_f^T tau_f */
+#define DL_COMP(b, f) ((b) + (f) * 43 + 27)    /* 10: composite of the finger: m, c - o5, I about o5 (comp_put) */
+#define DL_WRENCH(b, f) ((b) + (f) * 43 + 37)  /*  6: RNEA wrench about o5 */
+#define DL_CAPS(b, f) ((b) + 215 + (f) * 18)   /* 18: 3 capsules x (e0, e1) */
+#define DL_HANDOFF 305
+#define DL_WORDS (DL_PERSIST + DL_HANDOFF)
+#define DL_SPLIT DL_WORDS    /* k_dynamics: the env's split counts (wave 5, phase 2 -> the row builders) */
+
+// the fused sub-step (k_physics4 / k_physics1), by word
+#define FS_UB 53             /* u_B: free, then solved velocities of the base joints */
+#define FS_BOXV 59           /* box twist (v, w): free, then solved */
+#define FS_UF 65             /* u_f, word 4 f + l: free, then solved */
+#define FS_LAM 85            /* impulses of the KMAX list entries, 3 words each */
+#define FS_HDR 157           /* headers of the KMAX list entries, 4 words each: code, finger offset, mu, bias */
+#define FS_ROW 197           /* the per-finger hand-off (DL_SSUB .. DL_CAPS) */
+#define FS_HDR_HI 197        /* the headers from entry (FS_HDR_HI - FS_HDR) / 4 = 10 on, over the (then dead) hand-off */
+#define FS_X 253             /* block exchange of the contact solver, 13 blocks (12 hand blocks + the box/ground block 12) x 5 quads
+                                [block][quad][lane][4]: the velocity change a block made in one pass -- quad 0 = d u_B[0..3], 1 =
+                                (d u_B[4], d u_B[5], d v_box[0], d v_box[1]), 2 = d v_box[2..5], 3 = d u_f of the finger of the block's
+                                first contact, 4 = d u_f of the finger of its second contact when that is another one (pairs only) */
+#define FS_FORCE 253         /* net contact force partial sums, 3 DEXSIM_NFSLOT words per finger wave (forces_partial) */
+#define FS_T 513             /* the common velocities, 8 quads (absolute values): u_B, box twist as in FS_X, 3 + f = u_f of finger f */
+#define FS_SPRE 513          /* composite part of S, lower triangle (schur_precompute) */
+#define FS_SPRE_BIAS 534     /* bias of the base joints (schur_precompute) */
+#define FS_BCH 545           /* axes and origins of the base joints, 9 quads (ROWADDR layout, bch_get2) */
+#define FS_CTAB 581          /* work-item table, 768 entries indexed linearly: entry i = owner lane | block << 8 of the i-th hand block
+                                of the workgroup (block-major: all envs' block 0, then all envs' block 1, ...) */
+#define FS_NITEM 593         /* lane 0: number of items */
+#define FS_CMP 594           /* lever arms r = contact point - box centre of the (at most 4) box/ground contacts, 3 words each */
+#define FS_CARRY_QD 606      /* qd of the base joints, body to body (SubstepCarry) */
+#define FS_CARRY_BP 612      /* box position, body to body */
+#define FS_COMPCNT 615       /* lane 0: fingers whose composite + wrench are in LDS, counted over the bodies of the launch */
+                             /* (word 616 is free) */
+#define FS_GEN 617           /* the env's warm-start generation of this sub-step */
+#define FS_SPLIT 618         /* split counts of this sub-step, packed (split_pack) */
+#define FS_CPACK 619         /* corner index of box/ground list slot k in bits [3k+2 : 3k] */
+#define FS_CMP_INVM 620      /* 1/m, 1/I of the box */
+#define FS_FLAG 622          /* word FS_FLAG + w, w = finger 0-4 / palm 5: broadphase verdict (seq << 1) | clear in lane 0 (see
+                                substep_body); then (hand clear) the Schur helpers' tokens in lane 0 (| SCHUR_SPLIT_BIT, waves 1-3) or
+                                (else) the narrowphase counts of every lane (NP_*) */
+#define FS_CARRY_Q 628       /* q of the base joints, body to body */
+#define FS_TGTB 634          /* base DOF targets */
+#define FS_WORDS 640
+#define FS_LDS_BYTES (FS_WORDS * 64 * sizeof(float))
+
+// Live phases of a region: body phases 0-5 of substep_body (0 and 1 share a bit: no barrier separates them, the box wave starts on
+// phase 1 while the other waves run phase 0), the stretch between two bodies (and the prologue before the first), the publication
+// behind the last body, the post block.
+enum : unsigned { LIVE_ACROSS = 1u << 6, LIVE_PUB = 1u << 7, LIVE_POST = 1u << 8 };
+constexpr unsigned lds_live(int first, int last) {   // body phases first .. last
+  unsigned m = 0;
+  for (int p = first; p <= last; p++) m |= 1u << (p == 0 ? 1 : p);
+  return m;
+}
+constexpr unsigned LIVE_CARRY = lds_live(5, 5) | LIVE_ACROSS | lds_live(0, 0);   // phase 5 -> the next body's phase 0
+constexpr unsigned LIVE_LAUNCH = lds_live(0, 5) | LIVE_ACROSS;                   // counted or seq-tagged over the bodies
+struct LdsRegion { int start, words; unsigned live; };
+// Waves by role: f = finger waves, palm = wave 5, box = wave 6, items = the work items of waves 0-5 (general path).
+constexpr LdsRegion LDS_MAP[] = {
+  // start       words                    live              written by (phase) -> read by (phase)
+  {DL_SINV,      36,                      lds_live(2, 3)},  // S^-1: wave 0 (2) -> items (3); S, sum: Schur helpers, wave 0 (2) -> wave 0 (2)
+  {DL_PALM,      16,                      lds_live(1, 2)},  // palm (1) -> palm (1, schur_precompute), wave 0 (2)
+  {DL_NC,        1,                       lds_live(1, 5)},  // box (1), wave 0 (2) -> all (2-5)
+  {FS_UB,        6,                       lds_live(2, 5)},  // wave 0 (2, or 3 without items), palm (4) -> all (5)
+  {FS_BOXV,      6,                       lds_live(1, 5)},  // box (1-3), palm + box (4) -> box (3, 5)
+  {FS_UF,        20,                      lds_live(1, 5)},  // f (1, 4) -> f (3, 5)
+  {FS_LAM,       3 * DEXSIM_KMAX,         lds_live(1, 5)},  // box (1-4), items (3-4) -> box (1-4), items (4), f (5, forces)
+  {FS_HDR,       FS_HDR_HI - FS_HDR,      lds_live(1, 5)},  // entries 0-9: box (1), items (3) -> box (1-4), items (4), f + palm (5)
+  {FS_ROW,       DL_HANDOFF,              lds_live(1, 2)},  // f (1) -> palm (1), Schur phase + narrowphase (2)
+  {FS_HDR_HI,    4 * DEXSIM_KMAX - (FS_HDR_HI - FS_HDR), lds_live(3, 5)},   // entries 10-23: items (3) -> items (4), f + palm (5)
+  {FS_X,         13 * 5 * 4,              lds_live(3, 4)},  // all (3: zeros), items + box (4) -> reducers (4)
+  {FS_FORCE,     5 * 3 * DEXSIM_NFSLOT,   lds_live(5, 5)},  // last sub-step, general path: f (5) -> f (5)
+  {FS_T,         8 * 4,                   lds_live(3, 4)},  // waves 0, 6 and f (3), reducers (4) -> items, box, reducers (4)
+  {FS_SPRE,      27,                      lds_live(1, 2)},  // palm (1) -> Schur phase (2)
+  {FS_BCH,       36,                      lds_live(1, 3)},  // palm (1) -> items (3)
+  {FS_CTAB,      12,                      lds_live(2, 4)},  // wave 0 (2) -> items (3-4)
+  {FS_NITEM,     1,                       lds_live(2, 4)},  // wave 0 (2) -> all (3-4)
+  {FS_CMP,       12,                      lds_live(1, 4)},  // box (1) -> box (1-4)
+  {FS_CARRY_QD,  6,                       LIVE_CARRY},      // palm (5) -> waves 0-5 (0)
+  {FS_CARRY_BP,  3,                       LIVE_CARRY},      // box (5) -> waves 0-5 (0)
+  {FS_COMPCNT,   1,                       LIVE_LAUNCH},     // prologue (zero), f (1) -> palm (1)
+  {FS_GEN,       1,                       lds_live(1, 4)},  // box (1) -> items (3), all (4)
+  {FS_SPLIT,     1,                       lds_live(2, 4)},  // wave 0 (2) -> items, all (3-4)
+  {FS_CPACK,     1,                       lds_live(1, 4)},  // box (1) -> box (3-4)
+  {FS_CMP_INVM,  2,                       lds_live(1, 4)},  // box (1) -> box (1-4), all (4)
+  {FS_FLAG,      6,                       LIVE_LAUNCH},     // prologue (zero), f + palm (0-1), helpers + narrowphase (2) -> box (1), all (2), f (4)
+  {FS_CARRY_Q,   6,                       LIVE_CARRY},      // palm (5) -> waves 0-5 (0)
+  {FS_TGTB,      6,                       lds_live(1, 2)},  // palm (1) -> wave 0 (2)
+};
+// -1 when every region of LDS_MAP and `extra` lies in [0, FS_WORDS) and no two of them live in a common phase share a word, else
+// 1000 x the first word of the region at fault + the first word of the region it overlaps (+ 999: it leaves [0, FS_WORDS)).
+constexpr int lds_map_conflict(LdsRegion extra = {0, 0, 0}) {
+  constexpr int n = sizeof(LDS_MAP) / sizeof(LDS_MAP[0]);
+  for (int i = 0; i <= n; i++) {
+    const LdsRegion a = i < n ? LDS_MAP[i] : extra;
+    if (a.start < 0 || a.words < 0 || a.start + a.words > FS_WORDS) return 1000 * (a.start < 0 ? 0 : a.start) + 999;
+    for (int j = 0; j < i; j++) {
+      const LdsRegion b = LDS_MAP[j];
+      if ((a.live & b.live) && a.start < b.start + b.words && b.start < a.start + a.words) return 1000 * a.start + b.start;
+    }
+  }
+  return -1;
+}
+static_assert(FS_LDS_BYTES == 160 * 1024, "the sub-step kernels own the CU's whole LDS: one workgroup per CU");
+static_assert(lds_map_conflict() < 0, "LDS map: a region leaves the LDS or shares a word with a region live in a common phase "
+                                      "(the note shows 1000 x the first word of one + the first word of the other)");
+static_assert(DL_CAPS(0, 5) == DL_HANDOFF, "the per-finger hand-off is DL_HANDOFF words");
+// the stand-alone kernels: k_dynamics' array, k_solve's dynamic LDS (u_f, impulses, headers, kstage staged contacts; solve_kstage <= 4)
+#define SOLVE_LDS_WORDS(kstage) (60 + DEXSIM_KMAX * 3 + DEXSIM_KMAX * 4 + (kstage) * 3 * CROW_W)
+static_assert((DL_SPLIT + 1) * 64 * sizeof(float) <= FS_LDS_BYTES, "k_dynamics' LDS does not fit into the CU's");
+static_assert(SOLVE_LDS_WORDS(4) * 64 * sizeof(float) <= FS_LDS_BYTES, "k_solve's LDS does not fit into the CU's");
 
 // finger f: everything that depends only on the base chain and the finger's own 4 joints
-// LDS words of the fused sub-step that finger_dynamics writes (layout: see FS_* below)
-#define FS_FLAG 622       /* [622,628), lane 0: (seq << 1) | clear, broadphase verdict of wave w (see substep_body) */
-#define FS_SPRE 513       /* [513,540) = FS_T, unused in phases 1-2: composite part of S (21) + bias of the base joints (6), schur_precompute */
-#define FS_COMPCNT 615    /* lane 0: fingers whose composite + wrench are in LDS, counted over the bodies of the launch */
-
 // state of a finger's 4 joints, loaded at kernel entry (before the base chain) so that the memory round trip
 // overlaps the base-chain arithmetic instead of sitting inside the FK loop behind its jframe stores
 struct FingerIn { float ql[4], qdl[4], tg[4]; };
@@ -453,8 +567,8 @@ DI bool finger_dynamics(const Arena& A, const DevParams* __restrict__ P, const B
     if (l >= 1 && !(tok_seq > 0 && sphere_clear)) {
       const int cap = 3 + 3 * f + (l - 1);
       const V3 c0 = on + mul(R, v3p(M.cap_p0[cap])), c1 = on + mul(R, v3p(M.cap_p1[cap]));
-      sh_put3(sh, lane, DL_CAPS(f) + 6 * (l - 1), c0);
-      sh_put3(sh, lane, DL_CAPS(f) + 6 * (l - 1) + 3, c1);
+      sh_put3(sh, lane, DL_CAPS(dlb, f) + 6 * (l - 1), c0);
+      sh_put3(sh, lane, DL_CAPS(dlb, f) + 6 * (l - 1) + 3, c1);
       if (tok_seq > 0) clr = clr && capsule_clear(c0, c1, M.cap_r[cap], P->cfg, bpos, Rb);
     }
     a[l] = aw; o[l] = on; qf = qn; of = on;
@@ -477,8 +591,8 @@ DI bool finger_dynamics(const Arena& A, const DevParams* __restrict__ P, const B
     bias[l] = dot(a[l], nl[l]);
     if (l > 0) { fl[l - 1] += fl[l]; nl[l - 1] += nl[l] + cross(o[l] - o[l - 1], fl[l]); }
   }
-  sh_put3(sh, lane, DL_WRENCH(f), fl[0]);
-  sh_put3(sh, lane, DL_WRENCH(f) + 3, nl[0] + cross(o[0] - B.o5, fl[0]));
+  sh_put3(sh, lane, DL_WRENCH(dlb, f), fl[0]);
+  sh_put3(sh, lane, DL_WRENCH(dlb, f) + 3, nl[0] + cross(o[0] - B.o5, fl[0]));
   // CRBA blocks from the composite bodies of the finger
   float Fm[16], Cm[24]; // Cm[i*4 + l]
   Comp cc;
@@ -497,7 +611,7 @@ DI bool finger_dynamics(const Arena& A, const DevParams* __restrict__ P, const B
     for (int i = 0; i < 6; i++)
       Cm[i * 4 + l] = i < 3 ? dot(B.ab[i], Pm) : dot(B.ab[i], Lm + cross(cc.c - B.ob[i], Pm));
   }
-  comp_put(sh, lane, DL_COMP(f), cc, B.o5);
+  comp_put(sh, lane, DL_COMP(dlb, f), cc, B.o5);
   if (tok_seq > 0) {   // composite + wrench are in LDS: count this finger in for the palm wave's schur_precompute
     asm volatile("" ::: "memory");
     if (lane == 0) __hip_atomic_fetch_add((int*)(sh + FS_COMPCNT * 64), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -544,8 +658,8 @@ DI bool finger_dynamics(const Arena& A, const DevParams* __restrict__ P, const B
       f2 s2 = {0.f, 0.f};
 #pragma unroll
       for (int l = 0; l < 4; l++) s2 = G2[l * 3 + kp] * Cm[i * 4 + l] + s2;
-      SH(DL_SSUB(f) + i * (i + 1) / 2 + 2 * kp) = s2.x;
-      if (2 * kp + 1 <= i) SH(DL_SSUB(f) + i * (i + 1) / 2 + 2 * kp + 1) = s2.y;
+      SH(DL_SSUB(dlb, f) + i * (i + 1) / 2 + 2 * kp) = s2.x;
+      if (2 * kp + 1 <= i) SH(DL_SSUB(dlb, f) + i * (i + 1) / 2 + 2 * kp + 1) = s2.y;
     }
   if (!fclear) {   // lower triangle, row by row: 10 words in 3 quads
     *FQ(fac_finv, 3 * f) = f4{Fm[0], Fm[4], Fm[5], Fm[8]};
@@ -557,7 +671,7 @@ DI bool finger_dynamics(const Arena& A, const DevParams* __restrict__ P, const B
     f2 s2 = {0.f, 0.f};
 #pragma unroll
     for (int l = 0; l < 4; l++) s2 = G2[l * 3 + ip] * tau[l] + s2;
-    SH(DL_GSUM(f) + 2 * ip) = s2.x; SH(DL_GSUM(f) + 2 * ip + 1) = s2.y;
+    SH(DL_GSUM(dlb, f) + 2 * ip) = s2.x; SH(DL_GSUM(dlb, f) + 2 * ip + 1) = s2.y;
   }
 #pragma unroll
   for (int l = 0; l < 4; l++) {
@@ -606,10 +720,10 @@ DI Comp schur_comp(const float* sh, const int dlb, int lane, V3 o5) {
   S6 J = {SH(DL_PALM + 4), SH(DL_PALM + 5), SH(DL_PALM + 6), SH(DL_PALM + 7), SH(DL_PALM + 8), SH(DL_PALM + 9)};
 #pragma unroll
   for (int f = 0; f < 5; f++) {
-    const float mf = SH(DL_COMP(f));
+    const float mf = SH(DL_COMP(dlb, f));
     M += mf;
-    sd += mf * sh_get3(sh, lane, DL_COMP(f) + 1);
-    J = J + S6{SH(DL_COMP(f) + 4), SH(DL_COMP(f) + 5), SH(DL_COMP(f) + 6), SH(DL_COMP(f) + 7), SH(DL_COMP(f) + 8), SH(DL_COMP(f) + 9)};
+    sd += mf * sh_get3(sh, lane, DL_COMP(dlb, f) + 1);
+    J = J + S6{SH(DL_COMP(dlb, f) + 4), SH(DL_COMP(dlb, f) + 5), SH(DL_COMP(dlb, f) + 6), SH(DL_COMP(dlb, f) + 7), SH(DL_COMP(dlb, f) + 8), SH(DL_COMP(dlb, f) + 9)};
   }
   const float inv = M > 0.f ? 1.f / M : 0.f;
   const V3 d = inv * sd;
@@ -629,11 +743,11 @@ DI void schur_row(float* sh, const int dlb, int lane) {
     const float v = SH(FS_SPRE + i * (i + 1) / 2 + k);
     float ss = 0.f;
 #pragma unroll
-    for (int f = 0; f < 5; f++) ss += SH(DL_SSUB(f) + i * (i + 1) / 2 + k);
+    for (int f = 0; f < 5; f++) ss += SH(DL_SSUB(dlb, f) + i * (i + 1) / 2 + k);
     r[k - k0] = v - ss;
   }
 #pragma unroll
-  for (int k = k0; k <= k1; k++) SH(DL_SINV + i * (i + 1) / 2 + k) = r[k - k0];
+  for (int k = k0; k <= k1; k++) SH(DL_SCHUR_S + i * (i + 1) / 2 + k) = r[k - k0];
 }
 // The composite part of S (the 21 entries before the fingers' C_f G_f are subtracted) and the bias of the six base joints
 // depend on the fingers' composites and wrenches only, which are in LDS half-way through phase 1: the palm wave, idle from
@@ -659,17 +773,17 @@ DI void schur_precompute(float* sh, const int dlb, int lane, const BaseChain& B,
       idx++;
     }
   }
-  V3 ff = sh_get3(sh, lane, DL_PALM + 10), nn = sh_get3(sh, lane, DL_PALM + 13);
+  V3 ff = sh_get3(sh, lane, DL_PALM_WRENCH), nn = sh_get3(sh, lane, DL_PALM_WRENCH + 3);
 #pragma unroll
   for (int f = 0; f < 5; f++) {
-    ff += sh_get3(sh, lane, DL_WRENCH(f));
-    nn += sh_get3(sh, lane, DL_WRENCH(f) + 3);
+    ff += sh_get3(sh, lane, DL_WRENCH(dlb, f));
+    nn += sh_get3(sh, lane, DL_WRENCH(dlb, f) + 3);
   }
-  SH(FS_SPRE + 21 + 5) = dot(B.ab[5], nn);
+  SH(FS_SPRE_BIAS + 5) = dot(B.ab[5], nn);
 #pragma unroll
   for (int j = 4; j >= 0; j--) {
     nn += cross(B.ob[j + 1] - B.ob[j], ff);
-    SH(FS_SPRE + 21 + j) = j < 3 ? dot(B.ab[j], ff) : dot(B.ab[j], nn);
+    SH(FS_SPRE_BIAS + j) = j < 3 ? dot(B.ab[j], ff) : dot(B.ab[j], nn);
   }
 }
 DI void schur_helper(float* sh, const int dlb, int job, int lane) {
@@ -678,9 +792,9 @@ DI void schur_helper(float* sh, const int dlb, int job, int lane) {
 #pragma unroll
     for (int f = 0; f < 5; f++)
 #pragma unroll
-      for (int i = 0; i < 6; i++) gsum[i] += SH(DL_GSUM(f) + i);
+      for (int i = 0; i < 6; i++) gsum[i] += SH(DL_GSUM(dlb, f) + i);
 #pragma unroll
-    for (int i = 0; i < 6; i++) SH(DL_SINV + 27 + i) = gsum[i];
+    for (int i = 0; i < 6; i++) SH(DL_SCHUR_GSUM + i) = gsum[i];
     schur_row<0>(sh, dlb, lane); schur_row<1>(sh, dlb, lane); schur_row<2>(sh, dlb, lane);
   } else if (job == 0) {
     schur_row<3>(sh, dlb, lane); schur_row<5, 4, 5>(sh, dlb, lane);
@@ -700,7 +814,7 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
   const float h = P->h;
   SCHUR_STAMP(0);
   Comp comp5;
-  V3 f5 = sh_get3(sh, lane, DL_PALM + 10), n5 = sh_get3(sh, lane, DL_PALM + 13);
+  V3 f5 = sh_get3(sh, lane, DL_PALM_WRENCH), n5 = sh_get3(sh, lane, DL_PALM_WRENCH + 3);
   float Ssub[21], gsum[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < 21; i++) Ssub[i] = 0.f;
@@ -709,12 +823,12 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
 #pragma unroll
     for (int f = 0; f < 5; f++) {   // (unrolled: the five fingers' LDS reads are in flight together; rolled, every iteration
                                     // waited for its own)
-      f5 += sh_get3(sh, lane, DL_WRENCH(f));
-      n5 += sh_get3(sh, lane, DL_WRENCH(f) + 3);
+      f5 += sh_get3(sh, lane, DL_WRENCH(dlb, f));
+      n5 += sh_get3(sh, lane, DL_WRENCH(dlb, f) + 3);
 #pragma unroll
-      for (int i = 0; i < 21; i++) Ssub[i] += SH(DL_SSUB(f) + i);
+      for (int i = 0; i < 21; i++) Ssub[i] += SH(DL_SSUB(dlb, f) + i);
 #pragma unroll
-      for (int i = 0; i < 6; i++) gsum[i] += SH(DL_GSUM(f) + i);
+      for (int i = 0; i < 6; i++) gsum[i] += SH(DL_GSUM(dlb, f) + i);
     }
   }
   SCHUR_STAMP(1);   // composite sum done
@@ -755,12 +869,12 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
       for (int i = 0; i < 6; i++)
 #pragma unroll
         for (int k = 0; k <= i; k++) {
-          const float v = SH(DL_SINV + idx); idx++;
+          const float v = SH(DL_SCHUR_S + idx); idx++;
           S[i * 6 + k] = v; S[k * 6 + i] = v;
         }
     }
 #pragma unroll
-    for (int i = 0; i < 6; i++) { bias[i] = SH(FS_SPRE + 21 + i); gsum[i] = SH(DL_SINV + 27 + i); }
+    for (int i = 0; i < 6; i++) { bias[i] = SH(FS_SPRE_BIAS + i); gsum[i] = SH(DL_SCHUR_GSUM + i); }
   } else {
     V3 nn = n5, ff = f5;
     bias[5] = dot(B.ab[5], nn);
@@ -1046,7 +1160,7 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
 
 // (cnt, stamp: not read -- the stand-alone kernels never run gated -- but kept, so the kernel-argument layout stays as it was)
 __global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __restrict__ P, const int* __restrict__ cnt, int stamp, int N) {
-  __shared__ __attribute__((aligned(16))) float sh[(DL_WORDS + 1) * 64];   // + 1: the env's split counts (wave 5 -> the row builders); 16-byte aligned: S^-1 is stored as quads
+  __shared__ __attribute__((aligned(16))) float sh[(DL_SPLIT + 1) * 64];   // 16-byte aligned: S^-1 is stored as quads
   constexpr int dlb = DL_PERSIST;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int e = blockIdx.x * 64 + lane;   // N is the padded stride: every lane owns a (possibly dummy) env
@@ -1076,7 +1190,7 @@ __global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __re
     V3 f5 = comp5.m * ac;
     V3 n5 = mul(comp5.I, B.al5) + cross(B.w5, mul(comp5.I, B.w5)) + cross(rc, f5);
     comp_put(sh, lane, DL_PALM, comp5, B.o5);
-    sh_put3(sh, lane, DL_PALM + 10, f5); sh_put3(sh, lane, DL_PALM + 13, n5);
+    sh_put3(sh, lane, DL_PALM_WRENCH, f5); sh_put3(sh, lane, DL_PALM_WRENCH + 3, n5);
     const float h = P->h;
     if (has_box) {
       bpos = {FLD(box_pos, 0), FLD(box_pos, 1), FLD(box_pos, 2)};
@@ -1115,7 +1229,7 @@ __global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __re
 #pragma unroll 1
       for (int l = 3; l >= 1; l--) {   // distal, middle, proximal
         const int cap = 3 + 3 * f + (l - 1);
-        const V3 e0 = sh_get3(sh, lane, DL_CAPS(f) + 6 * (l - 1)), e1 = sh_get3(sh, lane, DL_CAPS(f) + 6 * (l - 1) + 3);
+        const V3 e0 = sh_get3(sh, lane, DL_CAPS(dlb, f) + 6 * (l - 1)), e1 = sh_get3(sh, lane, DL_CAPS(dlb, f) + 6 * (l - 1) + 3);
         collide_capsule(A, N, e, nc, C, cap, e0, e1, M.cap_r[cap], has_box, bpos, Rb, hb, mu_hb, mu_hg, -1, &tmask, code_info(M, cap));
       }
       if (f == 0) cntw[0] = nc - n0; else if (f == 1) cntw[1] = nc - n0; else if (f == 2) cntw[2] = nc - n0; else if (f == 3) cntw[3] = nc - n0; else cntw[4] = nc - n0;
@@ -1131,7 +1245,7 @@ __global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __re
     SH(DL_NC) = __int_as_float(nc);
     const int split = split_pack(nbg, cntw, (int)((unsigned)tmask >> nbg));
     FLD(csplit, 0) = split;
-    SH(DL_WORDS) = __int_as_float(split);
+    SH(DL_SPLIT) = __int_as_float(split);
   }
   __syncthreads();
 
@@ -1140,14 +1254,12 @@ __global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __re
   int kmax = nc;
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) kmax = max(kmax, __shfl_xor(kmax, s));
-  const int split = __float_as_int(SH(DL_WORDS)), gen = FLD(wgen, 0);
+  const int split = __float_as_int(SH(DL_SPLIT)), gen = FLD(wgen, 0);
 #pragma unroll 1
   for (int k = wv; k < kmax; k += 6) {
     if (k < nc) build_contact_rows(A, P, B, sh, nullptr, nullptr, 0, lane, k, N, e, -2, split, gen);
   }
 }
-
-#define SOLVE_LDS_WORDS(kstage) (60 + DEXSIM_KMAX * 3 + DEXSIM_KMAX * 4 + (kstage) * 3 * CROW_W)
 
 // wave-uniform per-contact masks: does ANY lane couple contact k to the hand / a finger / the box
 DI void solve_masks(const float* s_hdr, int nc, int kmax, int lane, unsigned& hand_mask, unsigned& fing_mask, unsigned& box_mask) {
@@ -1809,40 +1921,10 @@ __global__ __launch_bounds__(384) void k_publish(Arena A, ApiPtrs T, const DevPa
 //   phase 5  finger waves: back-substitute + integrate finger f | palm wave: base DOFs | box wave: box | (last sub-step) contact forces
 // Compared with k_dynamics + k_solve this removes one launch per sub-step and the HBM/L2 round trip of the free velocity and the
 // factors between the two kernels.
-// LDS words (x64 lanes x4 B): [0,53) persistent hand-off (S^-1, palm, contact counts) | [53,85) u_B, box twist, u_f (free velocities,
-// then the solved ones) | [85,157) impulses | [157,253) contact headers | [197,502) per-finger hand-off of phases 1-2 (dead after
-// phase 2; the header tail, the exchange words FS_X [253,513) and the force scratch reuse it) | [513,545) common velocities FS_T |
-// [545,581) base joint frames | [581,606) work-item table, count, box/ground lever arms | [617,640) generation, split counts, box
-// 1/m 1/I, broadphase tokens, base targets.
-#define FS_UB 53
-#define FS_BOXV 59
-#define FS_UF 65
-#define FS_LAM 85        /* [85,157): impulses of all KMAX list entries, 3 words each */
-#define FS_HDR 157       /* [157,253): headers of all KMAX list entries: code, finger offset, mu, bias (entries >= 10 overlap the
-                            per-finger hand-off block, which is dead when the hand contacts' headers are written in phase 3) */
-#define FS_ROW 197       /* base of the per-finger hand-off block of phases 1-2 (dlb), [197,502) */
-#define FS_X 253         /* [253,513): block exchange of the contact solver, 13 blocks (12 hand blocks + the box/ground block 12) x 5
-                            quads [block][quad][lane][4]: the velocity change a block made in one pass -- quad 0 = d u_B[0..3], 1 =
-                            (d u_B[4], d u_B[5], d v_box[0], d v_box[1]), 2 = d v_box[2..5], 3 = d u_f of the finger of the block's first
-                            contact, 4 = d u_f of the finger of its second contact when that is another one (pairs only).  First
-                            written in phase 4: overlaps the (then dead) hand-off block */
-#define FS_T 513         /* [513,545): the common velocities, 8 quads (absolute values): u_B, box twist as in FS_X, 3 + f = u_f of finger f */
-#define FS_WORDS 640
-#define FS_BCH 545       /* [545,581): axes and origins of the six base joints (palm wave, phase 1 -> build_contact_rows) */
-#define FS_CTAB 581      /* [581,593): work-item table, 768 entries indexed linearly: entry i = owner lane | block << 8 of the i-th hand
-                            block of the workgroup (block-major: all envs' block 0, then all envs' block 1, ...) */
-#define FS_NITEM 593     /* lane 0: number of items */
-#define FS_CARRY_QD 606   /* [606,612): qd of the base joints, [612,615): box position, [628,634): q of the base joints -- body to body (SubstepCarry) */
-#define FS_CARRY_BP 612
-#define FS_CARRY_Q 628
-#define FS_GEN 617       /* the env's warm-start generation of this sub-step (box wave, phase 1); + 2: corner indices of its slots */
-#define FS_SPLIT 618     /* split counts of this sub-step, packed (wave 5, phase 2): see split_pack */
+// LDS words: the LDS map (above finger_dynamics).  XQ(b, q): quad q of block b of the exchange; TQ(q): quad q of the common
+// velocities.
 #define XQ(b, q) ((f4*)(sh + FS_X * 64 + (((b) * 5 + (q)) * 64 + lane) * 4))
 #define TQ(q) ((f4*)(sh + FS_T * 64 + ((q) * 64 + lane) * 4))
-#define FS_CMP 594       /* [594,606): lever arms r = contact point - box centre of the (at most 4) box/ground contacts (box wave, phase 1);
-                            [620,622): 1/m, 1/I of the box */
-#define FS_TGTB 634       /* [634,640): base DOF targets, staged by wave 5 for wave 0's Schur phase */
-#define FS_CMP_INVM 620   /* [617,640) is never part of the row store */
 
 // LAST = the final sub-step of a sim.dt: it also accumulates the net contact forces (CC_LAST_SUBSTEP) and ends with
 // the site / dof_state / root publication (k_publish's body), so a physics step is `substeps` launches and nothing
@@ -2035,7 +2117,7 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
     const float nXf = (float)SPLIT_NX(split), rX = 1.f / nXf;
     if (wv == 6) {
       // the box wave: block 12 (box/ground contacts, all in VGPRs) + reducer of box twist words 2-5
-      const int cpack = __float_as_int(SH(FS_GEN + 2));
+      const int cpack = __float_as_int(SH(FS_CPACK));
       BoxBlock bb;
       bb.load<false>(kbg, inv_m, inv_I, s_lam, s_hdr, sh + FS_CMP * 64, 0, 0, lane, nbg, true, nXf);
       f4 Tm0 = *TQ(2);
@@ -2429,11 +2511,11 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     V3 f5 = comp5.m * ac;
     V3 n5 = mul(comp5.I, B.al5) + cross(B.w5, mul(comp5.I, B.w5)) + cross(rc, f5);
     comp_put(sh, lane, DL_PALM, comp5, B.o5);
-    sh_put3(sh, lane, DL_PALM + 10, f5); sh_put3(sh, lane, DL_PALM + 13, n5);
+    sh_put3(sh, lane, DL_PALM_WRENCH, f5); sh_put3(sh, lane, DL_PALM_WRENCH + 3, n5);
 #pragma unroll
     for (int i = 0; i < 6; i++) SH(FS_TGTB + i) = FLD(targets, i);
 #pragma unroll
-    for (int i2 = 0; i2 < 3; i2++) {   // axes + origins of the base joints, two joints = 12 words = 3 quads (ROWADDR layout): row build (phase 3), Schur helpers
+    for (int i2 = 0; i2 < 3; i2++) {   // axes + origins of the base joints, two joints = 12 words = 3 quads (ROWADDR layout): row build (phase 3)
       const V3 a0 = B.ab[2 * i2], o0 = B.ob[2 * i2], a1 = B.ab[2 * i2 + 1], o1 = B.ob[2 * i2 + 1];
       *(f4*)(sh + FS_BCH * 64 + ROWADDR(12 * i2, lane)) = f4{a0.x, a0.y, a0.z, o0.x};
       *(f4*)(sh + FS_BCH * 64 + ROWADDR(12 * i2 + 4, lane)) = f4{o0.y, o0.z, a1.x, a1.y};
@@ -2502,7 +2584,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
       s_lam[(3 * k) * 64 + lane] = warm ? wq[k].x : 0.f; s_lam[(3 * k + 1) * 64 + lane] = warm ? wq[k].y : 0.f;
       s_lam[(3 * k + 2) * 64 + lane] = warm ? wq[k].z : 0.f;
     }
-    SH(FS_GEN + 2) = __int_as_float(cpack);   // for the box wave's general-path branch (phase 4)
+    SH(FS_CPACK) = __int_as_float(cpack);   // for the box wave's general-path branch (phase 4)
     // SPECULATIVE box solve: the broadphase verdicts of the finger waves arrive only after their FK (~half of phase 1), and
     // in the regime that matters for throughput they say "hand clear".  So the box wave does not wait: it starts the sweeps
     // of the box/ground contacts right away, on a private copy of the twist in VGPRs, concurrently with the finger
@@ -2532,9 +2614,8 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     }
     {   // broadphase verdicts of this sub-step: the six tokens (fingers after their FK, palm after the base chain).
         // The spin is safe because the seven waves of a workgroup are always co-resident: a workgroup is placed on a CU as
-        // a whole (448 threads = 7 waves, __launch_bounds__(448); FS_WORDS = 160 KiB of LDS => one workgroup per CU), and the
-        // waves being waited for never wait for this one before they post their token.
-      static_assert(FS_WORDS * 64 * sizeof(float) == 160 * 1024, "the sub-step kernels own the CU's whole LDS: one workgroup per CU");
+        // a whole (448 threads = 7 waves, __launch_bounds__(448); FS_LDS_BYTES = 160 KiB of LDS => one workgroup per CU), and
+        // the waves being waited for never wait for this one before they post their token.
       hand_free = true;
 #pragma unroll 1
       for (int w = 0; w < 6; w++) {
@@ -2626,7 +2707,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
         for (int c = 0; c < 3; c++) {
           const int l = 3 - c;
           caps[c] = 3 + 3 * cw + (l - 1);
-          E0[c] = sh_get3(sh, lane, DL_CAPS(cw) + 6 * (l - 1)); E1[c] = sh_get3(sh, lane, DL_CAPS(cw) + 6 * (l - 1) + 3);
+          E0[c] = sh_get3(sh, lane, DL_CAPS(dlb, cw) + 6 * (l - 1)); E1[c] = sh_get3(sh, lane, DL_CAPS(dlb, cw) + 6 * (l - 1) + 3);
         }
       } else {
         const M3 R5 = q2mat(B.q5);
@@ -2657,7 +2738,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     }
     // counts (+ which contacts touch the box) go into the (now dead) token words, tagged so that they can never look like a
     // token of a later sub-step
-    const int nbg0 = __float_as_int(SH(DL_NC)) & 0xff;   // box/ground contacts found by wave 6 (read before wave 5 rewrites the word)
+    const int nbg0 = __float_as_int(SH(DL_NC)) & 0xff;   // box/ground contacts found by wave 6 (read before wave 0 rewrites the word)
     PH2_STAMP(0);
     if (cw >= 0) SH(FS_FLAG + cw) = __int_as_float(NP_TAG | ((clear_mask >> cw) & 1) | (nloc << 1) | (tmask << 8));
     __syncthreads();
@@ -2754,7 +2835,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
 #pragma unroll
       for (int i = 0; i < 6; i++) SH(FS_UB + i) = uB[i];
     } else if (wv == 6) {
-      const int gen = __float_as_int(SH(FS_GEN)), cpack = __float_as_int(SH(FS_GEN + 2));
+      const int gen = __float_as_int(SH(FS_GEN)), cpack = __float_as_int(SH(FS_CPACK));
       if (has_box) {
         int km = nbg;
 #pragma unroll
@@ -2814,7 +2895,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
 
   // ---- phase 5: back-substitution qd = L^-1 u, semi-implicit Euler, joint-limit clamp; forces
   if (last && gp) {   // net contact forces of the general path: partial sums on waves 0-4 (the exchange words are dead: 5 x 51 rows)
-    if (wv < 5) forces_partial(A, P, s_hdr, s_lam, sh + (FS_X + wv * DEXSIM_NFSLOT * 3) * 64, nc, wv, lane, N, e);
+    if (wv < 5) forces_partial(A, P, s_hdr, s_lam, sh + (FS_FORCE + wv * DEXSIM_NFSLOT * 3) * 64, nc, wv, lane, N, e);
     __syncthreads();
   }
 #pragma unroll
@@ -2856,7 +2937,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
       if (!C.box_fixed) integrate_box(A, h, vb, wb, N, e);   // (static box: its twist is exactly zero -- 1/m = 1/I = 0 in every row)
     }
   }
-  if (last && wv < 5 && gp) forces_reduce(A, ccnt, s_hdr, sh + FS_X * 64, nc, lane, N, e, NR, wv, 5);
+  if (last && wv < 5 && gp) forces_reduce(A, ccnt, s_hdr, sh + FS_FORCE * 64, nc, lane, N, e, NR, wv, 5);
   if (last && wv == 5 && gp) contact_stats(ccnt, s_hdr, nc, lane, e, NR);
   PHASE_STAMP();   // 5: phase 5 done
   }
