@@ -371,7 +371,7 @@ int dexsim_process_actions(dexsim_t h, const float* actions, int zero_targets, v
   next_stamp(h);   // the action stage opens a control step
   ApiPtrs api = h->api;
   if (api.actions_copy == actions) api.actions_copy = nullptr;   // the caller passed the bound copy itself: nothing to copy
-  k_actions<<<GRID(h)>>>(h->arena, api, h->d_params, actions, zero_targets, h->NS, h->N);
+  k_actions<<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, api, h->d_params, actions, zero_targets, h->NS, h->N);
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }

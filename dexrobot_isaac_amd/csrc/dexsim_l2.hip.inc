@@ -2,7 +2,8 @@
 //
 //   k_actions : ActionProcessor.process_actions (action_processor.py:284-352) with the default rules
 //               (default_rules.py:33-112), filters (rules.py:141-190) and coupling (:571-614);
-//               ObservationEncoder.update_prev_actions (:287-296).  ~25 torch kernels -> 1.
+//               ObservationEncoder.update_prev_actions (:287-296).  ~25 torch kernels -> 1.  Its body is actions_block,
+//               the block that also opens the first physics launch of dexsim_step.
 //   k_post    : StepProcessor.process_physics_step (step_processor.py:37-131) = ObservationEncoder
 //               (observation_encoder.py:576-758) + BlindGraspingTask.get_task_observations / FSM
 //               (blind_grasping_task.py:549-978) + termination (step_processor.py:133-181,
@@ -13,26 +14,33 @@
 //               stream instead of torch.rand (blind_grasping_task.py:449-547).
 //   k_finalize: the cross-env means / rates of TerminationManager.evaluate and consecutive successes.
 
-// coupling table (constants.py:71-88): (finger control, dof); dof 22 (r_f_joint5_1) has scale 2
-__constant__ int c_coupling[19][2] = {{0, 6}, {1, 7}, {2, 8}, {2, 9}, {3, 10}, {3, 18}, {3, 22}, {4, 11}, {5, 12}, {5, 13},
-                                      {6, 15}, {7, 16}, {7, 17}, {8, 19}, {9, 20}, {9, 21}, {10, 23}, {11, 24}, {11, 25}};
+// Coupling (constants.py:71-88): the DOFs that each of the 18 controls drives, in the reference's order, with their scales.
+// Controls 0-5 drive the base DOFs 0-5.  Every index is a compile-time constant in the unrolled loops that read the table.
+struct CouplingGroup { int n, dof[3]; float scale[3]; };
+constexpr CouplingGroup kCoupling[18] = {
+    {1, {0}, {1}}, {1, {1}, {1}}, {1, {2}, {1}}, {1, {3}, {1}}, {1, {4}, {1}}, {1, {5}, {1}},
+    {1, {6}, {1}},                          // thumb spread
+    {1, {7}, {1}},                          // thumb MCP
+    {2, {8, 9}, {1, 1}},                    // thumb DIP
+    {3, {10, 18, 22}, {1, 1, 2}},           // finger spread: r_f_joint5_1 (DOF 22) turns twice as far
+    {1, {11}, {1}}, {2, {12, 13}, {1, 1}},  // index MCP, DIP
+    {1, {15}, {1}}, {2, {16, 17}, {1, 1}},  // middle MCP, DIP
+    {1, {19}, {1}}, {2, {20, 21}, {1, 1}},  // ring MCP, DIP
+    {1, {23}, {1}}, {2, {24, 25}, {1, 1}},  // pinky MCP, DIP
+};
+constexpr int kHeldDof = 14;   // r_f_joint3_1 (middle spread): driven by no control, its target is held at 0
 // HardwareMapping enum order -> primary DOF (hand_initializer.py:20-38, observation_encoder.py:496-574)
-__constant__ int c_active_finger_dof[12] = {8, 7, 6, 10, 12, 11, 16, 15, 20, 19, 24, 23};
-// inverse coupling, CPU last-writer-wins order (action_processor.py:616-666): control -> (dof, 1/scale)
-__constant__ int c_inv_dof[12] = {6, 7, 9, 22, 11, 13, 15, 17, 19, 21, 23, 25};
+constexpr int kActiveFingerDof[12] = {8, 7, 6, 10, 12, 11, 16, 15, 20, 19, 24, 23};
 
-enum { O_base_dof_pos = 0, O_base_dof_vel = 6, O_active_finger_dof_pos = 12, O_active_finger_dof_vel = 24,
-       O_all_finger_dof_pos = 36, O_all_finger_dof_vel = 56, O_hand_pose = 76, O_hand_pose_arr_aligned = 83,
-       O_contact_forces = 90, O_prev_actions = 105, O_active_prev_targets = 123, O_base_dof_target = 141,
-       O_active_finger_dof_target = 147, O_all_finger_dof_target = 159, O_contact_force_magnitude = 179,
-       O_contact_binary = 184, O_contact_duration = 189, O_fingertip_poses_world = 194,
-       O_fingertip_poses_hand = 229, O_fingerpad_poses_world = 264, O_fingerpad_poses_hand = 299,
-       O_episode_time = 334, O_active_rule_targets = 335, O_object_pos = 353, O_object_vel = 356,
-       O_finger_to_object_distances = 359, O_avg_finger_to_object_distance = 364,
-       O_finger_to_object_height_diff = 365, O_avg_finger_to_object_height_diff = 370,
-       O_hand_to_object_distance = 371, O_fingerpad_distances = 372, O_first_three_fingerpad_centroid = 382,
-       O_thumb_contact = 385, O_other_fingers_contact = 386, O_grasp_state = 387, O_grasp_duration = 388,
-       O_current_stage = 389, O_time_in_stage = 390, O_stage_progress = 391 };
+// obs_all row of each obs_dict key (include/dexsim.h); O_<key>_last is the key's last row
+enum {
+#define X(name, dim) O_##name, O_##name##_last = O_##name + (dim) - 1,
+  DEXSIM_OBS_KEYS(X)
+#undef X
+  O_end
+};
+static_assert(O_end == DEXSIM_OBS_ALL_DIM, "DEXSIM_OBS_ALL_DIM is not the sum of the DEXSIM_OBS_KEYS dims");
+static_assert(O_object_pos == DEXSIM_OBS_BASE_TASK_DIM, "DEXSIM_OBS_BASE_TASK_DIM is not the row of object_pos");
 
 // The words the current step accumulates into (parity of its stamp) were cleared during the previous step; this clears the
 // other pair for the next one.  No launch clears a word that the same launch, or a concurrently running one, adds to.
@@ -41,94 +49,23 @@ DI void begin_step_counters(int* cnt, int stamp) {
   cnt[CNT_CONTACTS + o] = 0; cnt[CNT_HAND_CONTACTS + o] = 0;
 }
 
-__global__ __launch_bounds__(64) void k_actions(Arena A, ApiPtrs T, const DevParams* __restrict__ P, const float* __restrict__ act,
-                                                int zero_targets, int N, int NR) {
-  const int e = blockIdx.x * 64 + threadIdx.x;
-  const DexSimConfig& C = P->cfg;
-  const int na = C.num_actions;
-  const bool real = e < NR;
-  // start of a control step: clear the NEXT step's contact statistics words (see CNT_CONTACTS; the reset gate is a stamp)
-  if (blockIdx.x == 0 && threadIdx.x == 0) begin_step_counters(T.counters, T.stamp);
-  float a[18];
-#pragma unroll
-  for (int i = 0; i < 18; i++) {
-    a[i] = (real && i < na) ? act[(size_t)e * na + i] : 0.f;
-    FLD(actions, i) = a[i];
-    if (T.actions_copy && real && i < na) T.actions_copy[(size_t)e * na + i] = a[i];   // DexHandBase.actions = actions.clone()
-  }
-  float tgt[26];
-#pragma unroll
-  for (int i = 0; i < 26; i++) tgt[i] = 0.f;
-  if (!zero_targets) {
-    float raw[18], prev[18], nxt[18];
-#pragma unroll
-    for (int i = 0; i < 18; i++) { raw[i] = FLD(active_rule_targets, i); prev[i] = FLD(active_prev_targets, i); }
-    const int fs = C.policy_controls_base ? 6 : 0;
-    if (T.raw_targets) {   // host-side custom action rule already produced active_raw_targets
-#pragma unroll
-      for (int i = 0; i < 18; i++) raw[i] = real ? T.raw_targets[(size_t)e * 18 + i] : raw[i];
-    } else if (C.control_mode == DEXSIM_MODE_POSITION_DELTA) {
-      if (C.policy_controls_base) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) raw[i] = prev[i] + a[i] * C.max_deltas[i];
-      }
-      if (C.policy_controls_fingers) {
-#pragma unroll
-        for (int i = 0; i < 12; i++) raw[6 + i] = prev[6 + i] + (fs ? a[6 + i] : a[i]) * C.max_deltas[6 + i];
-      }
-#pragma unroll
-      for (int i = 0; i < 18; i++) raw[i] = clampf(raw[i], C.active_lower[i], C.active_upper[i]);
-    } else {
-      if (C.policy_controls_base) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) raw[i] = (a[i] + 1.0f) * 0.5f * (C.active_upper[i] - C.active_lower[i]) + C.active_lower[i];
-      }
-      if (C.policy_controls_fingers) {
-#pragma unroll
-        for (int i = 0; i < 12; i++)
-          raw[6 + i] = ((fs ? a[6 + i] : a[i]) + 1.0f) * 0.5f * (C.active_upper[6 + i] - C.active_lower[6 + i]) + C.active_lower[6 + i];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 18; i++) {
-      const float d = clampf(raw[i] - prev[i], -C.max_deltas[i], C.max_deltas[i]);
-      nxt[i] = clampf(prev[i] + d, C.active_lower[i], C.active_upper[i]);
-      FLD(active_prev_targets, i) = nxt[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) tgt[i] = nxt[i];
-    // coupling (static table, unrolled): dof <- control * scale ; r_f_joint3_1 (dof 14) stays 0
-    tgt[6] = nxt[6]; tgt[7] = nxt[7]; tgt[8] = nxt[8]; tgt[9] = nxt[8];
-    tgt[10] = nxt[9]; tgt[18] = nxt[9]; tgt[22] = nxt[9] * 2.0f;
-    tgt[11] = nxt[10]; tgt[12] = nxt[11]; tgt[13] = nxt[11];
-    tgt[15] = nxt[12]; tgt[16] = nxt[13]; tgt[17] = nxt[13];
-    tgt[19] = nxt[14]; tgt[20] = nxt[15]; tgt[21] = nxt[15];
-    tgt[23] = nxt[16]; tgt[24] = nxt[17]; tgt[25] = nxt[17];
-    tgt[14] = 0.f;
-  }
-#pragma unroll
-  for (int i = 0; i < 26; i++) {
-    FLD(targets, i) = tgt[i];
-    if (real && T.full_dof_targets) T.full_dof_targets[(size_t)e * 26 + i] = tgt[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 18; i++) FLD(prev_actions, i) = a[i];
-}
-
-// k_actions' arithmetic with the 18 action channels spread over the 6 wavefronts of a k_physics4 workgroup (channel i
-// on wave i / 3): per channel 3 loads, a dozen ALU ops and ~8 stores instead of ~60 loads and ~110 stores on one wave.
-// (zero_targets, the pre-finalize_setup mode, stays on the stand-alone kernel.)
-DI void actions_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, const float* __restrict__ act, int N, int NR) {
+// ActionProcessor.process_actions with the 18 action channels spread over 6 wavefronts (channel i on wave i / 3): per
+// channel 3 loads, a dozen ALU ops and ~8 stores instead of ~60 loads and ~110 stores on one wave.  zero_targets (the
+// pre-finalize_setup branch, action_processor.py:305-318): every target is 0, active_prev_targets keeps its value and no
+// raw target is read; the actions rows, the action copy and the step counters as in the other mode.
+DI void actions_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, const float* __restrict__ act,
+                      int zero_targets, int N, int NR) {
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int e = blockIdx.x * 64 + lane;
   const DexSimConfig& C = P->cfg;
   const int na = C.num_actions;
   const bool real = e < NR;
+  // start of a control step: clear the NEXT step's contact statistics words (see CNT_CONTACTS; the reset gate is a stamp)
   if (blockIdx.x == 0 && threadIdx.x == 0) begin_step_counters(T.counters, T.stamp);
   const int fs = C.policy_controls_base ? 6 : 0;
-  if (wv == 0) {   // r_f_joint3_1 (dof 14) is not driven by any control
-    FLD(targets, 14) = 0.f;
-    if (real && T.full_dof_targets) T.full_dof_targets[(size_t)e * 26 + 14] = 0.f;
+  if (wv == 0) {
+    FLD(targets, kHeldDof) = 0.f;
+    if (real && T.full_dof_targets) T.full_dof_targets[(size_t)e * 26 + kHeldDof] = 0.f;
   }
 #pragma unroll
   for (int i = 0; i < 18; i++) {
@@ -142,7 +79,7 @@ DI void actions_block(const Arena& A, const ApiPtrs& T, const DevParams* __restr
     const float prev = FLD(active_prev_targets, i);
     FLD(actions, i) = ai;
     if (T.actions_copy && real && i < na) T.actions_copy[(size_t)e * na + i] = ai;   // DexHandBase.actions = actions.clone()
-    if (T.raw_targets) {   // host-side custom action rule already produced active_raw_targets
+    if (T.raw_targets && !zero_targets) {   // host-side custom action rule already produced active_raw_targets
       raw = real ? T.raw_targets[(size_t)e * 18 + i] : raw;
     } else if (C.control_mode == DEXSIM_MODE_POSITION_DELTA) {
       if (driven) raw = prev + ac * C.max_deltas[i];
@@ -152,31 +89,24 @@ DI void actions_block(const Arena& A, const ApiPtrs& T, const DevParams* __restr
     }
     const float d = clampf(raw - prev, -C.max_deltas[i], C.max_deltas[i]);
     const float nxt = clampf(prev + d, C.active_lower[i], C.active_upper[i]);
-    FLD(active_prev_targets, i) = nxt;
-    // coupling (static table, constants.py:71-88): dof <- control * scale
-    int d0 = -1, d1 = -1, d2 = -1;
-    switch (i) {
-      case 0: case 1: case 2: case 3: case 4: case 5: d0 = i; break;
-      case 6: d0 = 6; break;   case 7: d0 = 7; break;   case 8: d0 = 8; d1 = 9; break;
-      case 9: d0 = 10; d1 = 18; d2 = 22; break;
-      case 10: d0 = 11; break; case 11: d0 = 12; d1 = 13; break;
-      case 12: d0 = 15; break; case 13: d0 = 16; d1 = 17; break;
-      case 14: d0 = 19; break; case 15: d0 = 20; d1 = 21; break;
-      case 16: d0 = 23; break; case 17: d0 = 24; d1 = 25; break;
-    }
-    FLD(targets, d0) = nxt;
-    if (real && T.full_dof_targets) T.full_dof_targets[(size_t)e * 26 + d0] = nxt;
-    if (d1 >= 0) {
-      FLD(targets, d1) = nxt;
-      if (real && T.full_dof_targets) T.full_dof_targets[(size_t)e * 26 + d1] = nxt;
-    }
-    if (d2 >= 0) {
-      const float t2 = nxt * 2.0f;
-      FLD(targets, d2) = t2;
-      if (real && T.full_dof_targets) T.full_dof_targets[(size_t)e * 26 + d2] = t2;
-    }
+    if (!zero_targets) FLD(active_prev_targets, i) = nxt;
+    const float tgt = zero_targets ? 0.f : nxt;
+    // coupling: the DOFs of control i's group, written out per slot (as a loop over the group, the scatter makes the physics
+    // kernels load the field pointers again on every wave)
+    const CouplingGroup& g = kCoupling[i];
+#define PUT(k) do { const float t = tgt * g.scale[k]; FLD(targets, g.dof[k]) = t; \
+                    if (real && T.full_dof_targets) T.full_dof_targets[(size_t)e * 26 + g.dof[k]] = t; } while (0)
+    PUT(0);
+    if (g.n > 1) PUT(1);
+    if (g.n > 2) PUT(2);
+#undef PUT
     FLD(prev_actions, i) = ai;
   }
+}
+
+__global__ __launch_bounds__(384) void k_actions(Arena A, ApiPtrs T, const DevParams* __restrict__ P, const float* __restrict__ act,
+                                                 int zero_targets, int N, int NR) {
+  actions_block(P->arena, T, P, act, zero_targets, N, NR);
 }
 
 // ------------------------------------------------------------------------------------------------- post
@@ -184,12 +114,12 @@ DI V3 site_pos(const Arena& A, int N, int e, int s) { return {FLD(site_pose, 7 *
 DI Q4 site_quat(const Arena& A, int N, int e, int s) {
   return {FLD(site_pose, 7 * s + 3), FLD(site_pose, 7 * s + 4), FLD(site_pose, 7 * s + 5), FLD(site_pose, 7 * s + 6)};
 }
-// Every obs_dict value of the wavefront's 64 envs is assembled in LDS as s_ob[env][row] (row stride 393, odd:
-// conflict-free both for the per-env writes and for the transposed reads), then flushed twice, both fully
+// Every obs_dict value of the wavefront's 64 envs is assembled in LDS as s_ob[env][row] (row stride DEXSIM_OBS_ALL_DIM + 1 =
+// 393, odd: conflict-free both for the per-env writes and for the transposed reads), then flushed twice, both fully
 // coalesced: SoA into obs_all (the obs_dict views) and row-major into obs_buf (N, O), whose 64 consecutive rows are
 // one contiguous block in HBM.  (v1 wrote obs_buf with 158 stride-632-B stores per lane and read obs_all back from
 // memory in a dependent loop: 57 us.)
-#define OB_STRIDE 393
+#define OB_STRIDE (DEXSIM_OBS_ALL_DIM + 1)
 #define OB(i) s_ob[lane * OB_STRIDE + (i)]
 
 // ---- k_post, v3.  A single wavefront can keep at most 64 memory instructions in flight and a burst of row accesses
@@ -233,9 +163,10 @@ DI void post_task(int t, const Arena& A, const DevParams* __restrict__ P, const 
     for (int i = 0; i < 26; i++) vel[i] = (q[i] - pq[i]) / cdt;   // prev_dof_pos := q is stored by the flush (phase C)
 #pragma unroll
     for (int i = 0; i < 6; i++) { OB(O_base_dof_pos + i) = q[i]; OB(O_base_dof_vel + i) = vel[i]; }
-    const int d[12] = {8, 7, 6, 10, 12, 11, 16, 15, 20, 19, 24, 23};   // active finger DOFs, static gather
 #pragma unroll
-    for (int i = 0; i < 12; i++) { OB(O_active_finger_dof_pos + i) = q[d[i]]; OB(O_active_finger_dof_vel + i) = vel[d[i]]; }
+    for (int i = 0; i < 12; i++) {
+      OB(O_active_finger_dof_pos + i) = q[kActiveFingerDof[i]]; OB(O_active_finger_dof_vel + i) = vel[kActiveFingerDof[i]];
+    }
     float pen = 0.f;
 #pragma unroll
     for (int i = 0; i < 20; i++) {
@@ -294,9 +225,8 @@ DI void post_task(int t, const Arena& A, const DevParams* __restrict__ P, const 
     for (int i = 0; i < 26; i++) tg[i] = FLD(targets, i);
 #pragma unroll
     for (int i = 0; i < 6; i++) OB(O_base_dof_target + i) = tg[i];
-    const int d[12] = {8, 7, 6, 10, 12, 11, 16, 15, 20, 19, 24, 23};
 #pragma unroll
-    for (int i = 0; i < 12; i++) OB(O_active_finger_dof_target + i) = tg[d[i]];
+    for (int i = 0; i < 12; i++) OB(O_active_finger_dof_target + i) = tg[kActiveFingerDof[i]];
 #pragma unroll
     for (int i = 0; i < 20; i++) OB(O_all_finger_dof_target + i) = tg[6 + i];
   } else if (t == 4) {     // previous actions
@@ -313,7 +243,7 @@ DI void post_task(int t, const Arena& A, const DevParams* __restrict__ P, const 
     for (int i = 0; i < 18; i++) {
       OB(O_active_prev_targets + i) = v[i];
       // default pre-action rule = identity clone (rules.py:78-95); a host-side custom rule overwrites the
-      // field before the next k_actions
+      // field before the next action stage
       FLD(active_rule_targets, i) = v[i];
       OB(O_active_rule_targets + i) = v[i];
     }
@@ -917,13 +847,12 @@ DI void reset_phase0(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     FLD(q, i) = q[i]; FLD(qd, i) = 0.f; FLD(targets, i) = q[i];
     if (T.full_dof_targets) T.full_dof_targets[(size_t)e * 26 + i] = q[i];
   }
-  // inverse coupling with the CPU last-writer-wins scatter (action_processor.py:616-666)
+  // inverse coupling with the CPU last-writer-wins scatter (action_processor.py:616-666): a control takes the last DOF of
+  // its group, divided by that DOF's scale
 #pragma unroll
-  for (int i = 0; i < 6; i++) FLD(active_prev_targets, i) = q[i];
-  {
-    const int d[12] = {6, 7, 9, 22, 11, 13, 15, 17, 19, 21, 23, 25};
-#pragma unroll
-    for (int c = 0; c < 12; c++) FLD(active_prev_targets, 6 + c) = d[c] == 22 ? q[22] / 2.0f : q[d[c]];
+  for (int c = 0; c < 18; c++) {
+    const CouplingGroup& g = kCoupling[c];
+    FLD(active_prev_targets, c) = q[g.dof[g.n - 1]] / g.scale[g.n - 1];
   }
 }
 

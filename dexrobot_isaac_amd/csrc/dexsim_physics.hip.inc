@@ -2955,7 +2955,8 @@ DI void reset_phase1(const Arena& A, int N, int e);                             
 DI void finalize_stats(const ApiPtrs& T, const DevParams* __restrict__ P, int NR);
 DI void post_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, int* __restrict__ cnt, float* s_ob,
                    int obs_only, int fold_reset, int N, int NR, int done_mask);
-DI void actions_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, const float* __restrict__ act, int N, int NR);
+DI void actions_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, const float* __restrict__ act,
+                      int zero_targets, int N, int NR);
 
 // `tail` of a physics launch (host and kernels): what runs behind its last sub-step body
 enum {
@@ -2991,13 +2992,13 @@ DI void physics_epilogue(const ApiPtrs& T, const DevParams* __restrict__ P, int 
 // removes three kernel boundaries (~2.7 us each on this part: dispatch + the L2 writeback / invalidate that makes
 // every first touch of the next kernel an Infinity-Cache / HBM miss, ~4k cycles).
 // act != nullptr (ungated first launch of dexsim_step): ActionProcessor.process_actions runs first, three action channels per
-// wavefront (k_actions' arithmetic, channel by channel), so that the whole control step up to the reset gate is ONE launch.
+// wavefront (actions_block, the body of k_actions too), so that the whole control step up to the reset gate is ONE launch.
 template <bool GATED>
 __global__ __launch_bounds__(448) void k_physics4(Arena A, ApiPtrs T, const DevParams* __restrict__ P, int* __restrict__ cnt,
                                                   const float* __restrict__ act, int tail, int N, int NR) {
   extern __shared__ float sh[];
   const unsigned long long pr_k0 = physics_prologue<GATED>(T, sh);
-  if (!GATED && act) actions_block(P->arena, T, P, act, N, NR);
+  if (!GATED && act) actions_block(P->arena, T, P, act, 0, N, NR);
   __syncthreads();   // targets are read by every wave of the first sub-step
   if (!GATED || cnt[CNT_ANY_RESET] == T.stamp) {
     SubstepCarry K;
@@ -3027,7 +3028,7 @@ __global__ __launch_bounds__(448) void k_physics1(Arena A, ApiPtrs T, const DevP
                                                   const float* __restrict__ act, int tail, int N, int NR) {
   extern __shared__ float sh[];
   const unsigned long long pr_k0 = physics_prologue<GATED>(T, sh);
-  if (!GATED && act) actions_block(P->arena, T, P, act, N, NR);
+  if (!GATED && act) actions_block(P->arena, T, P, act, 0, N, NR);
   __syncthreads();
   if (!GATED || cnt[CNT_ANY_RESET] == T.stamp) {
     SubstepCarry K;   // (a single body: nothing carried)

@@ -48,7 +48,8 @@ class _ActionScalingView:
 
 
 class _ActionProcessorView:
-    """ActionProcessor public API (action_processor.py:668-755) backed by the k_actions kernel."""
+    """ActionProcessor public API (action_processor.py:668-755) backed by the device action stage (actions_block: on the
+    first physics launch of dexsim_step, or alone as k_actions)."""
 
     def __init__(self, env):
         self._env = env

@@ -707,8 +707,9 @@ def test_fused_step_equals_staged_step_bitwise(task, substeps):
     """dexsim_step (the physics launches with the action block on the first and the post block on 7 waves on the last, then
     the gated twin; with 4 sub-steps one launch each) against the three staged calls (k_actions, the physics launches without
     the blocks, k_post on 8 waves + the gated physics step) from identical state, over steps that include in-step resets:
-    every output and the whole carried state must be BIT-identical -- the fused production post block is thereby tied to the
-    stand-alone stages that the golden replays exercise."""
+    every output and the whole carried state must be BIT-identical.  k_actions runs the production action block itself, so
+    this ties the fused production post block (7 waves, box-wave pre-tasks) to the stand-alone k_post that the golden
+    replays exercise, and the action block inside a physics launch to the same block launched alone."""
     import torch
     from tests.hip_backend import HipBackend
     n = 200                                                  # 4 workgroups, the last one padded
@@ -738,6 +739,58 @@ def test_fused_step_equals_staged_step_bitwise(task, substeps):
             assert np.array_equal(a.get(f), b.get(f)), (t, f)
         resets += int(a.core.reset_buf.sum())
     assert resets >= n                                       # time-outs at step 6: the reset path was part of the comparison
+
+
+@pytest.mark.parametrize("zero_targets", [False, True], ids=["targets", "zero_targets"])
+@pytest.mark.parametrize("hand_base", [True, False], ids=["base_and_fingers", "fingers_only"])
+@pytest.mark.parametrize("mode", ["position_delta", "position"])
+def test_action_stage_matches_oracle(mode, hand_base, zero_targets):
+    """dexsim_process_actions against the oracle's process_actions from a seeded random active_prev_targets /
+    active_rule_targets state, N = 200 (the last workgroup padded).  fingers_only: task.policy_controls_hand_base = False,
+    12 actions that drive the finger controls, the base controls follow their rule targets.  zero_targets: the
+    pre-finalize_setup branch, every target 0 and active_prev_targets untouched.  actions, prev_actions, the action copy
+    and every zero_targets output must match exactly; computed targets / active_prev_targets within 1e-6 abs (a target is at
+    most two fp32 operations on values below 4 rad, so a contraction difference between hipcc and the C compiler stays
+    below that)."""
+    import torch
+    from oracle.oracle import Oracle
+    from tests.hip_backend import HipBackend
+    n = 200
+    sc, model = _mk("BlindGrasping", n, **{"task.controlMode": mode, "task.policy_controls_hand_base": hand_base})
+    na = int(sc.num_actions)
+    assert na == (18 if hand_base else 12)
+    ms = model.to_struct()
+    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
+    rng = np.random.default_rng(13)
+    lo, hi = np.array(sc.active_lower)[:, None], np.array(sc.active_upper)[:, None]
+    prev = rng.uniform(lo, hi, (18, n)).astype(np.float32)
+    state = {"active_prev_targets": prev, "active_rule_targets": np.clip(prev + rng.normal(0, 0.02, (18, n)), lo, hi),
+             "targets": rng.uniform(-1, 1, (26, n)), "actions": rng.uniform(-1, 1, (18, n))}
+    for k, v in state.items():
+        v = np.asarray(v, dtype=np.float32)
+        o.set(k, v)
+        hb.set(k, v)
+    copy = torch.full((n, na), 7.0, device="cuda:0")
+    hb.core.set_action_copy(copy)
+    act = rng.uniform(-1, 1, (n, na)).astype(np.float32)
+    o.process_actions(act, zero_targets)
+    hb.process_actions(act, zero_targets)
+    torch.cuda.synchronize()
+    a18 = np.zeros((18, n))
+    a18[:na] = act.T
+    for f in ("actions", "prev_actions"):
+        assert np.array_equal(o.get(f), a18), f
+        assert np.array_equal(hb.get(f), a18), f
+    assert np.array_equal(copy.cpu().numpy(), act)
+    tg = hb.get("targets")
+    assert np.array_equal(hb.core.full_dof_targets.cpu().numpy().T.astype(np.float64), tg)
+    if zero_targets:
+        assert np.array_equal(o.get("targets"), np.zeros((26, n))) and np.array_equal(tg, np.zeros((26, n)))
+        assert np.array_equal(o.get("active_prev_targets"), prev) and np.array_equal(hb.get("active_prev_targets"), prev)
+    else:
+        np.testing.assert_allclose(tg, o.get("targets"), rtol=0, atol=1e-6)
+        np.testing.assert_allclose(hb.get("active_prev_targets"), o.get("active_prev_targets"), rtol=0, atol=1e-6)
+        assert not np.array_equal(o.get("active_prev_targets"), prev)      # the step really moved the targets
 
 
 def test_level2_gym_shim_matches_fused_step():
