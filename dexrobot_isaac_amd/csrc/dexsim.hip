@@ -268,12 +268,11 @@ int dexsim_create(const DexSimConfig* cfg, const DexHandModel* model, int device
     for (int i = 3; i < 6; i++) if (model->inertia[j][i] != 0.f) hp.inertia_diag = 0;
   HIP_TRY(hipMalloc(&h->d_params, sizeof(DevParams)));
   HIP_TRY(hipMemcpy(h->d_params, &hp, sizeof(DevParams), hipMemcpyHostToDevice));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_post), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics1<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_physics1<true>), hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
+  const void* const big_lds_kernels[] = {
+      reinterpret_cast<const void*>(&k_solve), reinterpret_cast<const void*>(&k_post),
+      reinterpret_cast<const void*>(&k_physics4<false>), reinterpret_cast<const void*>(&k_physics4<true>),
+      reinterpret_cast<const void*>(&k_physics1<false>), reinterpret_cast<const void*>(&k_physics1<true>)};
+  for (const void* k : big_lds_kernels) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
   HIP_TRY(hipEventCreate(&h->ev0));
   HIP_TRY(hipEventCreate(&h->ev1));
   cleanup.armed = false;
@@ -331,21 +330,26 @@ static int launch_publish(dexsim_t h, int full, void* stream) {
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
+static int launch_post(dexsim_t h, int obs_only, int fold_reset, void* stream) {
+  k_post<<<dim3(h->NS / 64), dim3(512), POST_LDS_BYTES, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, obs_only, fold_reset, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}
 
 // LDS budget of the contact-solve kernel: stage the rows of as many contacts as fit next to u_f and the impulses.
 // At <= 1 wavefront per CU (num_envs <= 64 * #CUs) the whole 160 KiB is this wave's to use.
 static int solve_kstage(const DexSim* h) { return h->NS <= 64 * 256 ? 4 : 2; }   // 4: (60 + 7 KMAX + 4 x 84) words x 256 B = 141 KiB
 static size_t solve_lds_bytes(int kstage) { return (size_t)SOLVE_LDS_WORDS(kstage) * 64 * sizeof(float); }
 
-static int launch_solve(dexsim_t h, int last, void* stream) {
+static int launch_solve(dexsim_t h, void* stream) {
   const int ks = solve_kstage(h);
   const size_t lds = solve_lds_bytes(ks);
-  k_solve<<<dim3(h->NS / 64), dim3(64), lds, (hipStream_t)stream>>>(h->arena, h->d_params, h->api.counters, h->api.stamp, last, ks, h->NS, h->N);
+  k_solve<<<dim3(h->NS / 64), dim3(64), lds, (hipStream_t)stream>>>(h->arena, h->d_params, h->api.counters, h->api.stamp, ks, h->NS, h->N);
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
 static int launch_dynamics(dexsim_t h, void* stream) {
-  k_dynamics<<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, h->d_params, h->api.counters, h->api.stamp, h->NS);
+  k_dynamics<<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, h->d_params, h->NS);
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
@@ -403,9 +407,8 @@ int dexsim_physics_step(dexsim_t h, int gate_on_reset, void* stream) {
 int dexsim_post_physics(dexsim_t h, int obs_only, void* stream) {
   NEED_BOUND(h);
   // fold_reset: phase 0 of the in-step reset runs inside k_post
-  k_post<<<dim3(h->NS / 64), dim3(512), POST_LDS_BYTES, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, obs_only, !obs_only, h->NS, h->N);
-  LAUNCH_CHECK();
-  if (obs_only) return DEXSIM_OK;
+  const int rc = launch_post(h, obs_only, !obs_only, stream);
+  if (rc || obs_only) return rc;
   // reset_idx(nonzero(reset_buf)) incl. the extra physics step for ALL envs (step_processor.py:109-111,
   // reset_manager.py:180), gated on the device-side flag instead of torch.any() on the host; phase 1 + statistics run in its
   // last launch
@@ -476,7 +479,7 @@ static int launch_stage(dexsim_t h, int stage, void* stream) {
     return fail(DEXSIM_ERR_ARG, "the un-fused k_dynamics / k_solve test kernels do not build joint-limit rows (joint_limit_rows): use the fused path");
   switch (stage) {
     case DEXSIM_STAGE_DYNAMICS: return launch_dynamics(h, stream);
-    case DEXSIM_STAGE_SOLVE: return launch_solve(h, 1, stream);
+    case DEXSIM_STAGE_SOLVE: return launch_solve(h, stream);
     case DEXSIM_STAGE_PUBLISH: return launch_publish(h, 0, stream);
     case DEXSIM_STAGE_SUBSTEP:   // one sub-step as its own launch, counting its contacts
       k_physics1<false><<<dim3(h->NS / 64), dim3(448), FS_LDS_BYTES, (hipStream_t)stream>>>(
@@ -486,8 +489,8 @@ static int launch_stage(dexsim_t h, int stage, void* stream) {
     case DEXSIM_STAGE_STEP:   // the ungated half of dexsim_step: actions + all sub-steps + post-physics, same arguments
       if (!h->last_actions) return fail(DEXSIM_ERR_ARG, "DEXSIM_STAGE_STEP needs a previous dexsim_step");
       return physics_step(h, 0, TAIL_POST, stream, h->last_actions);
-    case DEXSIM_STAGE_POST: k_post<<<dim3(h->NS / 64), dim3(512), POST_LDS_BYTES, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, 0, 0, h->NS, h->N); break;
-    case DEXSIM_STAGE_POST + 100: k_post<<<dim3(h->NS / 64), dim3(512), POST_LDS_BYTES, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, 1, 0, h->NS, h->N); break;
+    case DEXSIM_STAGE_POST: return launch_post(h, 0, 0, stream);
+    case DEXSIM_STAGE_POST + 100: return launch_post(h, 1, 0, stream);
     case DEXSIM_STAGE_RESET:   // both phases for the flagged envs, without the device-side gate and without physics
       k_reset<<<GRID(h)>>>(h->arena, h->api, h->d_params, nullptr, 0, 3, 0, h->NS, h->N);
       k_reset<<<GRID(h)>>>(h->arena, h->api, h->d_params, nullptr, 0, 3, 1, h->NS, h->N);

@@ -18,9 +18,9 @@
   /* compact L1 state read by the fused post-physics kernel */                                              \
   X(float, site_pose, 77) X(float, hand_vel, 6) X(float, cforce, 51) X(float, cf5, 15)                      \
   /* dynamics -> contact-solve interface (one sub-step) */                                                  \
-  X(float, jframe, 156) X(float, ufree, 32) X(float, fac_sinv, 21) X(float, fac_finv, 60)                   \
+  X(float, jframe, 156) X(float, ufree, 32) X(float, fac_finv, 60)                                          \
   X(float, fac_g, 120) X(int, ncontact, 1) X(float, cgeom, DEXSIM_KMAX * 8) X(int, ccode, DEXSIM_KMAX)      \
-  X(float, crow, DEXSIM_KMAX * 3 * 28) X(float, crowq, DEXSIM_KMAX * 3 * 28 + 4) X(float, cbias, DEXSIM_KMAX) X(float, clam, DEXSIM_KMAX * 3) X(float, chdr, DEXSIM_KMAX * 8) X(float, cstage, 6 * NP_STAGE * 9)                                         \
+  X(float, crow, DEXSIM_KMAX * 3 * 28) X(float, crowq, DEXSIM_KMAX * 3 * 28 + 4) X(float, clam, DEXSIM_KMAX * 3) X(float, chdr, DEXSIM_KMAX * 8) X(float, cstage, 6 * NP_STAGE * 9)                                         \
   /* warm-start cache: per contact key one float4 (impulses of the previous sub-step, tag), [key][env][4]; wgen = the env's sub-step generation */ \
   X(float, wlam, DEXSIM_NWKEY * 4) X(int, wgen, 1) X(int, csplit, 1)                                         \
   /* L2 state (ActionProcessor / ObservationEncoder / task / RewardCalculator / TerminationManager) */      \
@@ -85,7 +85,7 @@ struct DevParams {
   int obs_col_row[DEXSIM_OBS_ALL_DIM]; // obs_buf column -> obs_all row (flattened policy_observation_keys)
   JC jc[DEXSIM_NJ];  // packed copy of the per-joint model constants
   Arena arena;       // field pointers (filled by dexsim_bind): kernels with long live ranges read them on demand
-                     // through the scalar cache instead of pinning 114 SGPRs of by-value kernel arguments
+                     // through the scalar cache instead of pinning 110 SGPRs of by-value kernel arguments
 };
 
 // counters block (ints): reduction scratch + device-side control flags

@@ -149,6 +149,8 @@ DI float seg_box_dfdt(V3 a, V3 d, float t, float hb) {
 }
 
 // one capsule against the box (closest point of the axis + its far end, as sample spheres) and the ground (both ends)
+// (k_dynamics only.  Kept next to collide_capsules3: with k_dynamics on that one, 10-60 instructions of every k_physics* kernel
+// sit elsewhere -- same registers, same instruction multiset -- and the headline measured 0.5-0.9 % slower in 6 of 6 alternating runs.)
 DI void collide_capsule(const Arena& A, int N, int e, int& nc, const DexSimConfig& C, int cap, V3 e0, V3 e1, float r,
                         bool has_box, V3 bpos, const M3& Rb, float hb, float mu_hb, float mu_hg, int sw = -1, int* tmask = nullptr, int cinfo = 0) {
   const float co = C.contact_offset, rest = C.rest_offset;
@@ -909,45 +911,37 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
   // 16-byte LDS reads (round 2: 36 words [word][lane], 36 reads per contact)
 #pragma unroll
   for (int qd = 0; qd < 9; qd++) *(f4*)(sh + DL_SINV * 64 + ROWADDR(4 * qd, lane)) = f4{S[4 * qd], S[4 * qd + 1], S[4 * qd + 2], S[4 * qd + 3]};
-  {
-    int idx = 0;
 #pragma unroll
-    for (int i = 0; i < 6; i++) {
-      float acc = 0.f;
+  for (int i = 0; i < 6; i++) {
+    float acc = 0.f;
 #pragma unroll
-      for (int k = 0; k < 6; k++) acc += S[i * 6 + k] * tauB[k];
-      const float ub = B.qdb[i] + h * acc;
-      if (uB_out) uB_out[i] = ub;
-      else {
-        FLD(ufree, i) = ub;
-#pragma unroll
-        for (int k = 0; k <= i; k++) FLD(fac_sinv, idx++) = S[i * 6 + k];
-      }
-    }
+    for (int k = 0; k < 6; k++) acc += S[i * 6 + k] * tauB[k];
+    const float ub = B.qdb[i] + h * acc;
+    if (uB_out) uB_out[i] = ub;
+    else FLD(ufree, i) = ub;
   }
 }
 
 // rows of contact k in u-space: t = j_B - G_f^T j_f, S^-1 t, Fhat_f^-1 j_f, box parts, 1/D, bias
-// slot (fused general path): LDS row slot of this contact (>= 0), or -1 = the contact is streamed: its rows go to the arena in
-// the quad layout of the LDS row store (crowq: [quad][env][4], so that a 16-byte access moves four row words of a lane);
-// default (stand-alone kernels): slot k when k < kstage, else the SoA arena rows (crow).
-// split (fused general path): the env's packed split counts (SPLIT_*; 0 = no splitting): 1/D and the in-contact couplings A_rs
-// are those of the contact inside its solver block, where the hand base, the contact's finger and the box respond nB, nF and
-// nX times as strongly.  gen >= 0: warm start -- the contact's starting impulses come from the cache (slot by capsule / type /
-// sample, valid while its tag is 8 * gen) and go to s_lam.
-DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, const BaseChain& B, const float* sh, float* s_row,
-                           float* s_hdr, int kstage, int lane, int k, int N, int e, int slot = -2, int split = 0, int gen = -1,
-                           float* s_lam = nullptr, const float* s_bch = nullptr) {
+// FUSED (k_physics4 / k_physics1, general path): the rows go to the arena in the quad layout of the LDS row store (crowq:
+// [quad][env][4], so that a 16-byte access moves four row words of a lane), header and starting impulses to LDS (FS_HDR, FS_LAM),
+// and the base joints' axes and origins come from LDS (FS_BCH; B = nullptr).
+// !FUSED (stand-alone k_dynamics): SoA arena rows (crow), header and starting impulses to the arena (chdr, clam) for k_solve, base
+// joints from B.
+// split: the env's packed split counts (SPLIT_*; 0 = no splitting): 1/D and the in-contact couplings A_rs are those of the contact
+// inside its solver block, where the hand base, the contact's finger and the box respond nB, nF and nX times as strongly.
+// gen >= 0: warm start -- the contact's starting impulses come from the cache (slot by capsule / type / sample, valid while its
+// tag is 8 * gen); gen < 0: they start at zero.
+template <bool FUSED>
+DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, const BaseChain* B, float* sh, int lane, int k, int N, int e,
+                           int split, int gen) {
   // Built matrix by matrix, not row by row: every operand matrix (base joint frames, finger joint frames, G_f, Fhat_f^-1, S^-1)
   // is consumed for all three rows as soon as it is used, so that at most one of them is live next to the ~80 output words.
   // (Round 2 first looped over the rows with all five matrices live -- ~200 values: inlined in the sub-step kernel that cost
   // VGPR spills, and ANY scratch use makes short bursts of launches ~1.5x slower on this part, see DESIGN.md section 3.)
-  if (slot == -2) slot = (s_row && k < kstage) ? k : -3;
   const DexSimConfig& C = P->cfg;
   const float h = P->h;
-  const int b = k * 8;
   // ---- loads, round 1: the manifold entry, the box
-  (void)b;
   const f4 cg0 = *FQ(cgeom, 2 * k), cg1 = *FQ(cgeom, 2 * k + 1);
   const V3 p = {cg0.x, cg0.y, cg0.z};
   const V3 n = {cg0.w, cg1.x, cg1.y};
@@ -1006,9 +1000,9 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
 #pragma unroll
     for (int i2 = 0; i2 < 3; i2++) {
       V3 aa[2], oo[2];
-      if (s_bch) {   // two joints = 3 quads (bch_get2)
-        bch_get2(s_bch, lane, i2, aa[0], oo[0], aa[1], oo[1]);
-      } else { aa[0] = B.ab[2 * i2]; oo[0] = B.ob[2 * i2]; aa[1] = B.ab[2 * i2 + 1]; oo[1] = B.ob[2 * i2 + 1]; }
+      if (FUSED) {   // two joints = 3 quads (bch_get2)
+        bch_get2(sh + FS_BCH * 64, lane, i2, aa[0], oo[0], aa[1], oo[1]);
+      } else { aa[0] = B->ab[2 * i2]; oo[0] = B->ob[2 * i2]; aa[1] = B->ab[2 * i2 + 1]; oo[1] = B->ob[2 * i2 + 1]; }
 #pragma unroll
       for (int h = 0; h < 2; h++) {
         const int i = 2 * i2 + h;
@@ -1108,8 +1102,8 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
   for (int r = 0; r < 3; r++) {
     const float Dinv = (lim && r > 0) ? 0.f : 1.f / (Dq[r] + 1e-9f);
     const float pad = r == 0 ? A10 : (r == 1 ? A20 : A21);
-    const int rw = (k * 3 + r) * CROW_W, rws = (slot * 3 + r) * CROW_W;
-    if (slot == -1) {   // fused sub-step: quad layout in the arena
+    const int rw = (k * 3 + r) * CROW_W;
+    if (FUSED) {   // quad layout in the arena
       float* qb = A.crowq + ((size_t)(k * 21 + r * 7) * N + e) * 4;
       st4_global(qb, t[r][0], t[r][1], t[r][2], t[r][3]);
       st4_global(qb + (size_t)1 * N * 4, t[r][4], t[r][5], jf[r][0], jf[r][1]);
@@ -1118,7 +1112,7 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
       st4_global(qb + (size_t)4 * N * 4, Fj[r][0], Fj[r][1], Fj[r][2], Fj[r][3]);
       st4_global(qb + (size_t)5 * N * 4, db[r].x, db[r].y, db[r].z, rxd[r].x);
       st4_global(qb + (size_t)6 * N * 4, rxd[r].y, rxd[r].z, Dinv, pad);
-    } else if (slot < 0) {   // stand-alone kernels: rows go through the SoA arena rows
+    } else {   // stand-alone kernels: rows go through the SoA arena rows
 #pragma unroll
       for (int i = 0; i < 6; i++) { FLD(crow, rw + i) = t[r][i]; FLD(crow, rw + 10 + i) = St[r][i]; }
 #pragma unroll
@@ -1126,20 +1120,12 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
       FLD(crow, rw + 20) = db[r].x; FLD(crow, rw + 21) = db[r].y; FLD(crow, rw + 22) = db[r].z;
       FLD(crow, rw + 23) = rxd[r].x; FLD(crow, rw + 24) = rxd[r].y; FLD(crow, rw + 25) = rxd[r].z;
       FLD(crow, rw + 26) = Dinv; FLD(crow, rw + 27) = pad;
-    } else {                 // rows straight into an LDS row store
-      const float wds[28] = {t[r][0], t[r][1], t[r][2], t[r][3], t[r][4], t[r][5], jf[r][0], jf[r][1], jf[r][2], jf[r][3],
-                             St[r][0], St[r][1], St[r][2], St[r][3], St[r][4], St[r][5], Fj[r][0], Fj[r][1], Fj[r][2], Fj[r][3],
-                             db[r].x, db[r].y, db[r].z, rxd[r].x, rxd[r].y, rxd[r].z, Dinv, pad};
-#pragma unroll
-      for (int q = 0; q < 7; q++)   // rws is a multiple of 28: quad aligned
-        *(f4*)(s_row + ROWADDR(rws + 4 * q, lane)) = f4{wds[4 * q], wds[4 * q + 1], wds[4 * q + 2], wds[4 * q + 3]};
     }
   }
   const float cb = gap > 0.f ? gap / h : -fminf(-gap * C.erp / h, C.max_depenetration_velocity);
   const bool warm = gen >= 0 && __float_as_int(wq.w) == 8 * gen + (type == 2 ? CODE_SAMPLE(code) : 0);
   // compact per-contact header for the solve kernel: no dependent model look-ups on its critical path
-  if (!s_hdr) {
-    FLD(cbias, k) = cb;
+  if (!FUSED) {
     FLD(clam, 3 * k) = warm ? wq.x : 0.f; FLD(clam, 3 * k + 1) = warm ? wq.y : 0.f; FLD(clam, 3 * k + 2) = warm ? wq.z : 0.f;
     FLD(chdr, 8 * k + 0) = __int_as_float(code | (nFi << 12));
     FLD(chdr, 8 * k + 1) = __int_as_float(f >= 0 ? 4 * f : -1);
@@ -1148,18 +1134,17 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
   }
   FLD(chdr, 8 * k + 4) = __int_as_float(CODE_FSLOT(code));
   FLD(chdr, 8 * k + 5) = n.x; FLD(chdr, 8 * k + 6) = n.y; FLD(chdr, 8 * k + 7) = n.z;
-  if (s_hdr) {   // the fused kernel's LDS headers (all KMAX list entries)
+  if (FUSED) {   // the fused kernel's LDS headers (all KMAX list entries)
+    float* s_hdr = sh + FS_HDR * 64;
+    float* s_lam = sh + FS_LAM * 64;
     s_hdr[(4 * k) * 64 + lane] = __int_as_float(code | (nFi << 12)); s_hdr[(4 * k + 1) * 64 + lane] = __int_as_float(f >= 0 ? 4 * f : -1);
     s_hdr[(4 * k + 2) * 64 + lane] = mu_k; s_hdr[(4 * k + 3) * 64 + lane] = cb;
-    if (s_lam) {
-      s_lam[(3 * k) * 64 + lane] = warm ? wq.x : 0.f; s_lam[(3 * k + 1) * 64 + lane] = warm ? wq.y : 0.f;
-      s_lam[(3 * k + 2) * 64 + lane] = warm ? wq.z : 0.f;
-    }
+    s_lam[(3 * k) * 64 + lane] = warm ? wq.x : 0.f; s_lam[(3 * k + 1) * 64 + lane] = warm ? wq.y : 0.f;
+    s_lam[(3 * k + 2) * 64 + lane] = warm ? wq.z : 0.f;
   }
 }
 
-// (cnt, stamp: not read -- the stand-alone kernels never run gated -- but kept, so the kernel-argument layout stays as it was)
-__global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __restrict__ P, const int* __restrict__ cnt, int stamp, int N) {
+__global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __restrict__ P, int N) {
   __shared__ __attribute__((aligned(16))) float sh[(DL_SPLIT + 1) * 64];   // 16-byte aligned: S^-1 is stored as quads
   constexpr int dlb = DL_PERSIST;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1257,7 +1242,7 @@ __global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __re
   const int split = __float_as_int(SH(DL_SPLIT)), gen = FLD(wgen, 0);
 #pragma unroll 1
   for (int k = wv; k < kmax; k += 6) {
-    if (k < nc) build_contact_rows(A, P, B, sh, nullptr, nullptr, 0, lane, k, N, e, -2, split, gen);
+    if (k < nc) build_contact_rows<false>(A, P, &B, sh, lane, k, N, e, split, gen);
   }
 }
 
@@ -1421,23 +1406,21 @@ DI void cache_box_ground(const Arena& A, const float* s_lam, int gen, int cpack,
 
 // net contact force per body of the last sub-step (contact_collection: CC_LAST_SUBSTEP); the slot index is data
 // dependent per lane -> accumulate in LDS scratch s_f [51][64]
-// klds: how many list entries have their header / impulses in LDS (all of them since round 2's block solver)
 DI void solve_forces(const Arena& A, const DevParams* __restrict__ P, int* __restrict__ cnt, const float* s_hdr, const float* s_lam,
-                     float* s_f, int nc, int lane, int N, int e, int NR, int klds = DEXSIM_KMAX) {
+                     float* s_f, int nc, int lane, int N, int e, int NR) {
   const float h = P->h;
 #pragma unroll
   for (int i = 0; i < DEXSIM_NFSLOT * 3; i++) s_f[i * 64 + lane] = 0.f;
   int nhand = 0;
   for (int k = 0; k < nc; k++) {
-    const int type = __float_as_int(k < klds ? s_hdr[(4 * k) * 64 + lane] : FLD(chdr, 8 * k)) & 3;
+    const int type = __float_as_int(s_hdr[(4 * k) * 64 + lane]) & 3;
     nhand += type < 2 ? 1 : 0;
     if (type == 3) continue;   // a joint-limit reaction is a joint torque, not a force on a body
     const int slot = __float_as_int(FLD(chdr, 8 * k + 4));
     const V3 n = {FLD(chdr, 8 * k + 5), FLD(chdr, 8 * k + 6), FLD(chdr, 8 * k + 7)};
     V3 t1, t2;
     tangent_basis(n, t1, t2);
-    const float l0 = (k < klds ? s_lam[(3 * k) * 64 + lane] : FLD(clam, 3 * k)) / h, l1 = (k < klds ? s_lam[(3 * k + 1) * 64 + lane] : FLD(clam, 3 * k + 1)) / h,
-                l2 = (k < klds ? s_lam[(3 * k + 2) * 64 + lane] : FLD(clam, 3 * k + 2)) / h;
+    const float l0 = s_lam[(3 * k) * 64 + lane] / h, l1 = s_lam[(3 * k + 1) * 64 + lane] / h, l2 = s_lam[(3 * k + 2) * 64 + lane] / h;
     const V3 F = l0 * n + l1 * t1 + l2 * t2;
     s_f[(3 * slot) * 64 + lane] += F.x; s_f[(3 * slot + 1) * 64 + lane] += F.y; s_f[(3 * slot + 2) * 64 + lane] += F.z;
     if (type == 1) {
@@ -1563,8 +1546,8 @@ DI void integrate_box(const Arena& A, float h, const float* vb, const float* wb,
 
 // Stand-alone contact-solve kernel (profiling / staged tests; production runs the fused k_physics4 / k_physics1 below):
 // reads u_free, headers and rows from the arena, stages them in LDS, sweeps, integrates.
-__global__ __launch_bounds__(64) void k_solve(Arena A, const DevParams* __restrict__ P, int* __restrict__ cnt, int stamp, int last,
-                                              int kstage, int N, int NR) {
+__global__ __launch_bounds__(64) void k_solve(Arena A, const DevParams* __restrict__ P, int* __restrict__ cnt, int stamp, int kstage,
+                                              int N, int NR) {
   extern __shared__ float lds[];
   const int lane = threadIdx.x;
   const int e = blockIdx.x * 64 + lane;
@@ -1719,7 +1702,7 @@ __global__ __launch_bounds__(64) void k_solve(Arena A, const DevParams* __restri
     FLD(wgen, 0) = DEXSIM_WGEN_NEXT(gen);
   }
 
-  if (last) solve_forces(A, P, cnt + (stamp & 1), s_hdr, s_lam, s_row /* dead by now */, nc, lane, N, e, NR);
+  solve_forces(A, P, cnt + (stamp & 1), s_hdr, s_lam, s_row /* dead by now */, nc, lane, N, e, NR);
 
   // back-substitution qd = L^-1 u, semi-implicit Euler, joint-limit clamp
 #pragma unroll
@@ -2020,8 +2003,7 @@ DI void hand_warm(const HandRows& R, TurnVel& v, f2& G01, f2& G23, f2 inv_mI, co
 // everything else here -- a real call would spill the caller's live values around it.)
 DI void build_rows_item(const DevParams* __restrict__ P, int N, int ol, int k, int eo, int split, int gen) {
   extern __shared__ __attribute__((aligned(16))) float sh[];
-  BaseChain B;   // (unused: the builder reads the base joints' axes from LDS)
-  build_contact_rows(P->arena, P, B, sh, sh + FS_ROW * 64, sh + FS_HDR * 64, 0, ol, k, N, eo, -1, split, gen, sh + FS_LAM * 64, sh + FS_BCH * 64);
+  build_contact_rows<true>(P->arena, P, nullptr, sh, ol, k, N, eo, split, gen);
 }
 
 // ---- phases 3 and 4 of substep_body (general path: some hand contact in the workgroup) as a function of their own: everything the
@@ -2057,8 +2039,6 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
   float* s_uf = sh + FS_UF * 64;
   float* s_lam = sh + FS_LAM * 64;
   float* s_hdr = sh + FS_HDR * 64;
-  float* s_row = sh + FS_ROW * 64;
-  BaseChain B;   // (unused: the row builder reads the base joints' axes from LDS)
   int nc = __float_as_int(SH(DL_NC));
   const int nbg = (nc >> 8) & 0xff; nc &= 0xff;
   const int nh = nc - nbg;            // hand contacts of this lane
@@ -2074,12 +2054,11 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
   // (Round 3 tried the palm wave as the fourth item wave once more -- the four busy waves of the settled regime on four different
   // SIMDs, with the reduction of u_B moved off the palm wave: 180 -> 190 us settled, like round 2's 178 -> 188.  The palm wave shares
   // SIMD 2 with the box wave's block 12; two finger waves on one SIMD interleave better than that pair.)
-  const int widx = wv;
   if (wv == 6) __builtin_amdgcn_s_setprio(0);
   const int n_items = __builtin_amdgcn_readfirstlane(__float_as_int(sh[FS_NITEM * 64]));
   if (wv < 6) {
 #pragma unroll 1
-    for (int base = widx * 64; base < n_items; base += 6 * 64) {
+    for (int base = wv * 64; base < n_items; base += 6 * 64) {
       const int item = base + lane;
       if (item < n_items) {
         const int ent = __float_as_int(sh[FS_CTAB * 64 + item]);
@@ -2240,8 +2219,8 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
       if (fast) {
         // the common case: my item = ONE hand contact, resident in registers (rows, header, impulses) for all passes.  Per pass:
         // one batch of LDS reads (the common velocities), the update, the block's changes, the exchange.
-        const bool have = widx * 64 + lane_phys < n_items;
-        const int ent = have ? __float_as_int(sh[FS_CTAB * 64 + widx * 64 + lane_phys]) : lane_phys;
+        const bool have = wv * 64 + lane_phys < n_items;
+        const int ent = have ? __float_as_int(sh[FS_CTAB * 64 + wv * 64 + lane_phys]) : lane_phys;
         const int lane = ent & 0xff, blk = ent >> 8, e = blockIdx.x * 64 + lane;
         const int nc_o = __float_as_int(SH(DL_NC)), nbg_o = (nc_o >> 8) & 0xff;
         const int split_o = __float_as_int(SH(FS_SPLIT)), gen_o = __float_as_int(SH(FS_GEN));
@@ -2299,7 +2278,7 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
         // local velocities are carried from the first contact to the second.
         auto block_pass = [&](const bool warm) {
 #pragma unroll 1
-          for (int base = widx * 64; base < n_items; base += 6 * 64) {
+          for (int base = wv * 64; base < n_items; base += 6 * 64) {
             const bool have = base + lane_phys < n_items;
             const int ent = have ? __float_as_int(sh[FS_CTAB * 64 + base + lane_phys]) : lane_phys;
             const int lane = ent & 0xff, blk = ent >> 8, e = blockIdx.x * 64 + lane;
@@ -2364,7 +2343,7 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
         }
         // warm-start cache: the impulses my items' contacts end the sub-step with
 #pragma unroll 1
-        for (int base = widx * 64; base < n_items; base += 6 * 64) {
+        for (int base = wv * 64; base < n_items; base += 6 * 64) {
           if (base + lane_phys < n_items) {
             const int ent = __float_as_int(sh[FS_CTAB * 64 + base + lane_phys]);
             const int lane = ent & 0xff, blk = ent >> 8, e = blockIdx.x * 64 + lane;
@@ -2448,7 +2427,6 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   float* s_uf = sh + FS_UF * 64;
   float* s_lam = sh + FS_LAM * 64;
   float* s_hdr = sh + FS_HDR * 64;
-  float* s_row = sh + FS_ROW * 64;
   // the box wave's chain (rows, then the sweeps) is long and it shares its SIMD with the light palm wave: let the SIMD's
   // arbiter prefer it
   if (wv == 6) __builtin_amdgcn_s_setprio(2);
