@@ -5,4 +5,5 @@
     obs = env.reset(); obs, rew, done, info = env.step(actions)
 """
 from .config import default_cfg  # noqa: F401
+from .env import EnvState  # noqa: F401
 from .factory import create_dex_env, make_env  # noqa: F401

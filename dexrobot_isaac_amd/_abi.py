@@ -26,6 +26,7 @@ STAT = dict(SUCC_MEAN=0, FAIL_MEAN=4, SUCCESS_RATE=12, FAILURE_RATE=13, TIMEOUT_
 
 TASK_BASE, TASK_BLIND_GRASPING = 0, 1
 MODE_POSITION, MODE_POSITION_DELTA = 0, 1
+STATE_VERSION = 1   # DEXSIM_STATE_VERSION: layout of a state record / state bank
 STAGE = dict(DYNAMICS=0, SOLVE=1, PUBLISH=2, POST=3, RESET=4, FINALIZE=5, SUBSTEP=6, PHYSICS=7, STEP=8)
 
 SUCCESS_CRITERIA = ["grasp_lift_success"]
@@ -114,6 +115,8 @@ EXPORTED_SYMBOLS = [
     "dexsim_reset_idx", "dexsim_reset", "dexsim_refresh_body_states", "dexsim_set_dof_state_indexed",
     "dexsim_set_root_state_indexed", "dexsim_run_stage", "dexsim_time_stage", "dexsim_step_timing", "dexsim_set_step_sink", "dexsim_set_stats_sink", "dexsim_set_phase_probe", "dexsim_set_obs_dict_mode", "dexsim_set_action_copy", "dexsim_error_string",
     "dexsim_last_error",
+    "dexsim_state_layout", "dexsim_save_state", "dexsim_load_state", "dexsim_copy_envs", "dexsim_get_step_stamp",
+    "dexsim_set_step_stamp",
 ]
 
 
@@ -148,6 +151,12 @@ def declare_prototypes(lib):
     lib.dexsim_set_stats_sink.argtypes = [vp, vp]
     lib.dexsim_set_phase_probe.argtypes = [vp, vp]
     lib.dexsim_set_obs_dict_mode.argtypes = [vp, i32]
+    lib.dexsim_state_layout.argtypes = [P(DexSimConfig), P(DexSimField), i32, P(i32), P(sz)]
+    lib.dexsim_save_state.argtypes = [vp, vp, vp, i32, vp, C.c_int64, vp]
+    lib.dexsim_load_state.argtypes = [vp, vp, vp, i32, vp, C.c_int64, vp]
+    lib.dexsim_copy_envs.argtypes = [vp, vp, vp, i32, vp]
+    lib.dexsim_get_step_stamp.argtypes = [vp, P(i32)]
+    lib.dexsim_set_step_stamp.argtypes = [vp, i32]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = i32
     lib.dexsim_error_string.argtypes = [i32]

@@ -8,6 +8,26 @@ from . import _abi
 from ._lib import DexSimError, check, load
 
 
+class StateBank:
+    """A caller-owned state bank (include/dexsim.h): `data` is the flat float32 device tensor the library reads and writes,
+    the rest is what has to stay with it -- capacity, the record size and DEXSIM_STATE_VERSION."""
+
+    def __init__(self, data, capacity, record_words, layout, version=_abi.STATE_VERSION):
+        self.data, self.capacity, self.record_words, self.version = data, int(capacity), int(record_words), int(version)
+        self.layout = layout                      # name -> (word offset in the record, rows, is_int)
+        self.stride = (self.capacity + 63) // 64 * 64
+
+    def section(self, name):
+        """(rows, capacity) view of one section of the records, float32 or int32.  wlam is stored [quad][slot][4]: its view
+        is permuted so that row 4 q + c is word c of quad q, like every other section."""
+        off, rows, is_int = self.layout[name]
+        base = self.data.view(torch.int32) if is_int else self.data
+        flat = base[off * self.stride: (off + rows) * self.stride]
+        if name == "wlam":
+            return flat.view(rows // 4, self.stride, 4).permute(0, 2, 1).reshape(rows, self.stride)[:, : self.capacity]
+        return flat.view(rows, self.stride)[:, : self.capacity]
+
+
 class DexSimCore:
     def __init__(self, sim_cfg, model_struct, device):
         device = torch.device(device)
@@ -225,3 +245,77 @@ class DexSimCore:
         us = C.c_float(0)
         check(self.lib.dexsim_time_stage(self.h, int(stage), int(launches), self._stream(), C.byref(us)), "time_stage")
         return float(us.value)
+
+    # ------------------------------------------------------------------ state records (save / load / fork)
+    def state_layout(self):
+        """({section name: (word offset inside a record, rows, is_int)}, record_words) -- dexsim_state_layout."""
+        if getattr(self, "_state_layout", None) is None:      # fixed by the configuration: asked once
+            fields = (_abi.DexSimField * 128)()
+            nf, words = C.c_int(0), C.c_size_t(0)
+            check(self.lib.dexsim_state_layout(C.byref(self.cfg), fields, 128, C.byref(nf), C.byref(words)), "state_layout")
+            self._state_layout = ({fields[i].name.decode(): (int(fields[i].offset), int(fields[i].rows), bool(fields[i].is_int))
+                                   for i in range(nf.value)}, int(words.value))
+        return self._state_layout
+
+    def state_bank(self, capacity):
+        """A zeroed StateBank of `capacity` slots on this device (record_words * pad64(capacity) * 4 bytes)."""
+        layout, words = self.state_layout()
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise DexSimError(f"state_bank: capacity must be positive, got {capacity}")
+        data = torch.zeros(words * ((capacity + 63) // 64 * 64), dtype=torch.float32, device=self.device)
+        return StateBank(data, capacity, words, layout)
+
+    def _bank_args(self, bank, env_ids, slots, what):
+        if not isinstance(bank, StateBank):
+            raise DexSimError(f"{what}: bank must be a StateBank (DexSimCore.state_bank)")
+        _, words = self.state_layout()
+        if bank.version != _abi.STATE_VERSION:
+            raise DexSimError(f"{what}: state bank has version {bank.version}, this library writes version {_abi.STATE_VERSION}")
+        if bank.record_words != words:
+            raise DexSimError(f"{what}: state bank has record_words {bank.record_words}, this configuration needs {words}")
+        d = bank.data
+        if d.device != self.device or d.dtype != torch.float32 or not d.is_contiguous() or d.numel() != words * bank.stride:
+            raise DexSimError(f"{what}: the bank tensor must be contiguous float32 on {self.device} with record_words * pad64(capacity) elements")
+        if env_ids is None and slots is None:
+            return None, None, 0
+        if env_ids is None or slots is None:     # one side given: the other side counts 0, 1, 2, ...
+            n = len(slots if env_ids is None else env_ids)
+            rng = torch.arange(n, device=self.device)
+            env_ids, slots = (rng if env_ids is None else env_ids), (rng if slots is None else slots)
+        e = torch.as_tensor(env_ids, device=self.device).to(torch.int64).contiguous().view(-1)
+        s = torch.as_tensor(slots, device=self.device).to(torch.int64).contiguous().view(-1)
+        if e.numel() != s.numel():
+            raise DexSimError(f"{what}: {e.numel()} env ids but {s.numel()} slots")
+        self._keep_state_ids = (e, s)
+        return e, s, int(e.numel())
+
+    def save_state(self, bank, env_ids=None, slots=None):
+        """Records of `env_ids` -> bank slots `slots` (dexsim_save_state); both None = every lane to the slot of its own index."""
+        e, s, k = self._bank_args(bank, env_ids, slots, "save_state")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        check(self.lib.dexsim_save_state(self.h, ptr(e), ptr(s), k, C.c_void_p(bank.data.data_ptr()), bank.capacity, self._stream()), "save_state")
+
+    def load_state(self, bank, env_ids=None, slots=None):
+        """Bank slots `slots` -> records of `env_ids` (dexsim_load_state); env_ids must not repeat."""
+        e, s, k = self._bank_args(bank, env_ids, slots, "load_state")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        check(self.lib.dexsim_load_state(self.h, ptr(e), ptr(s), k, C.c_void_p(bank.data.data_ptr()), bank.capacity, self._stream()), "load_state")
+
+    def copy_envs(self, src_ids, dst_ids):
+        """Fork: record of env src_ids[i] -> env dst_ids[i] (dexsim_copy_envs).  Precondition, not checked here: the
+        destinations are unique and disjoint from the sources (DexHandEnv.fork_envs checks it)."""
+        a = torch.as_tensor(src_ids, device=self.device).to(torch.int64).contiguous().view(-1)
+        b = torch.as_tensor(dst_ids, device=self.device).to(torch.int64).contiguous().view(-1)
+        if a.numel() != b.numel():
+            raise DexSimError(f"copy_envs: {a.numel()} sources but {b.numel()} destinations")
+        self._keep_state_ids = (a, b)
+        check(self.lib.dexsim_copy_envs(self.h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), int(a.numel()), self._stream()), "copy_envs")
+
+    def get_step_stamp(self):
+        v = C.c_int(0)
+        check(self.lib.dexsim_get_step_stamp(self.h, C.byref(v)), "get_step_stamp")
+        return int(v.value)
+
+    def set_step_stamp(self, stamp):
+        check(self.lib.dexsim_set_step_stamp(self.h, int(stamp)), "set_step_stamp")

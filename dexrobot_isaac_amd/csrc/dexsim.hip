@@ -9,10 +9,12 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 // clang-format off
 #include "dexsim_physics.hip.inc"
 #include "dexsim_l2.hip.inc"
+#include "dexsim_state.hip.inc"
 // clang-format on
 
 // The post block runs in the sub-step kernels' LDS behind their last body (TAIL_POST); the box wave starts its tile during the
@@ -607,3 +609,144 @@ const char* dexsim_error_string(int code) {
 const char* dexsim_last_error(void) { return g_last_error.c_str(); }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------- state records
+// Record = [ROWS-layout state fields, in DEXSIM_STATE_FIELDS order][wlam quads][API sections]; word offsets inside a record.
+struct StateLayout {
+  int off_wlam, off_obs, off_rew, off_reset, off_esc, off_elen, off_dof, off_root, off_fdt, off_masks, words;
+  int num_obs, root_words;
+};
+static StateLayout state_layout_of(const DexSimConfig& c) {
+  StateLayout L;
+  int o = STATE_NROWS;
+  L.off_wlam = o; o += DEXSIM_ROWS_wlam;
+  L.num_obs = c.num_obs; L.root_words = 13 * (1 + (c.has_box ? 1 : 0));
+  L.off_obs = o; o += c.num_obs;
+  L.off_rew = o; o += 1;
+  L.off_reset = o; o += 1;
+  L.off_esc = o; o += 2;
+  L.off_elen = o; o += 2;
+  L.off_dof = o; o += DEXSIM_NJ * 2;
+  L.off_root = o; o += L.root_words;
+  L.off_fdt = o; o += DEXSIM_NJ;
+  L.off_masks = o; o += (DEXSIM_NUM_MASKS + 3) / 4;
+  L.words = o;
+  return L;
+}
+
+extern "C" int dexsim_state_layout(const DexSimConfig* cfg, DexSimField* fields, int max_fields, int* n_fields, size_t* record_words) {
+  if (!cfg || !n_fields || !record_words || cfg->num_envs <= 0 || cfg->num_obs <= 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_state_layout: bad argument");
+  const StateLayout L = state_layout_of(*cfg);
+  int n = 0;
+  auto put = [&](const char* prefix, const char* name, int rows, int is_int, int off) {
+    if (fields) {
+      if (n >= max_fields) return false;
+      std::snprintf(fields[n].name, sizeof fields[n].name, "%s%s", prefix, name);
+      fields[n].rows = rows; fields[n].is_int = is_int; fields[n].offset = (size_t)off;
+    }
+    n++;
+    return true;
+  };
+  int off = 0;
+#define X(nm, layout)                                                                                                         \
+  if (DEXSIM_LAYOUT_##layout == DEXSIM_LAYOUT_ROWS) {                                                                         \
+    if (!put("", #nm, DEXSIM_ROWS_##nm, std::is_same<decltype(Arena::nm), int*>::value, off)) return fail(DEXSIM_ERR_LAYOUT, "field table too small"); \
+    off += DEXSIM_ROWS_##nm;                                                                                                  \
+  }
+  DEXSIM_STATE_FIELDS(X)
+#undef X
+  const struct { const char* name; int rows, is_int, off; } sec[] = {
+      {"wlam", DEXSIM_ROWS_wlam, 0, L.off_wlam},
+      {"api.obs_buf", L.num_obs, 0, L.off_obs}, {"api.rew_buf", 1, 0, L.off_rew}, {"api.reset_buf", 1, 1, L.off_reset},
+      {"api.episode_step_count", 2, 1, L.off_esc}, {"api.episode_length", 2, 1, L.off_elen},
+      {"api.dof_state", DEXSIM_NJ * 2, 0, L.off_dof}, {"api.root_state", L.root_words, 0, L.off_root},
+      {"api.full_dof_targets", DEXSIM_NJ, 0, L.off_fdt}, {"api.masks", (DEXSIM_NUM_MASKS + 3) / 4, 1, L.off_masks}};
+  for (const auto& s : sec)
+    if (!put("", s.name, s.rows, s.is_int, s.off)) return fail(DEXSIM_ERR_LAYOUT, "field table too small");
+  *n_fields = n;
+  *record_words = (size_t)L.words;
+  return DEXSIM_OK;
+}
+
+// The three kernels of the family.  Named here, behind every use of the step kernels, so that the compiler also emits them behind
+// the step kernels: the code object keeps the step path's kernels where they were.
+static constexpr auto k_state_save = &k_state_xfer<ST_SAVE>;   // instance -> bank
+static constexpr auto k_state_load = &k_state_xfer<ST_LOAD>;   // bank -> instance
+static constexpr auto k_state_copy = &k_state_xfer<ST_COPY>;   // instance -> instance (fork)
+
+// The launch of one of them: every chunk of the record x every tile of 64 lanes.
+static int state_xfer(dexsim_t h, int mode, const int64_t* src_idx, const int64_t* dst_idx, int k, long long src_lim, long long dst_lim,
+                      void* bank, long long capacity, void* stream) {
+  const StateLayout L = state_layout_of(h->cfg);
+  StateXfer X;
+  std::memset(&X, 0, sizeof X);
+  X.src_idx = src_idx; X.dst_idx = dst_idx; X.k = k; X.src_lim = src_lim; X.dst_lim = dst_lim;
+  X.bank = (unsigned*)bank; X.caps = (capacity + 63) / 64 * 64;
+  X.n_row_chunks = (STATE_NROWS + ST_ROW_CHUNK - 1) / ST_ROW_CHUNK;
+  X.n_quad_chunks = (STATE_NQUADS + ST_QUAD_CHUNK - 1) / ST_QUAD_CHUNK;
+  X.off_wlam = L.off_wlam; X.off_rew = L.off_rew; X.off_reset = L.off_reset; X.off_esc = L.off_esc; X.off_elen = L.off_elen;
+  X.off_masks = L.off_masks;
+  const struct { float* base; int len, off; } aos[] = {{h->api.obs_buf, L.num_obs, L.off_obs}, {h->api.dof_state, DEXSIM_NJ * 2, L.off_dof},
+                                                       {h->api.root_state, L.root_words, L.off_root}, {h->api.full_dof_targets, DEXSIM_NJ, L.off_fdt}};
+  for (const auto& a : aos) {
+    if (!a.base) continue;   // an optional API tensor that is not bound has no rows to move
+    for (int c0 = 0; c0 < a.len; c0 += ST_AOS_CHUNK) {
+      if (X.n_aos >= ST_MAX_AOS) return fail(DEXSIM_ERR_ARG, "state transfer: observation row too long for the AoS chunk table");
+      X.aos[X.n_aos++] = StateAos{(unsigned*)a.base, a.len, c0, std::min(ST_AOS_CHUNK, a.len - c0), a.off};
+    }
+  }
+  const dim3 grid((k + 63) / 64, X.n_row_chunks + X.n_quad_chunks + X.n_aos + 1), block(256);
+  auto* kern = mode == ST_SAVE ? k_state_save : mode == ST_LOAD ? k_state_load : k_state_copy;
+  kern<<<grid, block, 0, (hipStream_t)stream>>>(h->api, h->d_params, X, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}
+
+static int state_save_load(dexsim_t h, int mode, const int64_t* env_ids, const int64_t* slots, int k, void* bank, int64_t capacity, void* stream) {
+  const char* who = mode == ST_SAVE ? "dexsim_save_state" : "dexsim_load_state";
+  const bool identity = !env_ids && !slots;
+  if (k < 0) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": k must not be negative").c_str());
+  NEED_BOUND(h);
+  if (!bank) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": the state bank is NULL").c_str());
+  if (((uintptr_t)bank & 15) != 0) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": the state bank must be 16-byte aligned").c_str());
+  if (capacity <= 0 || capacity > 0x7fffffc0ll) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": bad capacity").c_str());
+  if (identity) {
+    if (capacity < h->NS) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": the identity over all lanes needs capacity >= NS = pad64(num_envs)").c_str());
+    k = h->NS;
+  } else if (!env_ids || !slots) {
+    return fail(DEXSIM_ERR_ARG, (std::string(who) + ": env_ids and slots must both be given (or both NULL: identity)").c_str());
+  }
+  if (k == 0) return DEXSIM_OK;
+  const long long env_lim = identity ? h->NS : h->N;
+  return mode == ST_SAVE ? state_xfer(h, mode, env_ids, slots, k, env_lim, capacity, bank, capacity, stream)
+                         : state_xfer(h, mode, slots, env_ids, k, capacity, env_lim, bank, capacity, stream);
+}
+
+extern "C" int dexsim_save_state(dexsim_t h, const int64_t* env_ids, const int64_t* slots, int k, void* bank, int64_t capacity, void* stream) {
+  return state_save_load(h, ST_SAVE, env_ids, slots, k, bank, capacity, stream);
+}
+extern "C" int dexsim_load_state(dexsim_t h, const int64_t* env_ids, const int64_t* slots, int k, const void* bank, int64_t capacity, void* stream) {
+  return state_save_load(h, ST_LOAD, env_ids, slots, k, const_cast<void*>(bank), capacity, stream);
+}
+
+extern "C" int dexsim_copy_envs(dexsim_t h, const int64_t* src_ids, const int64_t* dst_ids, int k, void* stream) {
+  if (k < 0) return fail(DEXSIM_ERR_ARG, "dexsim_copy_envs: k must not be negative");
+  NEED_BOUND(h);
+  if (k == 0) return DEXSIM_OK;
+  if (!src_ids || !dst_ids) return fail(DEXSIM_ERR_ARG, "dexsim_copy_envs: src_ids and dst_ids are required");
+  return state_xfer(h, ST_COPY, src_ids, dst_ids, k, h->N, h->N, nullptr, 0, stream);
+}
+
+extern "C" int dexsim_get_step_stamp(dexsim_t h, int* stamp) {
+  if (!h) return fail(DEXSIM_ERR_ARG, "null handle");
+  if (!stamp) return fail(DEXSIM_ERR_ARG, "dexsim_get_step_stamp: null argument");
+  *stamp = h->api.stamp;
+  return DEXSIM_OK;
+}
+extern "C" int dexsim_set_step_stamp(dexsim_t h, int stamp) {
+  if (!h) return fail(DEXSIM_ERR_ARG, "null handle");
+  if (stamp < 1 || stamp > 0x3ffffffe) return fail(DEXSIM_ERR_ARG, "dexsim_set_step_stamp: the stamp must be in [1, 0x3ffffffe]");
+  h->api.stamp = stamp;
+  return DEXSIM_OK;
+}

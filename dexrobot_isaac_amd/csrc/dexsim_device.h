@@ -45,6 +45,42 @@ struct Arena {
 #undef X
 };
 
+// (name, layout) -- the *persistent* arena fields: what dexsim_save_state / dexsim_load_state / dexsim_copy_envs move for an env
+// (the arena part of a state record, include/dexsim.h).  Layout ROWS = plain [row][env] words, QUAD = [quad][env][4] (one
+// 16-byte access per lane and quad).  Type and row count come from DEXSIM_FIELDS (DEXSIM_ROWS_<name> below), so the two lists
+// cannot drift apart: a name that is not an arena field does not compile.
+//
+// Every field of DEXSIM_FIELDS is listed except the hand-off scratch of ONE sub-step, whose first access in a sub-step is a
+// write, or a read guarded by data written earlier in the same sub-step:
+//   jframe, fac_g, fac_finv  written by the chain walk / factorisation of every finger and base wave before the row builder and
+//                            the Schur phase read them back;
+//   ufree                    every word written by the free-velocity pass (fingers, base, box: the box rows are zeroed when
+//                            there is no box) before the solve reads it;
+//   cstage, cgeom, ccode     the narrowphase stages and compacts the sub-step's manifold; readers index below the contact count
+//                            (DL_NC in LDS, or ncontact written by the same sub-step in the staged kernels);
+//   crow, crowq, clam, chdr  written per list entry k < nc by the row builder, read for k < nc only (crowq's always-zero quad row
+//                            is never written: it is zero from dexsim_init_state on, in every instance);
+//   csplit                   written next to ncontact by the narrowphase, read by the solve of the same sub-step.
+// ncontact IS part of the record although the kernels rewrite it before they read it: it is observable after the last sub-step.
+// A record is therefore defined at control-step boundaries (and at sub-step boundaries of the staged entry points) only; the
+// k_dynamics -> k_solve hand-off of the stand-alone test kernels is deliberately not part of it.
+#define DEXSIM_STATE_FIELDS(X)                                                                              \
+  X(q, ROWS) X(qd, ROWS) X(targets, ROWS) X(box_pos, ROWS) X(box_quat, ROWS) X(box_lin, ROWS) X(box_ang, ROWS) \
+  X(box_mass, ROWS) X(box_mu, ROWS) X(site_pose, ROWS) X(hand_vel, ROWS) X(cforce, ROWS) X(cf5, ROWS)       \
+  X(ncontact, ROWS) X(wlam, QUAD) X(wgen, ROWS)                                                             \
+  X(active_prev_targets, ROWS) X(active_rule_targets, ROWS) X(prev_actions, ROWS) X(actions, ROWS)          \
+  X(prev_dof_pos, ROWS) X(contact_duration_steps, ROWS) X(prev_contact_binary, ROWS) X(episode_step, ROWS)  \
+  X(success_duration_steps, ROWS) X(success_conditions_met, ROWS) X(current_stage, ROWS) X(just2, ROWS)     \
+  X(just3, ROWS) X(time_in_stage, ROWS) X(stage_contact_duration, ROWS) X(initial_box_pos, ROWS)            \
+  X(prev_finger_dof_vel, ROWS) X(prev_hand_vel, ROWS) X(prev_hand_ang_vel, ROWS) X(prev_contacts, ROWS)     \
+  X(episode_success, ROWS) X(episode_failure, ROWS) X(success_reason, ROWS) X(failure_reason, ROWS)         \
+  X(crit_success, ROWS) X(crit_failure, ROWS) X(term_success, ROWS) X(term_failure, ROWS)                   \
+  X(term_timeout, ROWS) X(obs_all, ROWS) X(rew_comp, ROWS) X(rew, ROWS) X(reset_flag, ROWS)                 \
+  X(reset_count, ROWS)
+
+#define DEXSIM_LAYOUT_ROWS 0
+#define DEXSIM_LAYOUT_QUAD 1
+
 // Quad layout (round 3): the per-finger factor hand-off -- fac_g (G_f, 24 words = 6 quads per finger), fac_finv (Fhat_f^-1 lower
 // triangle, 10 words in 3 quads per finger) and the finger part of jframe (axes + origins of the finger's 4 joints, 24 words = 6
 // quads per finger, behind the 36 row-layout words of the base joints) -- is stored [quad][env][4]: a lane moves four consecutive
@@ -60,6 +96,12 @@ struct Arena {
 #define CROW_W 28 /* words per contact row: t6 jf4 St6 Fj4 d3 rxd3 Dinv pad */
 // crowq: the rows of streamed hand contacts in the quad layout of the LDS row store ([quad][env] of float4, 21 quads per
 // contact), followed by ONE always-zero quad row (index KMAX * 21) that lanes without the contact read instead
+
+enum {   // DEXSIM_ROWS_<field>: row count of every arena field (for DEXSIM_STATE_FIELDS)
+#define X(type, name, rows) DEXSIM_ROWS_##name = (rows),
+  DEXSIM_FIELDS(X)
+#undef X
+};
 
 // per-joint constants packed as one 128-byte record: a wave fetches everything it needs about joint j with two
 // s_load_dwordx16 instead of ~12 scattered scalar loads (the base-chain walk was scalar-load-latency bound)

@@ -7,14 +7,53 @@ bookkeeping and the hooks for host-side custom rules.  There is no CPU path in t
 raises (the reference's CPU pipeline is itself documented as broken for multi-env, docs/guide-debugging.md:309-353).
 """
 import copy
+import hashlib
 
 import numpy as np
 import torch
 
 from . import _abi
+from ._lib import DexSimError
 from .config import (FINGER_COUPLING_MAP, HARDWARE_MAPPING, OBS_KEYS, REWARD_TERMS, build_sim_config,
                      obs_key_offsets)
 from .spaces import Box
+
+
+class EnvState:
+    """A full snapshot of a DexHandEnv (DexHandEnv.get_state): the state bank with the record of every lane, the two global
+    blocks (stats, counters), the step stamp, env.actions and the host-side state of the action-processor view -- plus what
+    identifies the instance it fits: DEXSIM_STATE_VERSION, record_words, num_envs and a hash of the DexSimConfig / DexHandModel
+    bytes.  Tensors stay on the device they were taken on; save() / load() move them through a plain dict of CPU tensors."""
+
+    _TENSORS = ("bank", "stats", "counters", "actions")
+    _INTS = ("version", "record_words", "num_envs", "capacity", "stamp")
+
+    def __init__(self, version, record_words, num_envs, config_hash, capacity, stamp, bank, stats, counters, actions,
+                 enabled_post_action_filters):
+        self.version, self.record_words, self.num_envs = int(version), int(record_words), int(num_envs)
+        self.config_hash, self.capacity, self.stamp = str(config_hash), int(capacity), int(stamp)
+        self.bank, self.stats, self.counters, self.actions = bank, stats, counters, actions
+        self.enabled_post_action_filters = [str(n) for n in enabled_post_action_filters]
+
+    def to_dict(self):
+        d = {k: getattr(self, k).detach().cpu() for k in self._TENSORS}
+        d.update({k: int(getattr(self, k)) for k in self._INTS})
+        d["config_hash"] = self.config_hash
+        d["enabled_post_action_filters"] = list(self.enabled_post_action_filters)
+        return d
+
+    def save(self, path):
+        torch.save(self.to_dict(), path)
+
+    @classmethod
+    def load(cls, path, device="cpu"):
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        missing = [k for k in cls._TENSORS + cls._INTS + ("config_hash", "enabled_post_action_filters") if k not in d]
+        if missing:
+            raise DexSimError(f"EnvState.load: '{path}' is not an EnvState file (missing {missing})")
+        return cls(**{k: d[k] for k in cls._INTS}, config_hash=d["config_hash"],
+                   enabled_post_action_filters=d["enabled_post_action_filters"],
+                   **{k: d[k].to(device) for k in cls._TENSORS})
 
 
 class _PhysicsManagerView:
@@ -582,6 +621,85 @@ class DexHandEnv:
                 out[:, 6:] = finger_controller(self)
             return out
         self.action_processor.set_pre_action_rule(rule if (base_controller or finger_controller) else None)
+
+    # ------------------------------------------------------------------ save / restore / fork (dexsim_save_state and friends)
+    def _state_core(self, what):
+        core = self._core
+        for m in ("state_layout", "state_bank", "save_state", "load_state", "copy_envs", "get_step_stamp", "set_step_stamp"):
+            if not hasattr(core, m):
+                raise DexSimError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no {m}()")
+        return core
+
+    def _config_hash(self):
+        return hashlib.sha256(bytes(self._sim_cfg) + bytes(self._model_struct)).hexdigest()
+
+    def get_state(self):
+        """Full snapshot (EnvState) of this env at a control-step boundary; set_state() of it, here or in a fresh env of the
+        same configuration, continues bit for bit."""
+        core = self._state_core("get_state")
+        bank = core.state_bank(core.NS)
+        core.save_state(bank)
+        ap = self.action_processor
+        return EnvState(bank.version, bank.record_words, self.num_envs, self._config_hash(), bank.capacity, core.get_step_stamp(),
+                        bank.data, core.stats.clone(), core.counters.clone(), self.actions.clone(),
+                        ap._enabled_post_action_filters)
+
+    def set_state(self, state):
+        """Restore a snapshot taken by get_state().  Every env-owned tensor (obs_buf, rew_buf, reset_buf, extras, obs_dict,
+        dof_state, actor_root_state_tensor, ...) is written in place: the views callers hold stay valid."""
+        core = self._state_core("set_state")
+        from .core import StateBank
+        layout, words = core.state_layout()
+        for name, mine, theirs in (("version", _abi.STATE_VERSION, state.version), ("record_words", words, state.record_words),
+                                   ("num_envs", self.num_envs, state.num_envs), ("config_hash", self._config_hash(), state.config_hash)):
+            if mine != theirs:
+                raise DexSimError(f"set_state: the state does not fit this env: {name} is {theirs}, expected {mine}")
+        if state.capacity < core.NS:
+            raise DexSimError(f"set_state: the state does not fit this env: capacity is {state.capacity}, expected at least {core.NS}")
+        dev = core.device
+        bank = StateBank(state.bank.to(dev), state.capacity, state.record_words, layout, state.version)
+        core.load_state(bank)
+        core.stats.copy_(state.stats.to(dev))
+        core.counters.copy_(state.counters.to(dev))
+        core.set_step_stamp(state.stamp)
+        self.actions.copy_(state.actions.to(self.actions.device))
+        self.action_processor._enabled_post_action_filters = list(state.enabled_post_action_filters)
+
+    def state_bank(self, capacity):
+        """A state bank of `capacity` slots for save_states / load_states (a bank of grasp states, a curriculum, ...)."""
+        return self._state_core("state_bank").state_bank(capacity)
+
+    def save_states(self, bank, slots, env_ids):
+        """Records of envs `env_ids` -> slots `slots` of `bank`."""
+        self._state_core("save_states").save_state(bank, env_ids=env_ids, slots=slots)
+
+    def load_states(self, bank, slots, env_ids):
+        """Slots `slots` of `bank` -> envs `env_ids` (unique): reset-to-stored-state.  Only those envs change."""
+        self._state_core("load_states").load_state(bank, env_ids=env_ids, slots=slots)
+
+    def fork_envs(self, src_ids, dst_ids, check=True):
+        """Copy env src_ids[i] onto env dst_ids[i] (a source may repeat).  The destinations must be unique and none may also be a
+        source; check=True verifies that (and the id range) on the device, which costs a host synchronisation: pass
+        check=False when forking every step with ids known to be good."""
+        core = self._state_core("fork_envs")
+        src = torch.as_tensor(src_ids, device=core.device).to(torch.int64).view(-1)
+        dst = torch.as_tensor(dst_ids, device=core.device).to(torch.int64).view(-1)
+        if src.numel() != dst.numel():
+            raise DexSimError(f"fork_envs: {src.numel()} sources but {dst.numel()} destinations")
+        if check and src.numel():
+            n = self.num_envs
+            hits = torch.zeros(n, dtype=torch.int32, device=core.device)
+            ok = bool(((src >= 0) & (src < n)).all() & ((dst >= 0) & (dst < n)).all())
+            if not ok:
+                raise DexSimError(f"fork_envs: env ids must be in [0, {n})")
+            hits.index_add_(0, dst, torch.ones_like(dst, dtype=torch.int32))
+            is_src = torch.zeros(n, dtype=torch.bool, device=core.device)
+            is_src[src] = True
+            if bool((hits > 1).any()):
+                raise DexSimError("fork_envs: a destination env is listed more than once")
+            if bool(((hits > 0) & is_src).any()):
+                raise DexSimError("fork_envs: a destination env is also a source")
+        core.copy_envs(src, dst)
 
     def render(self, mode="rgb_array"):
         return None                                              # headless: no viewer / recorder / streamer

@@ -422,6 +422,68 @@ int dexsim_time_stage(dexsim_t h, int stage, int launches, void* stream, float* 
  * cost the kernel its warm L2: +30 % on MI355X; bench.py therefore times the whole region instead.) */
 int dexsim_step_timing(dexsim_t h, int enable, float* mean_us, int* n);
 
+/* ------------------------------------------------------------------ save, restore and fork of simulation state
+ * (new capability: the reference keeps its state inside PhysX and a dozen Python objects and cannot hand it out)
+ *
+ * The STATE RECORD of one env is everything that decides how that env continues:
+ *   - its share of every *persistent* arena field (DEXSIM_STATE_FIELDS in dexsim_device.h: every arena field except the
+ *     hand-off scratch of a single sub-step -- joint frames, factors, manifold, contact rows).  That includes the warm-start
+ *     cache (wlam, wgen), FSM stage and timers, contact durations, previous-velocity rows, episode counters, reward
+ *     bookkeeping, the per-env box parameters (box_mass, box_mu) and reset_count, the Philox key of the env's next reset;
+ *   - its rows of the published API tensors: obs_buf, rew_buf, reset_buf, episode_step_count, episode_length, dof_state,
+ *     root_state, full_dof_targets and its column of masks.  They are stored and restored, not recomputed: a load launches
+ *     no publication and changes no bit of any env outside its id list.  rigid_body_states / contact_forces_all are
+ *     materialised on access (dexsim_refresh_body_states) and are not part of the record.
+ * A record is defined at control-step boundaries (between two dexsim_step calls, after dexsim_reset / dexsim_reset_idx), and at
+ * sub-step boundaries for the staged entry points (dexsim_physics_step, DEXSIM_STAGE_SUBSTEP).  The hand-off between the
+ * stand-alone DEXSIM_STAGE_DYNAMICS and DEXSIM_STAGE_SOLVE launches is deliberately not part of it.
+ *
+ * Records live in a caller-allocated device buffer, the STATE BANK, of `capacity` slots:
+ * record_words * pad64(capacity) * 4 bytes (pad64 = rounded up to a multiple of 64), 16-byte aligned.  Its internal layout is
+ * the library's (slot-fastest SoA; dexsim_state_layout describes one record) and is versioned by DEXSIM_STATE_VERSION: keep the
+ * version, record_words and the configuration next to any bank that outlives the process.  The library allocates nothing.
+ *
+ * Outside the records there are two small caller-owned global blocks, `stats` and `counters` (DexSimBuffers; the latter holds
+ * the consecutive-successes count and the reward calculator's lazy-init flag), and ONE host-side word, the step stamp.  A full
+ * snapshot of an instance = a bank of >= NS slots saved in identity mode + copies of stats and counters + the stamp.
+ *
+ * Semantics:
+ *   - Whole-instance restore is bitwise: a snapshot loaded into the same instance, or into a fresh one with the same
+ *     configuration and model, continues bit for bit.
+ *   - A fork or indexed load onto arbitrary lanes is exact for the moved envs at that moment but need not continue bitwise
+ *     like the source: the 64 envs of a workgroup take workgroup-uniform decisions together (hand-clear or general contact
+ *     path, the wave-wide stop of the box sweeps).  A whole workgroup copied onto another in the same lane order does.
+ *   - Resets key Philox by (env index, reset_count): a forked env draws its own randoms at its next reset unless
+ *     reset_samples are injected.
+ *   - box_mass / box_mu travel with the record: a fork takes the source's box. */
+#define DEXSIM_STATE_VERSION 1
+
+/* Layout of one state record for this configuration: name, rows (= words), is_int and the word offset inside the record of
+ * every section, in record order; the arena sections carry the arena field's name, the API sections "api.<tensor>"
+ * (64-bit tensors as two int32 words lo/hi per element, reset_buf as one word, the mask column packed four bytes per word).
+ * Slot s of a bank keeps word w of a section at bank[(offset + w) * pad64(capacity) + s]; the one quad-layout section,
+ * wlam, keeps word 4 q + c at bank[offset * pad64(capacity) + (q * pad64(capacity) + s) * 4 + c], like the arena.
+ * Needs no device.  DEXSIM_ERR_LAYOUT when the table is too small (fields == NULL just counts). */
+int dexsim_state_layout(const DexSimConfig* cfg, DexSimField* fields, int max_fields, int* n_fields, size_t* record_words);
+
+/* Save the records of k envs into bank slots / load them back.  env_ids and slots are device arrays of k int64, ids in
+ * [0, num_envs), slots in [0, capacity); a lane whose id or slot is out of range moves nothing.  For a load, env_ids must
+ * not repeat.  env_ids == NULL together with slots == NULL is the identity over ALL NS = pad64(num_envs) lanes (k is
+ * not used but must not be negative): the arena records of the padded lanes are included, because they take part in their workgroup's decisions; it
+ * needs capacity >= NS.  Stream-ordered, no synchronisation, no allocation. */
+int dexsim_save_state(dexsim_t h, const int64_t* env_ids, const int64_t* slots, int k, void* bank, int64_t capacity, void* stream);
+int dexsim_load_state(dexsim_t h, const int64_t* env_ids, const int64_t* slots, int k, const void* bank, int64_t capacity, void* stream);
+
+/* Fork inside one instance: record of env src_ids[i] -> env dst_ids[i], i < k (device arrays of int64 in [0, num_envs)).
+ * A source may repeat.  PRECONDITION (not checked here): the destinations are unique and none of them is also a source. */
+int dexsim_copy_envs(dexsim_t h, const int64_t* src_ids, const int64_t* dst_ids, int k, void* stream);
+
+/* The step stamp: the only host-side simulation state.  Its parity selects the contact-statistics words of the counters
+ * block and its value is the device-side reset gate.  Host-only calls: no launch, no synchronisation.  Valid stamps are
+ * [1, 0x3ffffffe]. */
+int dexsim_get_step_stamp(dexsim_t h, int* stamp);
+int dexsim_set_step_stamp(dexsim_t h, int stamp);
+
 const char* dexsim_error_string(int code);
 const char* dexsim_last_error(void);
 
