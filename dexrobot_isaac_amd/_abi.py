@@ -33,6 +33,18 @@ SUCCESS_CRITERIA = ["grasp_lift_success"]
 FAILURE_CRITERIA = ["hitting_ground", "box_too_far", "stage1_pregrasp_failed",
                     "stage2_contact_failed", "stage3_grasp_lost"]
 
+# camera sensors (include/dexsim.h: pixel model, scene record)
+SEG_NONE, SEG_GROUND, SEG_BOX, SEG_CAPSULE0 = 0, 1, 2, 3
+RENDER_AMBIENT = 0.35
+RENDER_LIGHT = (2.0 / 7.0, 3.0 / 7.0, 6.0 / 7.0)          # unit vector towards the light, world frame
+RENDER_PALETTE = ((150, 150, 140), (215, 150, 60), (200, 200, 210), (230, 80, 70), (80, 180, 90),
+                  (70, 120, 230), (220, 200, 70), (180, 90, 200))   # ground, box, palm, finger 0..4
+RENDER_BACKGROUND = (135, 170, 215)
+RENDER_MAX_DIM = 4096
+RCAP = dict(A=0, R=3, B=4, LEN=7, U=8, UO=11, O=12, INVR=15, N=16, CA=19, CB=20, LO=21, LU=22, R2=23)
+RCAP_WORDS = 24
+SCENE_WORDS = 52 + NCAP * RCAP_WORDS
+
 f32, i32, u32 = C.c_float, C.c_int, C.c_uint32
 
 
@@ -107,6 +119,11 @@ class DexSimBuffers(C.Structure):
     ]
 
 
+class DexSimCamera(C.Structure):
+    _fields_ = [("width", i32), ("height", i32), ("hfov_deg", f32), ("near_clip", f32), ("far_clip", f32),
+                ("parent_joint", i32), ("eye", f32 * 3), ("target", f32 * 3)]
+
+
 # every symbol include/dexsim.h declares (checked by tests/test_abi.py against the built library)
 EXPORTED_SYMBOLS = [
     "dexsim_struct_sizes", "dexsim_arena_layout", "dexsim_obs_key_info", "dexsim_reward_term_name",
@@ -117,6 +134,7 @@ EXPORTED_SYMBOLS = [
     "dexsim_last_error",
     "dexsim_state_layout", "dexsim_save_state", "dexsim_load_state", "dexsim_copy_envs", "dexsim_get_step_stamp",
     "dexsim_set_step_stamp",
+    "dexsim_camera_struct_size", "dexsim_render_layout", "dexsim_render",
 ]
 
 
@@ -157,6 +175,9 @@ def declare_prototypes(lib):
     lib.dexsim_copy_envs.argtypes = [vp, vp, vp, i32, vp]
     lib.dexsim_get_step_stamp.argtypes = [vp, P(i32)]
     lib.dexsim_set_step_stamp.argtypes = [vp, i32]
+    lib.dexsim_camera_struct_size.argtypes = [P(sz)]
+    lib.dexsim_render_layout.argtypes = [P(DexSimField), i32, P(i32), P(sz)]
+    lib.dexsim_render.argtypes = [vp, P(DexSimCamera), vp, vp, vp, i32, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = i32
     lib.dexsim_error_string.argtypes = [i32]
@@ -172,3 +193,7 @@ def check_struct_sizes(lib):
     mine = [C.sizeof(DexHandModel), C.sizeof(DexSimConfig), C.sizeof(DexSimField), C.sizeof(DexSimBuffers)]
     if list(out) != mine:
         raise RuntimeError(f"dexsim ABI mismatch: library struct sizes {list(out)} != python mirrors {mine}")
+    cam = C.c_size_t(0)
+    lib.dexsim_camera_struct_size(C.byref(cam))
+    if cam.value != C.sizeof(DexSimCamera):
+        raise RuntimeError(f"dexsim ABI mismatch: DexSimCamera is {cam.value} bytes in the library, {C.sizeof(DexSimCamera)} in python")

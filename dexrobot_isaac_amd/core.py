@@ -319,3 +319,45 @@ class DexSimCore:
 
     def set_step_stamp(self, stamp):
         check(self.lib.dexsim_set_step_stamp(self.h, int(stamp)), "set_step_stamp")
+
+    # ------------------------------------------------------------------ camera sensors (dexsim_render)
+    def render_layout(self):
+        """({section name: (word offset inside a scene record, words, is_int)}, scene_words) -- dexsim_render_layout."""
+        if getattr(self, "_render_layout", None) is None:
+            fields = (_abi.DexSimField * 32)()
+            nf, words = C.c_int(0), C.c_size_t(0)
+            check(self.lib.dexsim_render_layout(fields, 32, C.byref(nf), C.byref(words)), "render_layout")
+            self._render_layout = ({fields[i].name.decode(): (int(fields[i].offset), int(fields[i].rows), bool(fields[i].is_int))
+                                    for i in range(nf.value)}, int(words.value))
+        return self._render_layout
+
+    def render(self, cam, scene, depth=None, rgba=None, seg=None, env_ids=None, eye=None, target=None):
+        """Render `cam` (an _abi.DexSimCamera) for the envs `env_ids` (None = all) into the caller's tensors: scene
+        (k, scene_words) f32 workspace, depth (k, H, W) f32, rgba (k, H, W, 4) u8, seg (k, H, W) i32 (any output may be None, not
+        all); eye / target: optional (k, 3) f32 per-env overrides of the camera's look-at pair.  All on this device, contiguous."""
+        _, words = self.render_layout()
+        H, W = int(cam.height), int(cam.width)
+        ids = None
+        k = self.N
+        if env_ids is not None:
+            ids = torch.as_tensor(env_ids, device=self.device).to(torch.int64).contiguous().view(-1)
+            k = int(ids.numel())
+
+        def ptr(t, name, dtype, shape, optional=True):
+            if t is None:
+                if optional:
+                    return None
+                raise DexSimError(f"render: {name} is required")
+            if t.device != self.device or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise DexSimError(f"render: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}, "
+                                  f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+            return C.c_void_p(t.data_ptr())
+        if depth is None and rgba is None and seg is None:
+            raise DexSimError("render: at least one of depth, rgba and seg is required")
+        args = (ptr(eye, "eye", torch.float32, (k, 3)), ptr(target, "target", torch.float32, (k, 3)),
+                None if ids is None else C.c_void_p(ids.data_ptr()), k,
+                ptr(scene, "scene", torch.float32, (k, words), optional=False),
+                ptr(depth, "depth", torch.float32, (k, H, W)), ptr(rgba, "rgba", torch.uint8, (k, H, W, 4)),
+                ptr(seg, "seg", torch.int32, (k, H, W)))
+        self._keep_render = (ids, eye, target)     # alive until the kernels ran
+        check(self.lib.dexsim_render(self.h, C.byref(cam), *args, self._stream()), "render")

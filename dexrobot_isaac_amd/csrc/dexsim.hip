@@ -750,3 +750,69 @@ extern "C" int dexsim_set_step_stamp(dexsim_t h, int stamp) {
   h->api.stamp = stamp;
   return DEXSIM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------- camera sensors
+// Templates instantiated here, behind every use of the step kernels, so that the code object keeps the step path's kernels where
+// they were (like the state kernels above).
+// clang-format off
+#include "dexsim_render.hip.inc"
+// clang-format on
+
+extern "C" int dexsim_camera_struct_size(size_t* out) {
+  if (!out) return fail(DEXSIM_ERR_ARG, "dexsim_camera_struct_size: null argument");
+  *out = sizeof(DexSimCamera);
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_render_layout(DexSimField* fields, int max_fields, int* n_fields, size_t* scene_words) {
+  if (!n_fields || !scene_words) return fail(DEXSIM_ERR_ARG, "dexsim_render_layout: bad argument");
+  int n = 0, end = 0;
+  for (const RenderSection& s : kRenderSections) {
+    if (fields) {
+      if (n >= max_fields) return fail(DEXSIM_ERR_LAYOUT, "field table too small");
+      std::snprintf(fields[n].name, sizeof fields[n].name, "%s", s.name);
+      fields[n].rows = s.words; fields[n].is_int = s.is_int; fields[n].offset = (size_t)s.off;
+    }
+    end = s.off + s.words;
+    n++;
+  }
+  *n_fields = n;
+  *scene_words = (size_t)end;
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_render(dexsim_t h, const DexSimCamera* cam, const float* eye, const float* target, const int64_t* env_ids, int k,
+                             float* scene, float* depth, uint8_t* rgba, int32_t* seg, void* stream) {
+  if (!h || !h->bound) return fail(DEXSIM_ERR_ARG, "dexsim_render: null or unbound handle");
+  if (!cam || !scene) return fail(DEXSIM_ERR_ARG, "dexsim_render: camera and scene workspace are required");
+  if (!depth && !rgba && !seg) return fail(DEXSIM_ERR_ARG, "dexsim_render: at least one of depth, rgba and seg is required");
+  if (((uintptr_t)scene & 15) != 0 || ((uintptr_t)rgba & 3) != 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_render: the scene workspace must be 16-byte aligned, rgba 4-byte aligned");
+  if (cam->width < 1 || cam->width > DEXSIM_RENDER_MAX_DIM || cam->height < 1 || cam->height > DEXSIM_RENDER_MAX_DIM)
+    return fail(DEXSIM_ERR_ARG, "dexsim_render: width and height must be in [1, 4096]");
+  if (!(cam->hfov_deg > 0.f && cam->hfov_deg < 180.f)) return fail(DEXSIM_ERR_ARG, "dexsim_render: hfov_deg must be in (0, 180)");
+  if (!(cam->near_clip < cam->far_clip)) return fail(DEXSIM_ERR_ARG, "dexsim_render: near_clip must be below far_clip");
+  if (cam->parent_joint < -1 || cam->parent_joint >= DEXSIM_NJ) return fail(DEXSIM_ERR_ARG, "dexsim_render: parent_joint out of range");
+  if (!env_ids) k = h->N;
+  if (k < 0) return fail(DEXSIM_ERR_ARG, "dexsim_render: k must not be negative");
+  const long long npix = (long long)cam->width * cam->height;
+  if ((long long)k * npix >= (1ll << 31)) return fail(DEXSIM_ERR_ARG, "dexsim_render: k * width * height must stay below 2^31");
+  if (k == 0) return DEXSIM_OK;
+  DeviceGuard guard(h->device);
+  RenderArgs R;
+  R.cam = *cam; R.eye = eye; R.target = target; R.env_ids = env_ids; R.k = k; R.img0 = 0;
+  const double t = std::tan(0.5 * (double)cam->hfov_deg * 3.14159265358979323846 / 180.0);
+  R.tan_x = (float)t; R.tan_y = (float)(t * (double)cam->height / (double)cam->width);
+  auto* ks = cam->parent_joint >= 0 ? k_render_scene<true> : k_render_scene<false>;
+  auto* kr = h->cfg.has_box ? k_render_rays<true> : k_render_rays<false>;
+  ks<<<dim3((k + 63) / 64), dim3(64), 0, (hipStream_t)stream>>>(h->d_params, R, scene, h->NS, h->N);
+  LAUNCH_CHECK();
+  const RayOut O{depth, (unsigned*)rgba, (int*)seg};
+  const int ymax = 32768;   // images per launch (extent of the grid's y dimension)
+  for (int i0 = 0; i0 < k; i0 += ymax) {
+    R.img0 = i0;
+    kr<<<dim3((unsigned)((npix + 255) / 256), (unsigned)std::min(ymax, k - i0)), dim3(256), 0, (hipStream_t)stream>>>(scene, R, O, h->N);
+    LAUNCH_CHECK();
+  }
+  return DEXSIM_OK;
+}

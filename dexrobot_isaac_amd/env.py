@@ -405,6 +405,14 @@ class DexHandEnv:
         core.physics_step()
         core.reset_idx(torch.arange(self.num_envs, device=self.device))
         self._apply_pre_action_rule()
+        # camera sensors (GraphicsManager.create_camera, graphics_manager.py:56-179).  A video_config with a `resolution`
+        # creates the reference's fixed "video" camera, placed as VideoManager._position_camera places it
+        # (video_manager.py:100-147): 75 deg, behind env 0, looking at the hand.
+        self._cameras = {}
+        if video_config and video_config.get("resolution") is not None:
+            w, h = (int(v) for v in video_config["resolution"])
+            back = max(1.5, 0.75 * float(self.env_cfg["envSpacing"]))
+            self.create_camera("video", w, h, hfov_deg=75.0, eye=(-back, 0.0, 0.5), target=(0.0, 0.0, 0.15))
         self._initialization_complete = True
 
     # ------------------------------------------------------------------ construction helpers
@@ -701,8 +709,101 @@ class DexHandEnv:
                 raise DexSimError("fork_envs: a destination env is also a source")
         core.copy_envs(src, dst)
 
+    # ------------------------------------------------------------------ camera sensors (dexsim_render)
+    def _render_core(self, what):
+        core = self._core
+        if not hasattr(core, "render"):
+            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no render()")
+        return core
+
+    def _camera(self, name):
+        if name not in self._cameras:
+            raise KeyError(f"no camera named '{name}' (cameras: {sorted(self._cameras)})")
+        return self._cameras[name]
+
+    def create_camera(self, name, width, height, hfov_deg=75.0, eye=(-1.5, 0.0, 0.5), target=(0.0, 0.0, 0.15), parent=None,
+                      near=0.01, far=10.0):
+        """A camera sensor for every env (GraphicsManager.create_camera, graphics_manager.py:56-100).  eye / target: the look-at
+        pair in the parent frame, shared 3-vectors or (N, 3) tensors; parent: None = each env's world frame, or a joint index /
+        DOF name to mount the camera on that joint's frame (e.g. 5 or "ARRz": eye-in-hand on the palm joint), up = the parent's +z.
+        near / far: clip distances along the optical axis in metres."""
+        core = self._render_core("create_camera")
+        if name in self._cameras:
+            raise ValueError(f"camera '{name}' already exists")
+        if parent is None:
+            pj = -1
+        elif isinstance(parent, str):
+            if parent not in self.model.dof_names:
+                raise ValueError(f"create_camera: unknown joint '{parent}' (joints: {self.model.dof_names})")
+            pj = self.model.dof_names.index(parent)
+        else:
+            pj = int(parent)
+        if not -1 <= pj < _abi.NJ:
+            raise ValueError(f"create_camera: parent joint index must be in [0, {_abi.NJ}), got {parent}")
+        width, height = int(width), int(height)
+        if not (1 <= width <= _abi.RENDER_MAX_DIM and 1 <= height <= _abi.RENDER_MAX_DIM):
+            raise ValueError(f"create_camera: width and height must be in [1, {_abi.RENDER_MAX_DIM}], got {width} x {height}")
+        if not 0.0 < float(hfov_deg) < 180.0:
+            raise ValueError(f"create_camera: hfov_deg must be in (0, 180), got {hfov_deg}")
+        if not float(near) < float(far):
+            raise ValueError(f"create_camera: near ({near}) must be below far ({far})")
+        cam = _abi.DexSimCamera()
+        cam.width, cam.height, cam.hfov_deg = width, height, float(hfov_deg)
+        cam.near_clip, cam.far_clip, cam.parent_joint = float(near), float(far), pj
+        core.render_layout()
+        self._cameras[name] = {"cam": cam, "eye": None, "target": None, "buffers": {}}
+        self.set_camera_location(name, eye, target)
+        return name
+
+    def set_camera_location(self, name, eye, target):
+        """GraphicsManager.set_camera_location (graphics_manager.py:102-134): eye and target in the camera's parent frame, each a
+        shared 3-vector or an (N, 3) tensor with one row per env."""
+        c = self._camera(name)
+        for key, val in (("eye", eye), ("target", target)):
+            t = torch.as_tensor(val, dtype=torch.float32)
+            if tuple(t.shape) == (3,):
+                for i in range(3):
+                    getattr(c["cam"], key)[i] = float(t[i])
+                c[key] = None
+            elif tuple(t.shape) == (self.num_envs, 3):
+                c[key] = t.to(self._core.device).contiguous()
+            else:
+                raise ValueError(f"set_camera_location: {key} must have shape (3,) or ({self.num_envs}, 3), got {tuple(t.shape)}")
+
+    def render_camera(self, name, env_ids=None, outputs=("rgba", "depth", "seg")):
+        """GraphicsManager.render_all_cameras + capture_frame (graphics_manager.py:136-179) for one camera: a dict of device
+        tensors -- "rgba" (k, H, W, 4) uint8, "depth" (k, H, W) float32 (+inf without a hit), "seg" (k, H, W) int32 -- for the
+        envs `env_ids` (None = all, k = num_envs).  The tensors belong to the camera: they are allocated once per k and
+        overwritten by the next render_camera of the same camera and k."""
+        core = self._render_core("render_camera")
+        c = self._camera(name)
+        outputs = tuple(outputs)
+        if not outputs or any(o not in ("rgba", "depth", "seg") for o in outputs):
+            raise ValueError(f"render_camera: outputs must be a non-empty subset of ('rgba', 'depth', 'seg'), got {outputs}")
+        ids = None if env_ids is None else torch.as_tensor(env_ids, device=core.device).to(torch.int64).view(-1)
+        k = self.num_envs if ids is None else int(ids.numel())
+        cam, dev = c["cam"], core.device
+        H, W = int(cam.height), int(cam.width)
+        buf = c["buffers"].setdefault(k, {})
+        if "scene" not in buf:
+            buf["scene"] = torch.zeros(k, core.render_layout()[1], dtype=torch.float32, device=dev)
+        shapes = {"rgba": ((k, H, W, 4), torch.uint8), "depth": ((k, H, W), torch.float32), "seg": ((k, H, W), torch.int32)}
+        for o in outputs:
+            if o not in buf:
+                buf[o] = torch.zeros(shapes[o][0], dtype=shapes[o][1], device=dev)
+        if k == 0:
+            return {o: buf[o] for o in outputs}
+        pick = lambda t: None if t is None else (t if ids is None else t[ids].contiguous())
+        core.render(cam, buf["scene"], env_ids=ids, eye=pick(c["eye"]), target=pick(c["target"]),
+                    **{o: buf[o] for o in outputs})
+        return {o: buf[o] for o in outputs}
+
     def render(self, mode="rgb_array"):
-        return None                                              # headless: no viewer / recorder / streamer
+        """env 0's (H, W, 3) uint8 frame of the camera named "video" (created by a video_config with a `resolution`, or by
+        create_camera("video", ...)); None without one -- headless: no viewer / recorder / streamer."""
+        if "video" not in getattr(self, "_cameras", {}):
+            return None
+        return self.render_camera("video", [0], ("rgba",))["rgba"][0, :, :, :3].cpu().numpy()
 
     def close(self):
         if self._core is not None:

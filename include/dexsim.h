@@ -484,6 +484,99 @@ int dexsim_copy_envs(dexsim_t h, const int64_t* src_ids, const int64_t* dst_ids,
 int dexsim_get_step_stamp(dexsim_t h, int* stamp);
 int dexsim_set_step_stamp(dexsim_t h, int stamp);
 
+/* ------------------------------------------------------------------ camera sensors: depth, segmentation and colour images
+ * Replaces the reference's graphics layer for sensors: GraphicsManager.create_camera / set_camera_location /
+ * render_all_cameras / capture_frame (graphics_manager.py:56-179) and the fixed "video camera" of VideoManager
+ * (video_manager.py:56-147: 75 deg horizontal FOV, behind env 0, looking at the hand).  No encoder, viewer or stream: a recorder
+ * is a caller-side loop over frames.
+ *
+ * Everything the engine collides is analytic -- DEXSIM_NCAP capsules welded to joint frames, one cube, the ground plane z = 0 --
+ * so a camera is an exact ray-caster over those primitives.  Rendering is a pure function of the persistent state (arena fields q,
+ * box_pos, box_quat): it changes no arena word, no API tensor, no statistics or counters word and not the step stamp.
+ *
+ * PIXEL MODEL.  Pinhole camera.  Pixel (x, y), x to the right, y downwards, row-major; its ray leaves the eye through the pixel
+ * centre: d = normalize(forward + sx right + sy up), sx = (2 (x + 0.5) / W - 1) tan(hfov / 2),
+ * sy = (1 - 2 (y + 0.5) / H) tan(hfov / 2) H / W (the vertical extent follows from the aspect ratio).
+ * Every primitive contributes the point where the ray ENTERS it (a camera inside a primitive does not see it; the ground is hit from
+ * either side); a hit's depth is its distance along the optical axis, t (d . forward).  Hits with depth outside
+ * [near_clip, far_clip] are dropped; the nearest remaining hit wins.
+ *   depth  f32: that depth, or +inf without a hit
+ *   seg    i32: DEXSIM_SEG_NONE without a hit, DEXSIM_SEG_GROUND, DEXSIM_SEG_BOX, DEXSIM_SEG_CAPSULE0 + c for capsule c in
+ *          DexHandModel order (cap_fslot maps a capsule to its finger link or the palm)
+ *   rgba   4 x u8: alpha 255; channel = round(palette[p][channel] * (ambient + (1 - ambient) * max(0, n . l))), n the outward
+ *          surface normal at the hit, l the unit vector towards the one directional light; palette entry p: 0 ground, 1 box, 2 palm,
+ *          3 + f finger f (= cap_fslot / 3).  No hit: the background colour.  No shadows, no textures. */
+#define DEXSIM_SEG_NONE     0
+#define DEXSIM_SEG_GROUND   1
+#define DEXSIM_SEG_BOX      2
+#define DEXSIM_SEG_CAPSULE0 3
+#define DEXSIM_RENDER_AMBIENT 0.35f
+#define DEXSIM_RENDER_LIGHT { 2.0f / 7.0f, 3.0f / 7.0f, 6.0f / 7.0f }   /* unit vector towards the light, world frame */
+#define DEXSIM_RENDER_NPALETTE 8
+#define DEXSIM_RENDER_PALETTE { {150, 150, 140}, {215, 150, 60}, {200, 200, 210}, {230, 80, 70}, {80, 180, 90}, \
+                                {70, 120, 230}, {220, 200, 70}, {180, 90, 200} }   /* 8-bit R, G, B */
+#define DEXSIM_RENDER_BACKGROUND { 135, 170, 215 }
+#define DEXSIM_RENDER_MAX_DIM 4096
+
+/* A camera.  The look-at pair is given in the PARENT frame: parent_joint = -1 is the env's world frame, 0 .. DEXSIM_NJ - 1 mounts
+ * the camera on that joint's frame (5 = the palm joint: an eye-in-hand camera).  Up is the parent's +z axis; when the sine of the
+ * angle between the view direction and that axis is below 1e-6 the parent's +y axis takes its place (and a zero-length view
+ * direction becomes the parent's +x), so the resolved frame never holds a NaN. */
+typedef struct DexSimCamera {
+  int   width, height;           /* [1, DEXSIM_RENDER_MAX_DIM] */
+  float hfov_deg;                /* horizontal field of view, (0, 180); the reference's video camera uses 75 */
+  float near_clip, far_clip;     /* metres along the optical axis, near_clip < far_clip */
+  int   parent_joint;
+  float eye[3], target[3];       /* shared by all rendered envs unless dexsim_render gets per-env arrays */
+} DexSimCamera;
+
+/* sizeof(DexSimCamera), for bindings to verify their mirror (dexsim_struct_sizes keeps its four entries). */
+int dexsim_camera_struct_size(size_t* out);
+
+/* The SCENE RECORD of one rendered env is the world-space geometry the ray kernel consumes: DEXSIM_SCENE_WORDS 4-byte words, one
+ * contiguous record per rendered env (AoS: all pixels of an image share one record and fetch it through the scalar cache).
+ * Sections, in record order (dexsim_render_layout reports name, words, is_int and word offset of each):
+ *   cam_eye 3, cam_right 3, cam_up 3, cam_forward 3   the resolved camera: eye and the orthonormal frame, world coordinates
+ *   box_center 3, box_rot 9, box_half 1               rotation row-major, world <- box; box_half = half edge, 0 = "no box"
+ *   box_eye 3, box_light 3                            eye relative to the centre and the light direction, in box coordinates
+ *   cap_rgb DEXSIM_NCAP (int)                         palette colour of each capsule, R | G << 8 | B << 16
+ *   reserved 3
+ *   capsules DEXSIM_NCAP x DEXSIM_RCAP_WORDS          per capsule, word offsets DEXSIM_RCAP_*: endpoints a, b, radius, and what
+ *                                                     is the same for every ray of the image (u = unit axis, o = eye - a) */
+#define DEXSIM_RCAP_A      0   /* [3] endpoint a (cap_p0), world                 */
+#define DEXSIM_RCAP_R      3   /* radius                                         */
+#define DEXSIM_RCAP_B      4   /* [3] endpoint b (cap_p1), world                 */
+#define DEXSIM_RCAP_LEN    7   /* |b - a|                                        */
+#define DEXSIM_RCAP_U      8   /* [3] u = (b - a) / |b - a|                      */
+#define DEXSIM_RCAP_UO    11   /* u . o                                          */
+#define DEXSIM_RCAP_O     12   /* [3] o = eye - a                                */
+#define DEXSIM_RCAP_INVR  15   /* 1 / radius                                     */
+#define DEXSIM_RCAP_N     16   /* [3] u x o                                      */
+#define DEXSIM_RCAP_CA    19   /* |eye - a|^2 - r^2                              */
+#define DEXSIM_RCAP_CB    20   /* |eye - b|^2 - r^2                              */
+#define DEXSIM_RCAP_LO    21   /* light . o                                      */
+#define DEXSIM_RCAP_LU    22   /* light . u                                      */
+#define DEXSIM_RCAP_R2    23   /* r^2                                            */
+#define DEXSIM_RCAP_WORDS 24
+#define DEXSIM_SCENE_WORDS (52 + DEXSIM_NCAP * DEXSIM_RCAP_WORDS)
+
+/* Layout of one scene record (DexSimField convention: rows = words of the section, offset in words inside the record).  Needs no
+ * device.  DEXSIM_ERR_LAYOUT when the table is too small (fields == NULL just counts). */
+int dexsim_render_layout(DexSimField* fields, int max_fields, int* n_fields, size_t* scene_words);
+
+/* Render camera `cam` for k envs: GraphicsManager.render_all_cameras + capture_frame (graphics_manager.py:56-179).
+ *   eye, target  optional device (k, 3) f32 arrays overriding cam->eye / cam->target per rendered env (per-env placement,
+ *                camera randomisation); NULL = the shared pair
+ *   env_ids      device array of k int64; NULL = all num_envs envs in order (k is then not used), as in dexsim_save_state.  A lane
+ *                whose id is outside [0, num_envs) renders nothing: its record and its images are left as they are
+ *   scene        caller workspace of k x DEXSIM_SCENE_WORDS floats, 16-byte aligned; it holds the scene records afterwards
+ *   depth (k, H, W) f32, rgba (k, H, W, 4) u8 (4-byte aligned), seg (k, H, W) i32: any may be NULL, not all three
+ * Two launches (scene records: one lane per env; rays: one lane per pixel), stream-ordered, no allocation, no synchronisation.
+ * DEXSIM_ERR_ARG for a NULL or unbound handle, width or height outside [1, DEXSIM_RENDER_MAX_DIM], k * width * height >= 2^31,
+ * hfov_deg outside (0, 180), near_clip >= far_clip, parent_joint outside [-1, DEXSIM_NJ), k < 0, a NULL scene or no output. */
+int dexsim_render(dexsim_t h, const DexSimCamera* cam, const float* eye, const float* target, const int64_t* env_ids, int k,
+                  float* scene, float* depth, uint8_t* rgba, int32_t* seg, void* stream);
+
 const char* dexsim_error_string(int code);
 const char* dexsim_last_error(void);
 

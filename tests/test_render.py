@@ -1,0 +1,454 @@
+"""Camera sensors (dexsim_render: depth, segmentation and colour by exact ray casting) against tests/render_ref.py.
+
+Rules of every pixel comparison:
+  * pixels the reference marks unstable (render_ref: id changes under +-0.2 mm inflation, box edges, clip planes, horizon) are
+    left out; at most 3 % of any compared image may be unstable -- asserted on the reference alone, before GPU output is read;
+  * segmentation: exact;
+  * depth, where both sides hit: ten times the error the SAME reference makes when evaluated in float32 instead of float64 on
+    the same inputs (computed here, on the CPU, never from the code under test) -- absolute on hand and box hits, relative on the
+    ground.  The factor ten covers another operation order, contracted FMAs and the 2.5-ulp divide / sqrt of the GPU build.
+    Measured float32 error of the reference on the 70 poses of the first test at 64 x 48 (213 366 stable pixels, 0 id
+    mismatches): 6.45e-6 m on hand and box hits, 5.1e-7 relative on the ground; the tolerances there are therefore 6.4e-5 m
+    and 5.1e-6, below the 0.2 mm stability margin (every test derives its own pair from its own images and prints it);
+  * rgba: +-2 levels per channel (one rounding step on each side plus the 2.5-ulp arithmetic);
+  * scene records against the reference's FK: atol 1e-5 m (fp32 epsilon x 0.6 m x ~30 chained operations ~ 1e-6, 10 x margin).
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from dexrobot_isaac_amd import _abi, _lib
+from dexrobot_isaac_amd.build import build_lib
+from dexrobot_isaac_amd.config import build_sim_config, default_cfg
+from tests import render_ref as rr
+
+MAX_UNSTABLE = 0.03
+
+
+# ------------------------------------------------------------------------------------------------- CPU
+@pytest.fixture(scope="module")
+def lib():
+    build_lib()
+    return _lib.load()
+
+
+def test_render_layout_tiles_the_record(lib):
+    fields = (_abi.DexSimField * 32)()
+    nf, words = C.c_int(), C.c_size_t()
+    assert lib.dexsim_render_layout(fields, 32, C.byref(nf), C.byref(words)) == 0      # no device needed
+    assert words.value == _abi.SCENE_WORDS
+    off = 0
+    names = []
+    for i in range(nf.value):
+        assert fields[i].offset == off and fields[i].rows > 0
+        off += fields[i].rows
+        names.append(fields[i].name.decode())
+    assert off == words.value and len(set(names)) == len(names)
+    assert {"cam_eye", "cam_right", "cam_up", "cam_forward", "box_center", "box_rot", "box_half", "capsules"} <= set(names)
+    caps = fields[names.index("capsules")]
+    assert caps.rows == _abi.NCAP * _abi.RCAP_WORDS
+    n2 = C.c_int()
+    assert lib.dexsim_render_layout(None, 0, C.byref(n2), C.byref(words)) == 0 and n2.value == nf.value   # NULL just counts
+    assert lib.dexsim_render_layout(fields, 3, C.byref(nf), C.byref(words)) == 5        # DEXSIM_ERR_LAYOUT
+
+
+def test_camera_struct_size_and_null_handle(lib):
+    sz = C.c_size_t()
+    assert lib.dexsim_camera_struct_size(C.byref(sz)) == 0 and sz.value == C.sizeof(_abi.DexSimCamera)
+    cam = _abi.DexSimCamera()
+    cam.width, cam.height, cam.hfov_deg, cam.near_clip, cam.far_clip, cam.parent_joint = 8, 8, 75.0, 0.01, 10.0, -1
+    assert lib.dexsim_render(None, C.byref(cam), None, None, None, 0, None, None, None, None, None) == 1   # DEXSIM_ERR_ARG
+
+
+class _OneCapsule:
+    """render_ref.render over a single free-standing capsule (all 18 coincide)."""
+    cap_r = np.full(_abi.NCAP, 0.01)
+
+    def __init__(self, a, b):
+        self.a, self.b = np.tile(a, (_abi.NCAP, 1)).astype(float), np.tile(b, (_abi.NCAP, 1)).astype(float)
+
+    def capsules(self, q, dtype=np.float64):
+        return self.a.astype(dtype), self.b.astype(dtype), None
+
+    def palette_index(self, c):
+        return 2
+
+
+def test_reference_closed_forms():
+    W = H = 5                                                     # odd: pixel (2, 2) looks along the optical axis
+    # a capsule seen end-on: centre depth = distance to the near endpoint - r
+    g = _OneCapsule(np.array([0.5, 0.0, 1.0]), np.array([0.8, 0.0, 1.0]))
+    cam = rr.look_at([0.0, 0.0, 1.0], [1.0, 0.0, 1.0])
+    out = rr.render(g, None, None, cam, W, H, 40.0, 0.01, 10.0)
+    assert out["seg"][2, 2] == _abi.SEG_CAPSULE0 and abs(out["depth"][2, 2] - (0.5 - 0.01)) < 1e-12
+    assert out["seg"][0, 0] == _abi.SEG_NONE and np.isinf(out["depth"][0, 0])     # sky: the view is horizontal
+    assert tuple(out["rgba"][0, 0]) == _abi.RENDER_BACKGROUND + (255,)
+    # ... and from the side: depth = distance to the axis - r, normal towards the camera
+    cam = rr.look_at([0.65, -0.4, 1.0], [0.65, 0.0, 1.0])
+    out = rr.render(g, None, None, cam, W, H, 40.0, 0.01, 10.0)
+    assert abs(out["depth"][2, 2] - (0.4 - 0.01)) < 1e-12
+    shade = _abi.RENDER_AMBIENT + (1 - _abi.RENDER_AMBIENT) * max(0.0, -_abi.RENDER_LIGHT[1])
+    assert tuple(out["rgba"][2, 2][:3]) == tuple(int(math.floor(c * shade + 0.5)) for c in _abi.RENDER_PALETTE[2])
+    # an axis-aligned box face (the capsule is far behind the camera)
+    far_away = _OneCapsule(np.array([-50.0, 0.0, 1.0]), np.array([-51.0, 0.0, 1.0]))
+    box = (np.array([1.0, 0.0, 1.0]), np.array([0.0, 0.0, 0.0, 1.0]), 0.2)
+    cam = rr.look_at([0.0, 0.0, 1.0], [1.0, 0.0, 1.0])
+    out = rr.render(far_away, None, box, cam, W, H, 40.0, 0.01, 10.0)
+    assert out["seg"][2, 2] == _abi.SEG_BOX and abs(out["depth"][2, 2] - 0.9) < 1e-12
+    shade = _abi.RENDER_AMBIENT                                   # the face's normal is -x: it faces away from the light
+    assert tuple(out["rgba"][2, 2][:3]) == tuple(int(math.floor(c * shade + 0.5)) for c in _abi.RENDER_PALETTE[1])
+    # ground depth from height and pitch: the central ray hits at z0 / sin(pitch)
+    pitch, z0 = math.radians(35.0), 0.7
+    cam = rr.look_at([0.0, 0.0, z0], [math.cos(pitch), 0.0, z0 - math.sin(pitch)])
+    out = rr.render(far_away, None, None, cam, W, H, 40.0, 0.01, 10.0)
+    assert out["seg"][2, 2] == _abi.SEG_GROUND and abs(out["depth"][2, 2] - z0 / math.sin(pitch)) < 1e-12
+    # looking straight down: the up fall-back keeps the frame finite
+    cam = rr.look_at([0.0, 0.0, 1.0], [0.0, 0.0, 0.0])
+    assert np.isfinite(np.concatenate(cam)).all() and abs(rr.render(far_away, None, None, cam, W, H, 40.0, 0.01, 10.0)["depth"][2, 2] - 1.0) < 1e-12
+
+
+# ------------------------------------------------------------------------------------------------- poses of the GPU tests
+def make_poses(geom, n, box_size, seed):
+    """The recipe of the issue: hand lowered by q[2] = -0.2 (fingertips ~0.10 m above the ground), finger joints uniform over
+    their ranges, base rotations +-0.25 rad; box within +-3 cm of the capsule centroid, 0-3 cm above rest, random orientation;
+    camera 0.24 m from the centroid at a random azimuth, 0.12-0.22 m above it, looking 5 cm below it; every third view
+    horizontal (half the image is sky).  Everything is rounded to float32, which is what both sides are given."""
+    rng = np.random.default_rng(seed)
+    q = np.zeros((n, _abi.NJ))
+    q[:, 0:2] = rng.uniform(-0.02, 0.02, (n, 2))
+    q[:, 2] = -0.2
+    q[:, 3:6] = rng.uniform(-0.25, 0.25, (n, 3))
+    q[:, 6:] = rng.uniform(geom.lo[6:], geom.hi[6:], (n, 20))
+    q = q.astype(np.float32)
+    box_pos, box_quat, eye, target = (np.zeros((n, 3)), np.zeros((n, 4)), np.zeros((n, 3)), np.zeros((n, 3)))
+    for e in range(n):
+        a, b, _ = geom.capsules(q[e].astype(np.float64))
+        cen = (0.5 * (a + b)).mean(0)
+        box_pos[e] = [cen[0] + rng.uniform(-0.03, 0.03), cen[1] + rng.uniform(-0.03, 0.03), 0.5 * box_size + rng.uniform(0, 0.03)]
+        box_quat[e] = rr._unit(rng.normal(size=4))
+        az = rng.uniform(0, 2 * math.pi)
+        eye[e] = cen + [0.24 * math.cos(az), 0.24 * math.sin(az), rng.uniform(0.12, 0.22)]
+        target[e] = cen - [0, 0, 0.05]
+        if e % 3 == 2:
+            eye[e, 2] = cen[2] + rng.uniform(0.0, 0.05)
+            target[e] = [cen[0], cen[1], eye[e, 2]]
+    f32 = lambda x: x.astype(np.float32)
+    return q, f32(box_pos), f32(box_quat), f32(eye), f32(target)
+
+
+def pose_core(core, q, box_pos=None, box_quat=None):
+    """Pose every env through the API tensors and the indexed setters (as test_body_states_and_indexed_setters does)."""
+    import torch
+    ids = torch.arange(core.N)
+    core.dof_state[:, :, 0] = torch.as_tensor(q, device=core.device)
+    core.dof_state[:, :, 1] = 0.0
+    core.set_dof_state_indexed(ids)
+    if box_pos is not None:
+        core.root_state[:, 1, :] = 0.0
+        core.root_state[:, 1, 0:3] = torch.as_tensor(box_pos, device=core.device)
+        core.root_state[:, 1, 3:7] = torch.as_tensor(box_quat, device=core.device)
+        core.set_root_state_indexed(ids)
+    assert (core.field("q").t().cpu().numpy() == q).all()
+
+
+def make_camera(W, H, hfov=60.0, near=0.01, far=10.0, parent=-1, eye=(0, 0, 0), target=(1, 0, 0)):
+    cam = _abi.DexSimCamera()
+    cam.width, cam.height, cam.hfov_deg, cam.near_clip, cam.far_clip, cam.parent_joint = W, H, hfov, near, far, parent
+    for i in range(3):
+        cam.eye[i], cam.target[i] = float(eye[i]), float(target[i])
+    return cam
+
+
+def gpu_render(core, cam, env_ids=None, eye=None, target=None, outputs=("depth", "rgba", "seg"), guard=True):
+    """dexsim_render into fresh tensors.  With `guard`, every output has one extra image-sized guard block behind the last image,
+    filled with a sentinel that must come back untouched.  Returns numpy arrays (scene, depth, rgba, seg; None where not asked)."""
+    import torch
+    dev = core.device
+    k = core.N if env_ids is None else len(env_ids)
+    H, W = cam.height, cam.width
+    words = core.render_layout()[1]
+    scene = torch.zeros(k, words, device=dev)
+    spec = {"depth": ((H, W), torch.float32, -7.0), "rgba": ((H, W, 4), torch.uint8, 77), "seg": ((H, W), torch.int32, -7)}
+    full, views = {}, {}
+    for o in outputs:
+        shape, dtype, sentinel = spec[o]
+        full[o] = torch.full((k + 1,) + shape, sentinel, dtype=dtype, device=dev)
+        views[o] = full[o][:k]
+    t = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32, device=dev)
+    core.render(cam, scene, env_ids=env_ids, eye=t(eye), target=t(target), **views)
+    torch.cuda.synchronize()
+    for o in outputs:
+        assert (full[o][k] == spec[o][2]).all(), f"{o}: the guard block behind the last image was written"
+    res = {o: views[o].cpu().numpy() for o in outputs}
+    return scene.cpu().numpy(), res.get("depth"), res.get("rgba"), res.get("seg")
+
+
+def reference_images(geom, q, boxes, cams, W, H, hfov, near, far):
+    """render_ref images of every env + the shared float32-derived depth tolerances; asserts the unstable share per image."""
+    refs = [rr.render_with_stability(geom, q[e], boxes[e], cams[e], W, H, hfov, near, far) for e in range(len(q))]
+    for e, r in enumerate(refs):
+        share = r["unstable"].mean()
+        assert share <= MAX_UNSTABLE, f"env {e}: {share:.3%} of the reference image is unstable"
+    err_abs, err_rel, mism, cnt = 0.0, 0.0, 0, 0
+    for r in refs:
+        st = ~r["unstable"]
+        mism += int((r["seg32"][st] != r["seg"][st]).sum())
+        both = st & (r["seg32"] == r["seg"]) & (r["seg"] != _abi.SEG_NONE)
+        cnt += int(st.sum())
+        gnd = both & (r["seg"] == _abi.SEG_GROUND)
+        obj = both & (r["seg"] != _abi.SEG_GROUND)
+        d64, d32 = np.where(both, r["depth"], 0.0), np.where(both, r["depth32"].astype(np.float64), 0.0)
+        if obj.any():
+            err_abs = max(err_abs, float(np.abs(d32 - d64)[obj].max()))
+        if gnd.any():
+            err_rel = max(err_rel, float((np.abs(d32 - d64)[gnd] / d64[gnd]).max()))
+    print(f"reference in float32: {cnt} stable pixels, {mism} id mismatches, depth error {err_abs:.3g} m on hand/box hits, "
+          f"{err_rel:.3g} relative on the ground")
+    return refs, 10 * err_abs, 10 * err_rel
+
+
+def compare_images(refs, tol_abs, tol_rel, depth, rgba, seg, what=""):
+    for e, r in enumerate(refs):
+        st = ~r["unstable"]
+        bad = st & (seg[e] != r["seg"])
+        assert not bad.any(), f"{what} env {e}: {int(bad.sum())} stable pixels with a wrong id, first at {np.argwhere(bad)[0]}"
+        assert not np.isnan(depth[e]).any()
+        miss = st & (r["seg"] == _abi.SEG_NONE)
+        assert np.isposinf(depth[e][miss]).all()
+        hit = st & (r["seg"] != _abi.SEG_NONE)
+        gnd = hit & (r["seg"] == _abi.SEG_GROUND)
+        obj = hit & ~gnd
+        err = np.abs(np.where(hit, depth[e].astype(np.float64), 0.0) - np.where(hit, r["depth"], 0.0))
+        print(f"{what} env {e}: depth error {err[obj].max() if obj.any() else 0:.3g} m (hand/box), "
+              f"{(err[gnd] / r['depth'][gnd]).max() if gnd.any() else 0:.3g} relative (ground)")
+        assert (err[obj] <= tol_abs).all(), f"{what} env {e}: depth error {err[obj].max():.3g} m > {tol_abs:.3g} m"
+        assert (err[gnd] <= tol_rel * r["depth"][gnd]).all(), f"{what} env {e}: ground depth error {(err[gnd] / r['depth'][gnd]).max():.3g}"
+        dc = np.abs(rgba[e].astype(np.int32) - r["rgba"].astype(np.int32))[st]
+        assert dc.max() <= 2, f"{what} env {e}: colour off by {dc.max()} levels"
+        assert (rgba[e][..., 3] == 255).all()
+
+
+def compare_scene(core, scene, geom, q, boxes, cams):
+    lay = core.render_layout()[0]
+    sec = lambda n: scene[:, lay[n][0]: lay[n][0] + lay[n][1]]
+    caps = sec("capsules").reshape(len(q), _abi.NCAP, _abi.RCAP_WORDS)
+    R = _abi.RCAP
+    for e in range(len(q)):
+        a, b, _ = geom.capsules(q[e].astype(np.float64))
+        np.testing.assert_allclose(caps[e, :, R["A"]:R["A"] + 3], a, atol=1e-5)
+        np.testing.assert_allclose(caps[e, :, R["B"]:R["B"] + 3], b, atol=1e-5)
+        np.testing.assert_allclose(caps[e, :, R["R"]], geom.cap_r, atol=1e-7)
+        np.testing.assert_allclose(caps[e, :, R["LEN"]], np.linalg.norm(b - a, axis=1), atol=1e-5)
+        for n, v in zip(("cam_eye", "cam_right", "cam_up", "cam_forward"), cams[e]):
+            np.testing.assert_allclose(sec(n)[e], v, atol=1e-5)
+        if boxes[e] is not None:
+            np.testing.assert_allclose(sec("box_center")[e], boxes[e][0], atol=1e-5)
+            np.testing.assert_allclose(sec("box_rot")[e].reshape(3, 3), rr.quat_to_mat(boxes[e][1]), atol=1e-5)
+            np.testing.assert_allclose(sec("box_half")[e], 0.5 * boxes[e][2], atol=1e-7)
+        else:
+            assert sec("box_half")[e] == 0.0
+    rgb = [_abi.RENDER_PALETTE[geom.palette_index(c)] for c in range(_abi.NCAP)]
+    pal = np.array([r | g << 8 | b << 16 for r, g, b in rgb])
+    assert (sec("cap_rgb").view(np.int32) == pal[None, :]).all()
+
+
+# ------------------------------------------------------------------------------------------------- GPU
+N = 70            # two workgroups of the scene kernel, six padded lanes
+W1, H1 = 64, 48
+
+
+@pytest.fixture(scope="module")
+def posed():
+    """BlindGrasping, N = 70, every env in its own pose; the reference images at 64 x 48 are computed once."""
+    from dexrobot_isaac_amd.core import DexSimCore
+    cfg = default_cfg("BlindGrasping")
+    cfg["env"]["numEnvs"] = N
+    sc, model = build_sim_config(cfg)
+    ms = model.to_struct()
+    geom = rr.HandGeometry(ms)
+    core = DexSimCore(sc, ms, "cuda:0")
+    core.reset()
+    q, bp, bq, eye, target = make_poses(geom, N, float(sc.box_size), seed=11)
+    pose_core(core, q, bp, bq)
+    boxes = [(bp[e].astype(np.float64), bq[e].astype(np.float64), float(sc.box_size)) for e in range(N)]
+    cams = [rr.look_at(eye[e].astype(np.float64), target[e].astype(np.float64)) for e in range(N)]
+    return dict(core=core, geom=geom, q=q, boxes=boxes, cams=cams, eye=eye, target=target, sc=sc)
+
+
+@pytest.mark.gpu
+def test_scene_and_images_padded_lanes(posed):
+    p = posed
+    refs, tol_abs, tol_rel = reference_images(p["geom"], p["q"], p["boxes"], p["cams"], W1, H1, 60.0, 0.01, 10.0)
+    ids = np.unique(np.concatenate([r["seg"].ravel() for r in refs]))
+    assert len(ids) >= 20 and {_abi.SEG_NONE, _abi.SEG_GROUND, _abi.SEG_BOX} <= set(ids.tolist())   # the recipe covers the ids
+    scene, depth, rgba, seg = gpu_render(p["core"], make_camera(W1, H1), eye=p["eye"], target=p["target"])
+    compare_scene(p["core"], scene, p["geom"], p["q"], p["boxes"], p["cams"])
+    compare_images(refs, tol_abs, tol_rel, depth, rgba, seg, "64x48")
+
+
+@pytest.mark.gpu
+def test_partial_waves_and_subsets(posed):
+    p = posed
+    core = p["core"]
+    W, H = 50, 30                                                 # 1500 pixels: 23 full waves + 28 lanes, waves straddle rows
+    cam = make_camera(W, H)
+    _, d_all, c_all, s_all = gpu_render(core, cam, eye=p["eye"], target=p["target"])
+    sub = [1, 65, 69]
+    sc_sub, d, c, s = gpu_render(core, cam, env_ids=sub, eye=p["eye"][sub], target=p["target"][sub])
+    for i, e in enumerate(sub):                                   # image i == the all-env render's image env_ids[i], bit for bit
+        assert (d[i].view(np.int32) == d_all[e].view(np.int32)).all() and (c[i] == c_all[e]).all() and (s[i] == s_all[e]).all()
+    refs, tol_abs, tol_rel = reference_images(p["geom"], p["q"][sub], [p["boxes"][e] for e in sub], [p["cams"][e] for e in sub],
+                                              W, H, 60.0, 0.01, 10.0)
+    compare_scene(core, sc_sub, p["geom"], p["q"][sub], [p["boxes"][e] for e in sub], [p["cams"][e] for e in sub])
+    compare_images(refs, tol_abs, tol_rel, d, c, s, "50x30")
+    for skip in ("depth", "rgba", "seg"):                        # each single NULL output leaves the other two unchanged
+        outs = tuple(o for o in ("depth", "rgba", "seg") if o != skip)
+        _, d2, c2, s2 = gpu_render(core, cam, env_ids=sub, eye=p["eye"][sub], target=p["target"][sub], outputs=outs)
+        for got, want in ((d2, d), (c2, c), (s2, s)):
+            assert got is None or (got.view(np.uint8) == want.view(np.uint8)).all()
+    # a lane whose id is out of range renders nothing: its images keep the caller's bytes
+    _, d3, c3, s3 = gpu_render(core, cam, env_ids=[1, N, -1], eye=p["eye"][[1, 0, 0]], target=p["target"][[1, 0, 0]])
+    assert (d3[0].view(np.int32) == d_all[1].view(np.int32)).all() and (d3[1:] == -7.0).all() and (s3[1:] == -7).all() and (c3[1:] == 77).all()
+
+
+@pytest.mark.gpu
+def test_mounted_camera(posed):
+    p = posed
+    core, geom = p["core"], p["geom"]
+    le, lt = np.array([0.03, -0.16, 0.10], dtype=np.float32), np.array([-0.06, 0.0, -0.02], dtype=np.float32)   # palm joint frame
+    envs = list(range(0, N, 7))
+    cams = []
+    for e in envs:                                                # the world camera the reference's FK computes
+        o, R = geom.fk(p["q"][e].astype(np.float64))
+        cams.append(rr.look_at(le.astype(np.float64), lt.astype(np.float64), o[5], R[5]))
+    refs, tol_abs, tol_rel = reference_images(geom, p["q"][envs], [p["boxes"][e] for e in envs], cams, W1, H1, 60.0, 0.01, 10.0)
+    assert max((r["seg"] >= _abi.SEG_CAPSULE0).mean() for r in refs) > 0.05          # the hand is in view
+    scene, depth, rgba, seg = gpu_render(core, make_camera(W1, H1, parent=5, eye=le, target=lt), env_ids=envs)
+    compare_scene(core, scene, geom, p["q"][envs], [p["boxes"][e] for e in envs], cams)
+    compare_images(refs, tol_abs, tol_rel, depth, rgba, seg, "mounted")
+
+
+def _core(task, n, **over):
+    from dexrobot_isaac_amd.core import DexSimCore
+    cfg = default_cfg(task)
+    cfg["env"]["numEnvs"] = n
+    for k, v in over.items():
+        cfg["env"][k] = v
+    sc, model = build_sim_config(cfg)
+    ms = model.to_struct()
+    core = DexSimCore(sc, ms, "cuda:0")
+    core.reset()
+    return core, sc, rr.HandGeometry(ms)
+
+
+@pytest.mark.gpu
+def test_no_box_and_static_box():
+    n = 6
+    eye, target = np.array([0.05, 0.40, 0.35], dtype=np.float32), np.array([0.15, 0.0, 0.12], dtype=np.float32)
+    for task, over in (("BaseTask", {}), ("BaseTask", {"box": {"fixed": True}})):
+        core, sc, geom = _core(task, n, **over)
+        q = make_poses(geom, n, 0.1, seed=5)[0]
+        pose_core(core, q)
+        if over:
+            assert sc.has_box and sc.box_fixed
+            box = (np.array(list(sc.box_fixed_pos), dtype=np.float64), np.array([0.0, 0.0, 0.0, 1.0]), float(sc.box_size))
+        else:
+            assert not sc.has_box
+            box = None
+        cams = [rr.look_at(eye.astype(np.float64), target.astype(np.float64))] * n
+        refs, tol_abs, tol_rel = reference_images(geom, q, [box] * n, cams, W1, H1, 60.0, 0.01, 10.0)
+        scene, depth, rgba, seg = gpu_render(core, make_camera(W1, H1, eye=eye, target=target))
+        if box is None:
+            assert not (seg == _abi.SEG_BOX).any()
+        else:
+            assert min((r["seg"] == _abi.SEG_BOX).mean() for r in refs) > 0.02       # the static box is in view
+        assert all((r["seg"] == _abi.SEG_GROUND).any() and (r["seg"] >= _abi.SEG_CAPSULE0).any() for r in refs)
+        compare_scene(core, scene, geom, q, [box] * n, cams)
+        compare_images(refs, tol_abs, tol_rel, depth, rgba, seg, "static box" if over else "no box")
+        core.close()
+
+
+def _snapshot(core):
+    import torch
+    torch.cuda.synchronize()
+    names = ("arena", "stats", "counters", "obs_buf", "rew_buf", "reset_buf", "episode_step_count", "episode_length", "dof_state",
+             "root_state", "full_dof_targets", "masks")
+    snap = {n: getattr(core, n).clone() for n in names}
+    snap["stamp"] = core.get_step_stamp()
+    return snap
+
+
+def _same(a, b):
+    import torch
+    return all((a[k] == b[k]) if k == "stamp" else torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
+
+
+@pytest.mark.gpu
+def test_purity_and_determinism():
+    import torch
+    n = 70
+    core, sc, _ = _core("BlindGrasping", n)
+    twin, _, _ = _core("BlindGrasping", n)
+    g = torch.Generator().manual_seed(3)
+    acts = [(2 * torch.rand(n, 18, generator=g) - 1).cuda() for _ in range(13)]
+    for a in acts[:3]:
+        core.step(a)
+        twin.step(a)
+    before = _snapshot(core)
+    cam = make_camera(50, 30, eye=(-0.3, 0.25, 0.6), target=(0.0, 0.0, 0.3))
+    r1 = gpu_render(core, cam)
+    assert _same(before, _snapshot(core))                         # a render between two steps changes nothing
+    r2 = gpu_render(core, cam)
+    assert all((x.view(np.uint8) == y.view(np.uint8)).all() for x, y in zip(r1, r2))   # two renders of one state: bit-identical
+    for a in acts[3:]:
+        core.step(a)
+        twin.step(a)
+    assert _same(_snapshot(core), _snapshot(twin))                # ... and the run continues like a twin that never rendered
+    for c in (core, twin):
+        c.close()
+
+
+@pytest.mark.gpu
+def test_env_surface():
+    import torch
+    from dexrobot_isaac_amd import make_env
+    env = make_env("BlindGrasping", 8, "cuda:0", "cuda:0", 0, video_config={"resolution": [64, 48]})
+    env.reset()
+    frame = env.render()
+    assert isinstance(frame, np.ndarray) and frame.shape == (48, 64, 3) and frame.dtype == np.uint8
+    out = env.render_camera("video", [0])
+    assert set(out) == {"rgba", "depth", "seg"} and out["rgba"].is_cuda and out["depth"].shape == (1, 48, 64)
+    assert (out["rgba"][0, ..., :3].cpu().numpy() == frame).all()
+    assert (out["seg"] >= _abi.SEG_CAPSULE0).any() and (out["seg"] == _abi.SEG_GROUND).any()   # hand and ground are in view
+    cam = env._cameras["video"]["cam"]
+    assert cam.hfov_deg == 75.0 and tuple(cam.eye) == (-1.5, 0.0, 0.5) and abs(cam.target[2] - 0.15) < 1e-7
+    g = torch.Generator().manual_seed(1)
+    for _ in range(12):
+        env.step((2 * torch.rand(8, 18, generator=g) - 1).cuda())
+    assert (env.render() != frame).any()                          # the hand moved
+    # per-env placement and a mounted camera through the env API
+    env.create_camera("palm", 32, 24, hfov_deg=90.0, eye=(0.0, -0.15, 0.1), target=(-0.05, 0.0, 0.0), parent="ARRz")
+    eyes = torch.tensor([[-0.4 - 0.05 * i, 0.3, 0.6] for i in range(8)])
+    env.create_camera("each", 32, 24, eye=eyes, target=(0.0, 0.0, 0.3))
+    a = env.render_camera("each", outputs=("depth",))["depth"]
+    assert a.shape == (8, 24, 32) and not torch.equal(a[0], a[7])
+    sub = env.render_camera("each", [7, 0], outputs=("depth",))["depth"]
+    assert torch.equal(sub[0], a[7]) and torch.equal(sub[1], a[0])
+    assert env.render_camera("palm", outputs=("seg",))["seg"].shape == (8, 24, 32)
+    with pytest.raises(KeyError):
+        env.render_camera("nope")
+    env.close()
+    plain = make_env("BlindGrasping", 8, "cuda:0", "cuda:0", 0)
+    assert plain.render() is None                                 # no camera: exactly as before
+    plain.close()
+
+
+def test_oracle_backend_has_no_cameras():
+    from dexrobot_isaac_amd import make_env
+    from oracle.py_backend import OracleCore
+    env = make_env("BaseTask", 2, "cpu", "cpu", 0, _core_factory=OracleCore)
+    assert env.render() is None
+    with pytest.raises(NotImplementedError):
+        env.create_camera("video", 64, 48)
