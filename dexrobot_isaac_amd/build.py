@@ -12,6 +12,9 @@ SOURCES = ["dexsim.hip", "dexsim_device.h", "dexsim_physics.hip.inc", "dexsim_l2
 
 
 DEBUG_SPIN_LIB = os.path.join(HERE, "libdexsim_dbgspin.so")
+# the code-generation flags of the library (reasons: build_lib); tests that compile device code of the library stand-alone use the same
+CODEGEN_FLAGS = ["--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
+                 "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-std=c++17"]
 
 
 def _stale(lib=LIB):
@@ -48,9 +51,7 @@ def build_lib(force=False, verbose=False, defs=(), out=None):
     # -mllvm -amdgpu-sched-strategy=max-ilp: the step kernel is a few long dependency chains on waves that are (almost) alone on
     # their SIMD, so the scheduler should interleave independent chains rather than minimise register pressure: same VGPR
     # counts, still no spills / scratch, 61.3 -> 62.2 M env-steps/s (contact-rich regime 187 -> 189 us: within 1 %).
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
-           "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-fPIC", "-shared", "-std=c++17", *defs,
-           "-o", lib, os.path.join(CSRC, "dexsim.hip")]
+    cmd = [hipcc, *CODEGEN_FLAGS, "-fPIC", "-shared", *defs, "-o", lib, os.path.join(CSRC, "dexsim.hip")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)

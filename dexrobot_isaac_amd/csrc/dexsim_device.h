@@ -174,6 +174,33 @@ DI V3& operator-=(V3& a, V3 b) { a.x -= b.x; a.y -= b.y; a.z -= b.z; return a; }
 DI float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 DI V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 DI float norm(V3 a) { return sqrtf(dot(a, a)); }
+// Range-unscaled reciprocal, division and square roots for the step path.  The operators `1.f / x`, `a / b`, sqrtf(x) and
+// 1.f / sqrtf(x) compile (2.5 ulp forms, FP32 denormals on) to the same v_rcp_f32 / v_sqrt_f32 / v_rsq_f32 wrapped in frexp / ldexp
+// range scaling that only matters when an operand or the result is denormal: 5, 8, 6 and 6 instructions instead of 1, 2, 1 and 1.
+// Inside the stated range the helpers return the operators' bits (tests/test_range_unscaled_math.py sweeps every bit pattern);
+// outside it they differ (denormals are flushed by the hardware instruction), so every call site states in one line why its
+// operand is in range.  Sites that cannot say so keep the operator.  rsq_n has no caller yet (the only
+// 1.f / sqrtf on the step path is spd_solve's clamped pivot, one instruction already); it is kept, and swept by the test, for later.
+// A site whose operator this build compiles as the correctly rounded v_div_scale / v_div_fmas / v_div_fixup sequence (schur_comp, the
+// solver's split factors) cannot go on a helper either: the last bit differs.
+// Two rewrites of the optimiser would change bits and are kept out: div_n's product is not contracted into a following add (the
+// operator's quotient is not either: its last instruction is the ldexp), and a root that a helper divides by is made opaque()
+// first (sqrt_n does it itself), so that div_n(a, root) stays v_sqrt_f32 + v_rcp_f32 like the operators' sequence instead of
+// becoming v_rsq_f32.
+DI float opaque(float x) { asm("" : "+v"(x)); return x; }   // no instruction: the value's origin is hidden from the optimiser
+// rcp_n: x and 1/x normal (2^-126 <= |x| <= 2^126)
+DI float rcp_n(float x) { return __builtin_amdgcn_rcpf(x); }
+// div_n: b and 1/b normal as for rcp_n; a anything finite as long as the quotient is zero or normal
+DI float div_n(float a, float b) {
+#pragma clang fp contract(off)
+  return a * __builtin_amdgcn_rcpf(b);
+}
+// sqrt_n: x zero or normal (the operator has no Newton step in this build: one v_sqrt_f32, as here)
+DI float sqrt_n(float x) { return opaque(__builtin_amdgcn_sqrtf(x)); }
+// rsq_n: x and the result normal (for 1.f / sqrtf(x) where the root has no other use: the operators are one v_rsq_f32 there)
+DI float rsq_n(float x) { return __builtin_amdgcn_rsqf(x); }
+// norm_n: |a| for a vector that is exactly zero or of model scale (a capsule axis): dot(a, a) zero or normal
+DI float norm_n(V3 a) { return sqrt_n(dot(a, a)); }
 DI float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 DI Q4 q4p(const float* p) { return {p[0], p[1], p[2], p[3]}; }
@@ -242,7 +269,7 @@ struct Comp { float m; V3 c; S6 I; };
 DI void comp_add(Comp& a, const Comp& b) {
   float m = a.m + b.m;
   if (m <= 0.f) return;
-  float inv = 1.f / m;
+  float inv = rcp_n(m);   // m > 0 is a sum of link masses of the model (zero or grams and up): normal
   V3 c = {(a.m * a.c.x + b.m * b.c.x) * inv, (a.m * a.c.y + b.m * b.c.y) * inv, (a.m * a.c.z + b.m * b.c.z) * inv};
   // the two parallel-axis shifts to the common centre of mass are one shift with the reduced mass: m_a |c_a - c|^2 (x) +
   // m_b |c_b - c|^2 (x) = (m_a m_b / m) |c_a - c_b|^2 (x) -- half the instructions, three times per finger and sub-step
@@ -261,8 +288,14 @@ DI void spd_inverse(float* A) {
       float s = A[i * n + j];
 #pragma unroll
       for (int k = 0; k < j; k++) s -= L[i * n + k] * L[j * n + k];
-      if (i == j) L[i * n + i] = sqrtf(fmaxf(s, 1e-20f));
-      else L[i * n + j] = s / L[j * n + j];
+      // pivots are clamped: 1e-20 <= s, so 1e-10 <= L_ii and 1 / L_ii <= 1e10.  ASSUMPTION, checked by nothing but the bitwise
+      // tests in the regimes they run: an off-diagonal numerator is exactly zero or a cancellation residue of model-scale inertias
+      // (a multiple of their ulp, far above 2^-100), so every quotient is zero or normal.  A denormal quotient would round once here
+      // and twice in the operator (mantissa product, then ldexp) and could differ in the last bit.  (sqrtf of a clamped
+      // value is one v_sqrt_f32 already: the compiler sees the range.  The operator also lets it share the first pivot with
+      // spd_solve where a caller branches between the two, as before.)
+      if (i == j) L[i * n + i] = opaque(sqrtf(fmaxf(s, 1e-20f)));
+      else L[i * n + j] = div_n(s, L[j * n + j]);
     }
   float Li[n * n]; // inverse of L (lower)
 #pragma unroll
@@ -272,7 +305,7 @@ DI void spd_inverse(float* A) {
       float s = (i == c) ? 1.f : 0.f;
 #pragma unroll
       for (int k = c; k < i; k++) s -= L[i * n + k] * Li[k * n + c];
-      Li[i * n + c] = s / L[i * n + i];
+      Li[i * n + c] = div_n(s, L[i * n + i]);   // L_ii >= 1e-10 (clamped pivot); s is 1 or a sum of products of quotients of the same kind
     }
 #pragma unroll
   for (int i = 0; i < n; i++)
@@ -299,6 +332,7 @@ DI void spd_solve(const float* A, const float* b, float* x) {
       float s = A[i * n + j];
 #pragma unroll
       for (int k = 0; k < j; k++) s -= L[i * n + k] * L[j * n + k];
+      // (operators: the clamp tells the compiler the range, 1.f / sqrtf is one v_rsq_f32 here)
       if (i == j) { const float d = sqrtf(fmaxf(s, 1e-20f)); L[i * n + i] = d; rd[i] = 1.f / d; }
       else L[i * n + j] = s * rd[j];
     }

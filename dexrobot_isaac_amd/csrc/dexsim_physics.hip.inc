@@ -125,8 +125,8 @@ DI void sphere_box(V3 P, float r, float hb, V3& nl, V3& pl, float& gapraw) {
   V3 d = P - qv;
   float d2 = dot(d, d);
   if (d2 > 1e-12f) {
-    float dist = sqrtf(d2);
-    nl = {d.x / dist, d.y / dist, d.z / dist};
+    float dist = sqrt_n(d2);   // d2 > 1e-12: dist > 1e-6, |d_i| <= dist
+    nl = {div_n(d.x, dist), div_n(d.y, dist), div_n(d.z, dist)};
     pl = qv;
     gapraw = dist - r;
   } else {
@@ -157,7 +157,7 @@ DI void collide_capsule(const Arena& A, int N, int e, int& nc, const DexSimConfi
   if (has_box) {
     V3 a = mulT(Rb, e0 - bpos), b = mulT(Rb, e1 - bpos), d = b - a;
     V3 mid = {0.5f * (a.x + b.x), 0.5f * (a.y + b.y), 0.5f * (a.z + b.z)};
-    float reach = 0.5f * norm(d) + r + 1.7320508f * hb + co;
+    float reach = 0.5f * norm_n(d) + r + 1.7320508f * hb + co;   // d: a capsule axis of the model (exactly zero for a sphere)
     // broadphase (bounding spheres); wave-level early-out keeps the lockstep lanes from paying for the
     // bisection when no env in the wavefront is near its box
     bool near = dot(mid, mid) < reach * reach;
@@ -207,7 +207,7 @@ DI void collide_capsules3(const Arena& A, int N, int e, int& nc, const DexSimCon
       const V3 b = mulT(Rb, E1[c] - bpos);
       d[c] = b - a[c];
       const V3 mid = {0.5f * (a[c].x + b.x), 0.5f * (a[c].y + b.y), 0.5f * (a[c].z + b.z)};
-      const float reach = 0.5f * norm(d[c]) + r[c] + 1.7320508f * hb + co;
+      const float reach = 0.5f * norm_n(d[c]) + r[c] + 1.7320508f * hb + co;   // d: a capsule axis of the model (exactly zero for a sphere)
       near[c] = dot(mid, mid) < reach * reach;      // broadphase (bounding spheres)
     }
     // (Round 3 guarded each capsule's chain with its own wave-uniform "some lane is near" branch: no measurable change in any regime
@@ -358,7 +358,7 @@ DI bool capsule_clear(V3 e0, V3 e1, float r, const DexSimConfig& C, V3 bpos, con
     const V3 mid = mulT(Rb, V3{0.5f * (e0.x + e1.x) - bpos.x, 0.5f * (e0.y + e1.y) - bpos.y, 0.5f * (e0.z + e1.z) - bpos.z});
     const float hb = 0.5f * C.box_size;
     const V3 ex = {mid.x - clampf(mid.x, -hb, hb), mid.y - clampf(mid.y, -hb, hb), mid.z - clampf(mid.z, -hb, hb)};
-    const float reach = (0.5f * norm(d) + r + co) * 1.0001f + 1e-6f;
+    const float reach = (0.5f * norm_n(d) + r + co) * 1.0001f + 1e-6f;   // d: a capsule axis of the model (exactly zero for a sphere)
     clear = clear && !(dot(ex, ex) < reach * reach);
   }
   return clear;
@@ -727,6 +727,9 @@ DI Comp schur_comp(const float* sh, const int dlb, int lane, V3 o5) {
     sd += mf * sh_get3(sh, lane, DL_COMP(dlb, f) + 1);
     J = J + S6{SH(DL_COMP(dlb, f) + 4), SH(DL_COMP(dlb, f) + 5), SH(DL_COMP(dlb, f) + 6), SH(DL_COMP(dlb, f) + 7), SH(DL_COMP(dlb, f) + 8), SH(DL_COMP(dlb, f) + 9)};
   }
+  // (operator, not rcp_n, although M is a sum of link masses: this reciprocal -- like five of the block sweeps' split factors 1/n --
+  // is the correctly rounded v_div_scale / v_div_fmas / v_div_fixup sequence in this build, not the scaled v_rcp_f32, and a helper
+  // would change its last bit)
   const float inv = M > 0.f ? 1.f / M : 0.f;
   const V3 d = inv * sd;
   const S6 sh_back = pa(M, d);
@@ -950,7 +953,7 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
   float inv_m = 0.f, inv_I = 0.f;
   V3 bpos = {0, 0, 0};
   if (C.has_box) {
-    if (!C.box_fixed) { inv_m = 1.f / FLD(box_mass, 0); inv_I = P->box_inv_I_k * inv_m; }   // (static box: 1/m = 1/I = 0)
+    if (!C.box_fixed) { inv_m = rcp_n(FLD(box_mass, 0)); inv_I = P->box_inv_I_k * inv_m; }   // (static box: 1/m = 1/I = 0)  [rcp_n: a body mass in kg]
     bpos = {FLD(box_pos, 0), FLD(box_pos, 1), FLD(box_pos, 2)};
   }
   const int f = type != 2 ? CODE_FINGER(code) : -1, lvl = f >= 0 ? CODE_LEVEL(code) : -1;   // (looked up by the narrowphase)
@@ -1100,7 +1103,7 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
   // lets the solver take a contact's three J.u products against the velocities at contact entry)
 #pragma unroll
   for (int r = 0; r < 3; r++) {
-    const float Dinv = (lim && r > 0) ? 0.f : 1.f / (Dq[r] + 1e-9f);
+    const float Dinv = (lim && r > 0) ? 0.f : 1.f / (Dq[r] + 1e-9f);   // (operator: see the note at the box block's 1/D)
     const float pad = r == 0 ? A10 : (r == 1 ? A20 : A21);
     const int rw = (k * 3 + r) * CROW_W;
     if (FUSED) {   // quad layout in the arena
@@ -1122,7 +1125,8 @@ DI void build_contact_rows(const Arena& A, const DevParams* __restrict__ P, cons
       FLD(crow, rw + 26) = Dinv; FLD(crow, rw + 27) = pad;
     }
   }
-  const float cb = gap > 0.f ? gap / h : -fminf(-gap * C.erp / h, C.max_depenetration_velocity);
+  // h: the sub-step, 1e-4 .. 1e-1 s; the gap is zero or a rounding residue of model-scale lengths (>= 2^-60), so is the quotient
+  const float cb = gap > 0.f ? div_n(gap, h) : -fminf(div_n(-gap * C.erp, h), C.max_depenetration_velocity);
   const bool warm = gen >= 0 && __float_as_int(wq.w) == 8 * gen + (type == 2 ? CODE_SAMPLE(code) : 0);
   // compact per-contact header for the solve kernel: no dependent model look-ups on its critical path
   if (!FUSED) {
@@ -1303,6 +1307,10 @@ struct BoxBlock {
 #pragma unroll
       for (int r = 0; r < 3; r++) lam4[k][r] = (use && resume) ? s_lam[(3 * k + r) * 64 + lane] : 0.f;
       const float xx = rx[k] * rx[k], yy = ry[k] * ry[k], zz = rz[k] * rz[k];
+      // These three, the row builder's 1/D and tangent_basis stay on the operators although their operands are in rcp_n's range
+      // (non-negative terms plus 1e-9): with them on the helpers the register allocator leaves a 36-byte spill slot that no
+      // instruction uses in k_physics4<false> or k_physics1<false>, and a launch with any private segment pays for its set-up.
+      // None of them is on a finger chain.
       Dv[k][0] = use ? 1.f / (inv_m + inv_I * (xx + yy) + 1e-9f) : 0.f;
       Dv[k][1] = use ? 1.f / (inv_m + inv_I * (xx + zz) + 1e-9f) : 0.f;
       Dv[k][2] = use ? 1.f / (inv_m + inv_I * (yy + zz) + 1e-9f) : 0.f;
@@ -1467,7 +1475,7 @@ DI void solve_forces_box(const Arena& A, const DevParams* __restrict__ P, int* _
 // forces_reduce (one wave, after a barrier) adds the five blocks in wave order and writes the result: fixed order, bit-reproducible.
 DI void forces_partial(const Arena& A, const DevParams* __restrict__ P, const float* s_hdr, const float* s_lam, float* s_f, int nc, int w,
                        int lane, int N, int e) {
-  const float rh = 1.f / P->h;
+  const float rh = rcp_n(P->h);   // the sub-step, 1e-4 .. 1e-1 s
 #pragma unroll
   for (int i = 0; i < DEXSIM_NFSLOT * 3; i++) s_f[i * 64 + lane] = 0.f;
   int slot[5];
@@ -1540,8 +1548,9 @@ DI void integrate_box(const Arena& A, float h, const float* vb, const float* wb,
   Q4 bq = {FLD(box_quat, 0), FLD(box_quat, 1), FLD(box_quat, 2), FLD(box_quat, 3)};
   Q4 dq = qmul(Q4{wb[0], wb[1], wb[2], 0.f}, bq);
   Q4 qn = {bq.x + 0.5f * h * dq.x, bq.y + 0.5f * h * dq.y, bq.z + 0.5f * h * dq.z, bq.w + 0.5f * h * dq.w};
-  float l = sqrtf(qn.x * qn.x + qn.y * qn.y + qn.z * qn.z + qn.w * qn.w);
-  FLD(box_quat, 0) = qn.x / l; FLD(box_quat, 1) = qn.y / l; FLD(box_quat, 2) = qn.z / l; FLD(box_quat, 3) = qn.w / l;
+  // a unit quaternion plus an increment orthogonal to it: l >= 1 - rounding, every |component| <= l (zero components stay zero)
+  float l = sqrt_n(qn.x * qn.x + qn.y * qn.y + qn.z * qn.z + qn.w * qn.w);
+  FLD(box_quat, 0) = div_n(qn.x, l); FLD(box_quat, 1) = div_n(qn.y, l); FLD(box_quat, 2) = div_n(qn.z, l); FLD(box_quat, 3) = div_n(qn.w, l);
 }
 
 // Stand-alone contact-solve kernel (profiling / staged tests; production runs the fused k_physics4 / k_physics1 below):
@@ -1568,7 +1577,7 @@ __global__ __launch_bounds__(64) void k_solve(Arena A, const DevParams* __restri
   for (int i = 0; i < 3; i++) { vb[i] = FLD(ufree, 26 + i); wb[i] = FLD(ufree, 29 + i); }
   const int nc = FLD(ncontact, 0);
   float inv_m = 0.f, inv_I = 0.f;
-  if (has_box && !C.box_fixed) { inv_m = 1.f / FLD(box_mass, 0); inv_I = P->box_inv_I_k * inv_m; }
+  if (has_box && !C.box_fixed) { inv_m = rcp_n(FLD(box_mass, 0)); inv_I = P->box_inv_I_k * inv_m; }   // a body mass in kg
   int kmax = nc;
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) kmax = max(kmax, __shfl_xor(kmax, s));
@@ -2093,7 +2102,7 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) nbmax = max(nbmax, __shfl_xor(nbmax, s));
     nbmax = __builtin_amdgcn_readfirstlane(nbmax);
-    const float nXf = (float)SPLIT_NX(split), rX = 1.f / nXf;
+    const float nXf = (float)SPLIT_NX(split), rX = 1.f / nXf;   // (the split factors 1/n stay on the operator: see schur_comp)
     if (wv == 6) {
       // the box wave: block 12 (box/ground contacts, all in VGPRs) + reducer of box twist words 2-5
       const int cpack = __float_as_int(SH(FS_CPACK));
@@ -2517,7 +2526,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
       bmu = FLD(box_mu, 0);
       const float mu_bg = 0.5f * (bmu + C.ground_friction);
       const bool bfix = C.box_fixed != 0;   // the harness's static box: infinite mass, no gravity, no box/ground rows
-      const float inv_m = bfix ? 0.f : 1.f / FLD(box_mass, 0), inv_I = P->box_inv_I_k * inv_m;
+      const float inv_m = bfix ? 0.f : rcp_n(FLD(box_mass, 0)) /* a body mass in kg */, inv_I = P->box_inv_I_k * inv_m;
       SH(FS_CMP_INVM) = inv_m; SH(FS_CMP_INVM + 1) = inv_I;
       V3 dirz[3];
       dirz[0] = v3(0, 0, 1);
@@ -2537,7 +2546,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
           const float gap = p.z - C.rest_offset;
           const V3 rb = p - bpos;
           { float* rp = sh + (FS_CMP + 3 * k) * 64 + lane; rp[0] = rb.x; rp[64] = rb.y; rp[128] = rb.z; }
-          const float cb = gap > 0.f ? gap / h : -fminf(-gap * C.erp / h, C.max_depenetration_velocity);
+          const float cb = gap > 0.f ? div_n(gap, h) : -fminf(div_n(-gap * C.erp, h), C.max_depenetration_velocity);   // as in build_contact_rows
           s_hdr[(4 * k) * 64 + lane] = __int_as_float(2); s_hdr[(4 * k + 1) * 64 + lane] = __int_as_float(-1);
           s_hdr[(4 * k + 2) * 64 + lane] = mu_bg; s_hdr[(4 * k + 3) * 64 + lane] = cb;
           if (LAST) {   // observable after the step: manifold arrays, force slot / normal (solve_forces)
