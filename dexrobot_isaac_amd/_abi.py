@@ -135,6 +135,7 @@ EXPORTED_SYMBOLS = [
     "dexsim_state_layout", "dexsim_save_state", "dexsim_load_state", "dexsim_copy_envs", "dexsim_get_step_stamp",
     "dexsim_set_step_stamp",
     "dexsim_camera_struct_size", "dexsim_render_layout", "dexsim_render",
+    "dexsim_body_jacobian", "dexsim_mass_matrix",
 ]
 
 
@@ -178,6 +179,8 @@ def declare_prototypes(lib):
     lib.dexsim_camera_struct_size.argtypes = [P(sz)]
     lib.dexsim_render_layout.argtypes = [P(DexSimField), i32, P(i32), P(sz)]
     lib.dexsim_render.argtypes = [vp, P(DexSimCamera), vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.dexsim_body_jacobian.argtypes = [vp, vp, i32, vp, P(i32), i32, vp, vp]
+    lib.dexsim_mass_matrix.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = i32
     lib.dexsim_error_string.argtypes = [i32]

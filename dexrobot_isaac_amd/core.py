@@ -361,3 +361,56 @@ class DexSimCore:
                 ptr(seg, "seg", torch.int32, (k, H, W)))
         self._keep_render = (ids, eye, target)     # alive until the kernels ran
         check(self.lib.dexsim_render(self.h, C.byref(cam), *args, self._stream()), "render")
+
+    # ------------------------------------------------------------------ Jacobians, mass matrix, gravity force
+    def _kin_rows(self, what, env_ids, q):
+        """(ids pointer, q pointer, k) of a dexsim_body_jacobian / dexsim_mass_matrix call; keeps the tensors alive."""
+        ids = None
+        k = self.N
+        if q is not None:
+            if q.device != self.device or q.dtype != torch.float32 or not q.is_contiguous() or q.dim() != 2 or q.shape[1] != _abi.NJ \
+                    or q.shape[0] < 1:
+                raise DexSimError(f"{what}: q must be a contiguous float32 tensor of shape (k, {_abi.NJ}), k >= 1, on {self.device}, "
+                                  f"got {q.dtype} {tuple(q.shape)} on {q.device}")
+            k = int(q.shape[0])
+        elif env_ids is not None:
+            ids = torch.as_tensor(env_ids, device=self.device).to(torch.int64).contiguous().view(-1)
+            k = int(ids.numel())
+            if k < 1:
+                raise DexSimError(f"{what}: env_ids is empty")
+        self._keep_kin = (ids, q)
+        return (None if ids is None else C.c_void_p(ids.data_ptr())), (None if q is None else C.c_void_p(q.data_ptr())), k
+
+    def _kin_out(self, what, name, t, shape):
+        if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise DexSimError(f"{what}: {name} must be a contiguous float32 tensor of shape {shape} on {self.device}, "
+                              f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return C.c_void_p(t.data_ptr())
+
+    def body_jacobian(self, out, env_ids=None, q=None, bodies=None):
+        """Geometric Jacobians of the hand bodies `bodies` (indices into the rows of rigid_body_states; None = all 37) into
+        `out` (k, nb, 6, 26) f32: rows 0-2 linear velocity of the body origin, 3-5 angular velocity, world frame, so that
+        out[i, b] @ qd == rigid_body_states[env, b, 7:13].  Rows: env_ids (None = all envs), or the rows of a (k, 26) `q`
+        override (env_ids is then ignored).  dexsim_body_jacobian."""
+        ids, qp, k = self._kin_rows("body_jacobian", env_ids, q)
+        if bodies is None:
+            nb, bp = _abi.NUM_HAND_BODIES, None
+        else:
+            bl = [int(b) for b in bodies]
+            nb = len(bl)
+            if not 1 <= nb <= _abi.NUM_HAND_BODIES:
+                raise DexSimError(f"body_jacobian: between 1 and {_abi.NUM_HAND_BODIES} bodies, got {nb}")
+            bp = (C.c_int * nb)(*bl)
+        op = self._kin_out("body_jacobian", "out", out, (k, nb, 6, _abi.NJ))
+        check(self.lib.dexsim_body_jacobian(self.h, ids, k, qp, bp, nb, op, self._stream()), "body_jacobian")
+
+    def mass_matrix(self, mass=None, gravity=None, env_ids=None, q=None):
+        """Joint-space inertia M(q) into `mass` (k, 26, 26) f32 and / or the gravity force dV/dq into `gravity` (k, 26) f32
+        (what a controller adds to hold the hand).  M carries no armature and no PD terms.  Rows as for body_jacobian.
+        dexsim_mass_matrix."""
+        if mass is None and gravity is None:
+            raise DexSimError("mass_matrix: at least one of mass and gravity is required")
+        ids, qp, k = self._kin_rows("mass_matrix", env_ids, q)
+        mp = None if mass is None else self._kin_out("mass_matrix", "mass", mass, (k, _abi.NJ, _abi.NJ))
+        gp = None if gravity is None else self._kin_out("mass_matrix", "gravity", gravity, (k, _abi.NJ))
+        check(self.lib.dexsim_mass_matrix(self.h, ids, k, qp, mp, gp, self._stream()), "mass_matrix")

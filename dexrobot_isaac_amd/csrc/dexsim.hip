@@ -816,3 +816,58 @@ extern "C" int dexsim_render(dexsim_t h, const DexSimCamera* cam, const float* e
   }
   return DEXSIM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------- Jacobians, mass matrix, gravity force
+// Behind every use of the step kernels, like the state and camera kernels above.
+// clang-format off
+#include "dexsim_kindyn.hip.inc"
+// clang-format on
+
+// The checks both entry points share; none of them needs a device.  k is the number of output rows.
+static int kin_rows(const char* who, dexsim_t h, const int64_t* env_ids, int k, const float* q, KinRows* R) {
+  if (!h) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": null handle").c_str());
+  if (k <= 0) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": k must be positive").c_str());
+  if (!q && !env_ids && k != h->N) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": env_ids == NULL without a q override needs k == num_envs").c_str());
+  R->env_ids = q ? nullptr : env_ids; R->q = q; R->k = k;
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_body_jacobian(dexsim_t h, const int64_t* env_ids, int k, const float* q, const int* bodies, int nb, float* jac,
+                                    void* stream) {
+  KinJac J;
+  std::memset(&J, 0, sizeof J);
+  int rc = kin_rows("dexsim_body_jacobian", h, env_ids, k, q, &J.rows);
+  if (rc) return rc;
+  if (nb < 1 || nb > DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: nb must be in [1, DEXSIM_NUM_HAND_BODIES]");
+  if (!bodies && nb != DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: bodies == NULL needs nb == DEXSIM_NUM_HAND_BODIES");
+  for (int i = 0; i < nb; i++) {
+    const int b = bodies ? bodies[i] : i;
+    if (b < 0 || b >= DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: body index out of range");
+    J.body[i] = (unsigned char)b;
+  }
+  if (!jac || ((uintptr_t)jac & 15) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: jac must be a 16-byte aligned device pointer");
+  for (int b = 0; b < DEXSIM_NUM_HAND_BODIES; b++)
+    if (h->model.body_parent[b] != kd_body_joint(b))
+      return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: model.body_parent differs from the frames rigid_body_states is published on");
+  NEED_BOUND(h);
+  J.jac = jac; J.nb = nb;
+  const dim3 grid((unsigned)((k + 63) / 64), (unsigned)((nb + KJ_CHUNK - 1) / KJ_CHUNK));
+  k_kin_jacobian<<<grid, dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, J, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_mass_matrix(dexsim_t h, const int64_t* env_ids, int k, const float* q, float* mass, float* gravity, void* stream) {
+  KinMass K;
+  std::memset(&K, 0, sizeof K);
+  int rc = kin_rows("dexsim_mass_matrix", h, env_ids, k, q, &K.rows);
+  if (rc) return rc;
+  if (!mass && !gravity) return fail(DEXSIM_ERR_ARG, "dexsim_mass_matrix: at least one of mass and gravity is required");
+  if (((uintptr_t)mass & 15) != 0 || ((uintptr_t)gravity & 3) != 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_mass_matrix: mass must be 16-byte aligned, gravity 4-byte aligned");
+  NEED_BOUND(h);
+  K.mass = mass; K.gravity = gravity;
+  k_kin_mass<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}

@@ -805,6 +805,79 @@ class DexHandEnv:
             return None
         return self.render_camera("video", [0], ("rgba",))["rgba"][0, :, :, :3].cpu().numpy()
 
+    # ------------------------------------------------------------------ Jacobians, mass matrix, gravity force
+    def _kindyn_rows(self, what, env_ids, q):
+        """The HIP core, (ids, q) as device tensors and the number of output rows k, for get_jacobian / get_mass_matrix."""
+        core = self._core
+        if not hasattr(core, "body_jacobian"):
+            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no body_jacobian()")
+        if q is not None:
+            q = torch.as_tensor(q, dtype=torch.float32, device=core.device)
+            if q.dim() != 2 or q.shape[1] != _abi.NJ or q.shape[0] < 1:
+                raise ValueError(f"{what}: q must have shape (k, {_abi.NJ}) with k >= 1, got {tuple(q.shape)}")
+            return core, None, q.contiguous(), int(q.shape[0])
+        if env_ids is None:
+            return core, None, None, self.num_envs
+        ids = torch.as_tensor(env_ids, device=core.device).to(torch.int64).view(-1)
+        if ids.numel() < 1:
+            raise ValueError(f"{what}: env_ids is empty")
+        return core, ids, None, int(ids.numel())
+
+    def _kindyn_out(self, what, out, shape, device):
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=device)      # the kernels write every element
+        if not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() \
+                or out.device != device:
+            raise ValueError(f"{what}: out must be a contiguous float32 tensor of shape {shape} on {device}")
+        return out
+
+    def get_jacobian(self, bodies=None, env_ids=None, q=None, out=None):
+        """gym.acquire_jacobian_tensor / refresh_jacobian_tensors for the hand: (k, nb, 6, 26) geometric Jacobians of the hand
+        bodies `bodies` -- indices into the rows of rigid_body_states or names from hand_model.BODY_NAMES such as
+        "r_f_link2_tip"; None = all 37 in order.  Rows 0-2: world linear velocity of the body origin, 3-5: world angular
+        velocity; column j: DOF j of dof_state, so jac[i, b] @ dof_vel[env] == rigid_body_states[env, b, 7:13].  Rows: the
+        envs `env_ids` (None = all), or the rows of a (k, 26) joint-position override `q` (env_ids is then ignored)."""
+        core, ids, q, k = self._kindyn_rows("get_jacobian", env_ids, q)
+        if bodies is None:
+            idx = None
+            nb = _abi.NUM_HAND_BODIES
+        else:
+            if isinstance(bodies, (str, int)):
+                bodies = [bodies]
+            idx = []
+            for b in bodies:
+                if isinstance(b, str):
+                    if b not in self.model.body_names:
+                        raise ValueError(f"get_jacobian: unknown body '{b}' (bodies: {self.model.body_names})")
+                    b = self.model.body_names.index(b)
+                b = int(b)
+                if not 0 <= b < _abi.NUM_HAND_BODIES:
+                    raise ValueError(f"get_jacobian: body index must be in [0, {_abi.NUM_HAND_BODIES}), got {b}")
+                idx.append(b)
+            nb = len(idx)
+            if not 1 <= nb <= _abi.NUM_HAND_BODIES:
+                raise ValueError(f"get_jacobian: between 1 and {_abi.NUM_HAND_BODIES} bodies, got {nb}")
+        out = self._kindyn_out("get_jacobian", out, (k, nb, 6, _abi.NJ), core.device)
+        core.body_jacobian(out, env_ids=ids, q=q, bodies=idx)
+        return out
+
+    def get_mass_matrix(self, env_ids=None, q=None, gravity=False, out=None):
+        """gym.acquire_mass_matrix_tensor / refresh_mass_matrix_tensors for the hand: the (k, 26, 26) joint-space inertia M(q)
+        (no armature, no PD terms).  gravity=True returns (M, g) with g (k, 26) the gravity force dV/dq: the generalized force
+        a controller adds to hold the hand.  Rows as for get_jacobian.  out: M, or the pair (M, g) when gravity=True."""
+        core, ids, q, k = self._kindyn_rows("get_mass_matrix", env_ids, q)
+        if gravity:
+            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+                raise ValueError("get_mass_matrix: with gravity=True, out must be the pair (M, g)")
+            om, og = (None, None) if out is None else out
+            M = self._kindyn_out("get_mass_matrix", om, (k, _abi.NJ, _abi.NJ), core.device)
+            g = self._kindyn_out("get_mass_matrix", og, (k, _abi.NJ), core.device)
+            core.mass_matrix(mass=M, gravity=g, env_ids=ids, q=q)
+            return M, g
+        M = self._kindyn_out("get_mass_matrix", out, (k, _abi.NJ, _abi.NJ), core.device)
+        core.mass_matrix(mass=M, env_ids=ids, q=q)
+        return M
+
     def close(self):
         if self._core is not None:
             self._core.close()

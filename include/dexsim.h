@@ -577,6 +577,44 @@ int dexsim_render_layout(DexSimField* fields, int max_fields, int* n_fields, siz
 int dexsim_render(dexsim_t h, const DexSimCamera* cam, const float* eye, const float* target, const int64_t* env_ids, int k,
                   float* scene, float* depth, uint8_t* rgba, int32_t* seg, void* stream);
 
+/* ------------------------------------------------------------------ body Jacobians, mass matrix and gravity force
+ * The counterparts of gym.acquire_jacobian_tensor / refresh_jacobian_tensors and gym.acquire_mass_matrix_tensor /
+ * refresh_mass_matrix_tensors for the hand actor, for Cartesian fingertip control and inverse kinematics, operational-space and
+ * impedance control, gravity compensation and grasp analysis (J^T maps contact forces to joint torques).  Everything here is a
+ * pure function of q: no velocity-product terms.  Both calls are stream-ordered, never synchronise and allocate nothing, and
+ * neither writes any arena word, API tensor, statistics word, counter or the step stamp.
+ *
+ * ROWS.  Output row i describes env env_ids[i] (device array of k int64).  env_ids == NULL: row i is env i, and k must be
+ * num_envs.  A row whose id is outside [0, num_envs) is skipped: its output row is left untouched, as the camera call leaves
+ * the images of such a row.
+ * Q OVERRIDE.  q == NULL: the envs' current q (arena).  q != NULL: a device (k, 26) row-major array of joint positions in
+ * dof_state order that takes the place of the state; env_ids is then ignored and k may be any positive number (the model is
+ * shared by all envs: a batched kinematics service for planners and IK loops).  A row of q equal to an env's current q gives
+ * that env's output bit for bit.
+ *
+ * JACOBIAN  jac (k, nb, 6, 26) f32 row-major, 16-byte aligned.  bodies: HOST array of nb hand-body indices in
+ * [0, DEXSIM_NUM_HAND_BODIES), in the row order of rigid_body_states and the name order of the body-name table; NULL = all
+ * DEXSIM_NUM_HAND_BODIES in order (nb must then be DEXSIM_NUM_HAND_BODIES).  Rows 0-2: world linear velocity of the body-frame
+ * origin (the point rigid_body_states publishes in columns 0:3, whose velocity it publishes in 7:10); rows 3-5: world angular
+ * velocity; column j: DOF j in dof_state order.  Contract: jac[i, b] @ qd == rigid_body_states[env, b, 7:13].  Columns of
+ * joints that do not move the body are written as exact 0.0f (the buffer need not be zeroed); body 0 (hand_mount, welded to
+ * the fixed spawn frame) is all zeros.  The bodies ride on the joint frames rigid_body_states places them on; a model whose
+ * body_parent says otherwise is refused.
+ *
+ * MASS MATRIX  mass (k, 26, 26) f32, 16-byte aligned: the joint-space inertia M(q) of the articulated hand (composite-rigid-body
+ * method), general link inertias.  No armature and no PD terms: the integrator's M^ adds diag(armature + h (kd + h kp)) to it.
+ * Both triangles are written from one computed value (M == M^T bitwise); the finger-finger cross blocks are exact zeros.
+ * GRAVITY FORCE  gravity (k, 26) f32: dV/dq for cfg.gravity, i.e. the bias force of the recursive Newton-Euler pass at qd = 0 --
+ * the generalized force a controller ADDS to hold the hand (default model, gravity (0, 0, -9.81): entry 2, the z slide, is about
+ * +5.17 N).  Either of mass and gravity may be NULL, not both.
+ *
+ * DEXSIM_ERR_ARG (with a dexsim_last_error text; no device needed): NULL handle, k <= 0, env_ids == NULL without q and
+ * k != num_envs, nb outside [1, DEXSIM_NUM_HAND_BODIES], a body index out of range, bodies == NULL with
+ * nb != DEXSIM_NUM_HAND_BODIES, a NULL or misaligned output.  DEXSIM_ERR_NOT_BOUND before dexsim_bind. */
+int dexsim_body_jacobian(dexsim_t h, const int64_t* env_ids, int k, const float* q, const int* bodies, int nb, float* jac,
+                         void* stream);
+int dexsim_mass_matrix(dexsim_t h, const int64_t* env_ids, int k, const float* q, float* mass, float* gravity, void* stream);
+
 const char* dexsim_error_string(int code);
 const char* dexsim_last_error(void);
 

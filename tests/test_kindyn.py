@@ -1,0 +1,450 @@
+"""Body Jacobians, mass matrix and gravity force on the device (dexsim_body_jacobian, dexsim_mass_matrix) against
+tests/kindyn_ref.py: a float64 geometric Jacobian built on render_ref's forward kinematics, and the CPU oracle's M(q) and bias force.
+
+Tolerances:
+  * Jacobian: 1e-5 absolute.  sincos_joint is good to 2e-7 per half-angle (tests/test_sincos_joint.py), so a rotation-matrix entry
+    is off by <~ 6e-7 per revolute joint, there are 7 revolute joints from the base to a fingertip, and levers are below 0.4 m;
+    any index, sign, lever or ancestor bug is >= 1e-3.
+  * M and gravity: 4 x the roundoff of the fp32 oracle against the fp64 oracle on the SAME poses (test_reference_roundoff measures
+    it: e_M ~ 1.7e-5, e_g ~ 9e-7), in scale-free metrics (kindyn_ref.err_M, err_g).  The factor 4 is the project's factor 3 for
+    "a different factorisation of the same fp32 arithmetic" plus one for sincos_joint and the 2.5-ulp division / root of the build.
+Every GPU test uses N = 70: two workgroups, six live lanes in the second.  Every device output sits between two guard rows that
+must come back untouched.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from dexrobot_isaac_amd import _abi, _lib
+from dexrobot_isaac_amd.build import build_lib
+from dexrobot_isaac_amd.config import build_sim_config, default_cfg
+from tests import kindyn_ref as kr
+
+N = 70
+NB, NJ = _abi.NUM_HAND_BODIES, _abi.NJ
+GUARD = -7.0
+
+
+def _setup(n, task="BlindGrasping"):
+    cfg = default_cfg(task)
+    cfg["env"]["numEnvs"] = n
+    sc, model = build_sim_config(cfg)
+    return sc, model.to_struct()
+
+
+# ------------------------------------------------------------------------------------------------- CPU
+@pytest.fixture(scope="module")
+def lib():
+    build_lib()
+    return _lib.load()
+
+
+def test_abi_exports_and_null_handle(lib):
+    for name in ("dexsim_body_jacobian", "dexsim_mass_matrix"):
+        assert name in _abi.EXPORTED_SYMBOLS
+        assert hasattr(lib, name), f"libdexsim.so does not export {name}"
+    assert lib.dexsim_body_jacobian(None, None, 1, None, None, NB, None, None) == 1          # DEXSIM_ERR_ARG
+    assert b"null handle" in lib.dexsim_last_error()
+    assert lib.dexsim_mass_matrix(None, None, 1, None, None, None, None) == 1
+    assert b"null handle" in lib.dexsim_last_error()
+
+
+def test_reference_jacobian_is_the_derivative_of_fk():
+    _, ms = _setup(1)
+    hk = kr.HandKin(ms)
+    h = 1e-4
+    worst = 0.0
+    for q in hk.random_poses(5, seed=1).astype(np.float64):
+        J = hk.jacobian(q)
+        for j in range(NJ):
+            dq = np.zeros(NJ)
+            dq[j] = h
+            pp, Rp, _, _ = hk.body_frames(q + dq)
+            pm, Rm, _, _ = hk.body_frames(q - dq)
+            p0, R0, _, _ = hk.body_frames(q)
+            lin = (pp - pm) / (2 * h)
+            W = np.einsum("bik,bjk->bij", (Rp - Rm) / (2 * h), R0)          # dR/dq R^T = [w]x
+            ang = np.stack([W[:, 2, 1], W[:, 0, 2], W[:, 1, 0]], axis=1)
+            worst = max(worst, float(np.abs(J[:, 0:3, j] - lin).max()), float(np.abs(J[:, 3:6, j] - ang).max()))
+    print(f"reference Jacobian against central differences of fk: {worst:.3g}")
+    assert worst <= 1e-7
+
+
+def test_reference_roundoff():
+    """The measurement the GPU tolerances rest on.  Measured over these 300 poses: e_M = 1.99e-5, e_g = 8.7e-7, e_J = 2.2e-7.
+    e_M is the maximum of a long-tailed distribution (per pose: median 6e-6, 95 % below 1.5e-5; the momentum-form CRBA of the
+    oracle takes moments about the world origin, and the worst poses have the slides near +-1 m): over six other seeds of 300 poses
+    it came out between 1.9e-5 and 3.5e-5.  The GPU tests recompute it on their own 70 poses."""
+    sc, ms = _setup(1)
+    hk = kr.HandKin(ms)
+    o32, o64 = kr.oracle_pair(sc, ms)
+    q = hk.random_poses(300, seed=3)
+    M32, g32 = kr.mass_gravity(o32, q)
+    M64, g64 = kr.mass_gravity(o64, q)
+    e_M, e_g = kr.err_M(M32, M64), kr.err_g(g32, g64, M64)
+    e_J = max(float(np.abs(hk.jacobian(x, np.float32).astype(np.float64) - hk.jacobian(x.astype(np.float64))).max()) for x in q)
+    print(f"reference roundoff over {len(q)} poses: e_M = {e_M:.3g}, e_g = {e_g:.3g}, e_J = {e_J:.3g}")
+    assert 4 * e_M <= 1e-4 and 4 * e_g <= 1e-5
+    assert abs(g64[:, 2] - 5.17).max() < 0.01                                  # the z slide carries the hand's weight
+
+
+def _stub_core(sim_cfg, model_struct, device="cpu"):
+    """Just enough of a core for DexHandEnv's own argument checks: records the calls, computes nothing."""
+    from oracle.py_backend import OracleCore
+
+    class Stub(OracleCore):
+        calls = []
+
+        def body_jacobian(self, out, env_ids=None, q=None, bodies=None):
+            self.calls.append(("jac", tuple(out.shape), bodies))
+
+        def mass_matrix(self, mass=None, gravity=None, env_ids=None, q=None):
+            self.calls.append(("mass", None if mass is None else tuple(mass.shape), None if gravity is None else tuple(gravity.shape)))
+    return Stub(sim_cfg, model_struct, device)
+
+
+def test_env_argument_validation():
+    import torch
+    from dexrobot_isaac_amd import make_env
+    from oracle.py_backend import OracleCore
+    env = make_env("BaseTask", 3, "cpu", "cpu", 0, _core_factory=_stub_core)
+    with pytest.raises(ValueError, match="unknown body"):
+        env.get_jacobian(bodies=["r_f_link9_tip"])
+    with pytest.raises(ValueError, match="body index"):
+        env.get_jacobian(bodies=[NB])
+    with pytest.raises(ValueError, match="shape"):
+        env.get_jacobian(q=torch.zeros(4, NJ - 1))
+    with pytest.raises(ValueError, match="shape"):
+        env.get_mass_matrix(q=torch.zeros(4, NJ - 1))
+    with pytest.raises(ValueError, match="out"):
+        env.get_mass_matrix(out=torch.zeros(3, NJ))
+    assert not env._core.calls                                                 # nothing reached the core
+    assert env.get_jacobian(bodies=["r_f_link2_tip", 6]).shape == (3, 2, 6, NJ)
+    assert env._core.calls[-1] == ("jac", (3, 2, 6, NJ), [18, 6])
+    M, g = env.get_mass_matrix(q=torch.zeros(5, NJ), gravity=True)
+    assert M.shape == (5, NJ, NJ) and g.shape == (5, NJ)
+    plain = make_env("BaseTask", 2, "cpu", "cpu", 0, _core_factory=OracleCore)  # the CPU stand-in has no such tensors
+    for call in (plain.get_jacobian, plain.get_mass_matrix):
+        with pytest.raises(NotImplementedError):
+            call()
+
+
+# ------------------------------------------------------------------------------------------------- GPU helpers
+def _guarded(k, *tail):
+    """A NaN-filled (k, *tail) float32 device view between one leading and one trailing guard row."""
+    import torch
+    full = torch.full((k + 2,) + tail, float("nan"), dtype=torch.float32, device="cuda:0")
+    full[0], full[-1] = GUARD, GUARD
+    return full, full[1:-1]
+
+
+def _guards_ok(full):
+    import torch
+    torch.cuda.synchronize()
+    assert bool((full[0] == GUARD).all()) and bool((full[-1] == GUARD).all()), "a guard row was written"
+
+
+def gpu_jac(core, k, env_ids=None, q=None, bodies=None):
+    full, out = _guarded(k, NB if bodies is None else len(bodies), 6, NJ)
+    core.body_jacobian(out, env_ids=env_ids, q=q, bodies=bodies)
+    _guards_ok(full)
+    return out.cpu().numpy()
+
+
+def gpu_mass(core, k, env_ids=None, q=None, mass=True, gravity=True):
+    fm, M = _guarded(k, NJ, NJ) if mass else (None, None)
+    fg, g = _guarded(k, NJ) if gravity else (None, None)
+    core.mass_matrix(mass=M, gravity=g, env_ids=env_ids, q=q)
+    for f in (fm, fg):
+        if f is not None:
+            _guards_ok(f)
+    return (None if M is None else M.cpu().numpy()), (None if g is None else g.cpu().numpy())
+
+
+def pose_core(core, q, qd=None):
+    import torch
+    core.dof_state[:, :, 0] = torch.as_tensor(q, device=core.device)
+    core.dof_state[:, :, 1] = 0.0 if qd is None else torch.as_tensor(qd, device=core.device)
+    core.set_dof_state_indexed(torch.arange(core.N))
+    assert (core.field("q").t().cpu().numpy() == q).all()
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+def _case(ms, sc, seed):
+    """A posed core of N envs and, computed once, every reference the tests share."""
+    from dexrobot_isaac_amd.core import DexSimCore
+    hk = kr.HandKin(ms)
+    core = DexSimCore(sc, ms, "cuda:0")
+    core.reset()
+    q = hk.random_poses(N, seed)
+    pose_core(core, q)
+    o32, o64 = kr.oracle_pair(sc, ms)
+    M32, g32 = kr.mass_gravity(o32, q)
+    M64, g64 = kr.mass_gravity(o64, q)
+    J64 = np.stack([hk.jacobian(x.astype(np.float64)) for x in q])
+    return dict(core=core, hk=hk, q=q, J64=J64, M64=M64, g64=g64, e_M=kr.err_M(M32, M64), e_g=kr.err_g(g32, g64, M64), sc=sc)
+
+
+@pytest.fixture(scope="module")
+def posed():
+    sc, ms = _setup(N)
+    c = _case(ms, sc, seed=21)
+    c["jac"] = gpu_jac(c["core"], N)
+    c["M"], c["g"] = gpu_mass(c["core"], N)
+    return c
+
+
+def check_jacobian(c, jac, what):
+    assert not np.isnan(jac).any(), f"{what}: an element was not written"
+    err = float(np.abs(jac.astype(np.float64) - c["J64"]).max())
+    print(f"{what}: Jacobian max abs error {err:.3g}")
+    assert err <= 1e-5
+    assert (bits(jac[:, :, 3:6, 0:3]) == 0).all()                              # a slide turns nothing
+    assert (bits(jac[:, 0]) == 0).all()                                        # hand_mount: +0.0f everywhere
+    moving = np.zeros((NB, NJ), dtype=bool)
+    for b in range(NB):
+        moving[b, c["hk"].ancestors[c["hk"].body_parent[b]] if c["hk"].body_parent[b] >= 0 else []] = True
+    assert (bits(jac[:, ~moving.reshape(NB, 1, NJ).repeat(6, 1)]) == 0).all()  # exact +0.0f wherever the joint does not move the body
+
+
+def check_mass(c, M, g, what):
+    assert not np.isnan(M).any() and not np.isnan(g).any(), f"{what}: an element was not written"
+    E_M, E_g = kr.err_M(M, c["M64"]), kr.err_g(g, c["g64"], c["M64"])
+    print(f"{what}: E_M = {E_M:.3g} (fp32 oracle e_M = {c['e_M']:.3g}), E_g = {E_g:.3g} (fp32 oracle e_g = {c['e_g']:.3g})")
+    assert E_M <= 4 * c["e_M"] and E_g <= 4 * c["e_g"]
+    assert (bits(M) == bits(M.transpose(0, 2, 1))).all()                       # one computed value for both triangles
+    for fa in range(5):
+        for fb in range(5):
+            if fa != fb:
+                assert (bits(M[:, 6 + 4 * fa: 10 + 4 * fa, 6 + 4 * fb: 10 + 4 * fb]) == 0).all()
+    assert (np.linalg.eigvalsh(M.astype(np.float64)) > 0).all()
+    assert (np.abs(g[:, 0:2]) <= 1e-6 * np.abs(g[:, 2:3])).all()               # gravity along z: no force on the x and y slides
+
+
+# ------------------------------------------------------------------------------------------------- GPU
+@pytest.mark.gpu
+def test_jacobian_against_float64_reference(posed):
+    check_jacobian(posed, posed["jac"], "default model")
+
+
+@pytest.mark.gpu
+def test_contract_with_published_body_states(posed):
+    import torch
+    c = posed
+    core, q = c["core"], c["q"]
+    rng = np.random.default_rng(5)
+    qd = rng.uniform(-1, 1, (N, NJ)).astype(np.float32)
+    pose_core(core, q, qd)
+    core.refresh_body_states()
+    torch.cuda.synchronize()
+    rbs = core.rigid_body_states[:, :NB].cpu().numpy().astype(np.float64)
+    jac = gpu_jac(core, N)
+    assert (bits(jac) == bits(c["jac"])).all()                                 # a function of q alone
+    twist = np.einsum("nbdj,nj->nbd", jac.astype(np.float64), qd.astype(np.float64))
+    err = np.abs(twist - rbs[:, :, 7:13]).max(axis=(1, 2))
+    bound = 2e-5 * np.abs(qd).sum(1)
+    print(f"jac @ qd against rigid_body_states[:, :, 7:13]: max error {err.max():.3g}, smallest bound {bound.min():.3g}")
+    assert (err <= bound).all()
+    # A slide moves by 1e-2: finite difference of the published positions.  They are float32, so the difference resolves 1e-5 only
+    # where a coordinate's spacing is well below 1e-7: with the slides over their full +-1 m range the figure is one spacing of a
+    # coordinate in [1, 2) m over the step, 1.19e-7 / 1e-2 = 1.19e-5 (measured: 5.96e-6 and 1.19e-5 for slides 0 and 1), which
+    # is the test's own resolution, not the kernel's error.  This part therefore brings the hand to within 0.5 m of the origin
+    # (slides scaled to +-0.25 m, z around -0.5 m under the 0.5 m spawn height; spacing <= 3e-8); rotations and fingers keep
+    # their full range, and a slide's column does not depend on where the hand is.
+    qn = q.copy()
+    qn[:, 0:2] = np.float32(0.25) * q[:, 0:2]
+    qn[:, 2] = np.float32(-0.5) + np.float32(0.25) * q[:, 2]
+    pose_core(core, qn, qd)
+    core.refresh_body_states()
+    torch.cuda.synchronize()
+    pos = core.rigid_body_states[:, :NB, 0:3].cpu().numpy().astype(np.float64)
+    jn = gpu_jac(core, N)
+    for j in range(3):
+        q2 = qn.copy()
+        q2[:, j] += np.float32(1e-2)
+        step = q2[:, j].astype(np.float64) - qn[:, j].astype(np.float64)      # what the slide really moved by, in float32
+        pose_core(core, q2, qd)
+        core.refresh_body_states()
+        torch.cuda.synchronize()
+        pos2 = core.rigid_body_states[:, :NB, 0:3].cpu().numpy().astype(np.float64)
+        moved = pos2 != pos                                                    # (hand_mount and the links under this slide stay put)
+        assert moved.any() and max(np.abs(pos[moved]).max(), np.abs(pos2[moved]).max()) < 0.5
+        fd = (pos2 - pos) / step[:, None, None]
+        e = float(np.abs(fd - jn[:, :, 0:3, j]).max())
+        print(f"slide {j}: Jacobian column against the finite difference of published positions: {e:.3g}")
+        assert e <= 1e-5
+    pose_core(core, q)                                                         # back to the shared state of the module
+
+
+@pytest.mark.gpu
+def test_mass_matrix_and_gravity_against_fp64_oracle(posed):
+    check_mass(posed, posed["M"], posed["g"], "default model")
+    assert abs(posed["g"][:, 2] - 5.17).max() < 0.01
+
+
+@pytest.mark.gpu
+def test_different_model():
+    """Per-joint scaled offsets, centres of mass and masses, finger links with off-diagonal inertia: no constant of the default
+    model is baked in, and the diagonal-inertia shortcut of the step path is not taken."""
+    sc, ms = _setup(N)
+    rng = np.random.default_rng(8)
+    for j in range(NJ):
+        fp, fc, fm = rng.uniform(0.7, 1.4, 3)
+        for i in range(3):
+            ms.jpoff[j][i] *= fp
+            ms.com[j][i] *= fc
+        ms.mass[j] *= fm
+        if j >= 6:                                                             # [[1, .3, -.2], [.3, 1, .25], [-.2, .25, 1]] is positive definite
+            a, b, d = ms.inertia[j][0], ms.inertia[j][1], ms.inertia[j][2]
+            ms.inertia[j][3], ms.inertia[j][4], ms.inertia[j][5] = 0.3 * (a * b) ** 0.5, -0.2 * (a * d) ** 0.5, 0.25 * (b * d) ** 0.5
+    c = _case(ms, sc, seed=22)
+    check_jacobian(c, gpu_jac(c["core"], N), "scaled model")
+    check_mass(c, *gpu_mass(c["core"], N), "scaled model")
+    c["core"].close()
+
+
+@pytest.mark.gpu
+def test_addressing(posed):
+    import torch
+    c = posed
+    core, q = c["core"], c["q"]
+    ids = [69, 0, 64, 3, 63]
+    jac = gpu_jac(core, len(ids), env_ids=ids)
+    M, g = gpu_mass(core, len(ids), env_ids=ids)
+    assert (bits(jac) == bits(c["jac"][ids])).all() and (bits(M) == bits(c["M"][ids])).all() and (bits(g) == bits(c["g"][ids])).all()
+    assert (bits(gpu_jac(core, 1, env_ids=[37])) == bits(c["jac"][[37]])).all()                     # k = 1
+    M1, g1 = gpu_mass(core, 1, env_ids=[37])
+    assert (bits(M1) == bits(c["M"][[37]])).all() and (bits(g1) == bits(c["g"][[37]])).all()
+    sel = [36, 6, 12]                                                          # out of order
+    assert (bits(gpu_jac(core, N, bodies=sel)) == bits(c["jac"][:, sel])).all()
+    assert (bits(gpu_jac(core, len(ids), env_ids=ids, bodies=sel)) == bits(c["jac"][ids][:, sel])).all()
+    Mo, _ = gpu_mass(core, N, gravity=False)                                   # each single NULL output leaves the other unchanged
+    _, go = gpu_mass(core, N, mass=False)
+    assert (bits(Mo) == bits(c["M"])).all() and (bits(go) == bits(c["g"])).all()
+    # q override, k = 130 (three workgroups): rows copied from env state are the state path's bits, the rest meet the reference
+    extra = c["hk"].random_poses(130 - N, seed=23)
+    qo = np.concatenate([q[:40], extra, q[40:]])
+    src = np.concatenate([np.arange(40), np.full(len(extra), -1), np.arange(40, N)])
+    qt = torch.as_tensor(qo, device=core.device)
+    jo = gpu_jac(core, 130, q=qt, env_ids=[-1])                                # env_ids is ignored with an override
+    Mq, gq = gpu_mass(core, 130, q=qt)
+    st = src >= 0
+    assert (bits(jo[st]) == bits(c["jac"][src[st]])).all() and (bits(Mq[st]) == bits(c["M"][src[st]])).all()
+    assert (bits(gq[st]) == bits(c["g"][src[st]])).all()
+    o32, o64 = kr.oracle_pair(c["sc"], core.model)
+    M64, g64 = kr.mass_gravity(o64, extra)
+    M32, g32 = kr.mass_gravity(o32, extra)
+    ce = dict(c, J64=np.stack([c["hk"].jacobian(x.astype(np.float64)) for x in extra]), M64=M64, g64=g64,
+              e_M=kr.err_M(M32, M64), e_g=kr.err_g(g32, g64, M64))
+    check_jacobian(ce, jo[~st], "q override")
+    check_mass(ce, Mq[~st], gq[~st], "q override")
+    # ids outside [0, N) leave their rows as they are
+    bad = [5, -1, N, 69]
+    jb = gpu_jac(core, 4, env_ids=bad, bodies=sel)
+    Mb, gb = gpu_mass(core, 4, env_ids=bad)
+    assert np.isnan(jb[1:3]).all() and np.isnan(Mb[1:3]).all() and np.isnan(gb[1:3]).all()
+    assert (bits(jb[[0, 3]]) == bits(c["jac"][[5, 69]][:, sel])).all() and (bits(Mb[[0, 3]]) == bits(c["M"][[5, 69]])).all()
+    assert (bits(gb[[0, 3]]) == bits(c["g"][[5, 69]])).all()
+    # argument errors come back as DEXSIM_ERR_ARG, before any launch
+    lib, h = core.lib, core.h
+    out = torch.zeros(N, NB, 6, NJ, device=core.device)
+    p = C.c_void_p(out.data_ptr())
+    assert lib.dexsim_body_jacobian(h, None, 0, None, None, NB, p, None) == 1
+    assert lib.dexsim_body_jacobian(h, None, N - 1, None, None, NB, p, None) == 1            # all envs needs k == num_envs
+    assert lib.dexsim_body_jacobian(h, None, N, None, None, NB - 1, p, None) == 1            # all bodies needs nb == 37
+    assert lib.dexsim_body_jacobian(h, None, N, None, (C.c_int * 2)(3, NB), 2, p, None) == 1
+    assert lib.dexsim_body_jacobian(h, None, N, None, (C.c_int * 1)(3), 0, p, None) == 1
+    assert lib.dexsim_mass_matrix(h, None, N, None, None, None, None) == 1
+    assert b"mass and gravity" in lib.dexsim_last_error()
+
+
+def _snapshot(core):
+    import torch
+    torch.cuda.synchronize()
+    names = ("arena", "stats", "counters", "obs_buf", "rew_buf", "reset_buf", "episode_step_count", "episode_length", "dof_state",
+             "root_state", "full_dof_targets", "masks")
+    snap = {n: getattr(core, n).clone() for n in names}
+    snap["stamp"] = core.get_step_stamp()
+    return snap
+
+
+def _same(a, b):
+    import torch
+    return all((a[k] == b[k]) if k == "stamp" else torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
+
+
+@pytest.mark.gpu
+def test_purity():
+    import torch
+    from dexrobot_isaac_amd.core import DexSimCore
+    sc, ms = _setup(N)
+    core, twin = DexSimCore(sc, ms, "cuda:0"), DexSimCore(sc, ms, "cuda:0")
+    g = torch.Generator().manual_seed(4)
+    acts = [(2 * torch.rand(N, 18, generator=g) - 1).cuda() for _ in range(8)]
+    for c in (core, twin):
+        c.reset()
+        for a in acts[:3]:
+            c.step(a)
+    before = _snapshot(core)
+    j1 = gpu_jac(core, N)
+    gpu_jac(core, 3, env_ids=[69, 1, 64], bodies=[12, 18])
+    m1 = gpu_mass(core, N)
+    gpu_mass(core, 100, q=torch.rand(100, NJ, device="cuda:0"))
+    gpu_jac(core, 100, q=torch.rand(100, NJ, device="cuda:0"), bodies=[6])
+    j2, m2 = gpu_jac(core, N), gpu_mass(core, N)
+    assert _same(before, _snapshot(core))                                      # nothing of the instance changed
+    assert (bits(j1) == bits(j2)).all() and all((bits(x) == bits(y)).all() for x, y in zip(m1, m2))
+    for a in acts[3:]:
+        core.step(a)
+        twin.step(a)
+    assert _same(_snapshot(core), _snapshot(twin))                             # ... and the run continues like a twin that never called them
+    for c in (core, twin):
+        c.close()
+
+
+@pytest.mark.gpu
+def test_public_surface():
+    import torch
+    from dexrobot_isaac_amd import make_env
+    env = make_env("BlindGrasping", N, "cuda:0", "cuda:0", 0)
+    env.reset()
+    tip = "r_f_link1_tip"
+    assert env.get_jacobian(bodies=[tip]).shape == (N, 1, 6, NJ)               # allocated by the call
+    full, out = _guarded(N, 1, 6, NJ)
+    J = env.get_jacobian(bodies=[tip], out=out)
+    _guards_ok(full)
+    assert J is out and not torch.isnan(J).any()
+    fM, oM = _guarded(N, NJ, NJ)
+    fg, og = _guarded(N, NJ)
+    M, g = env.get_mass_matrix(gravity=True, out=(oM, og))
+    _guards_ok(fM)
+    _guards_ok(fg)
+    assert M.shape == (N, NJ, NJ) and g.shape == (N, NJ) and not torch.isnan(M).any() and not torch.isnan(g).any()
+    assert torch.equal(env.get_mass_matrix(env_ids=[3, 1]), M[[3, 1]])
+    with pytest.raises(ValueError):
+        env.get_jacobian(bodies=["no_such_body"])
+    # one damped-least-squares step towards a 1 mm displacement of the fingertip, through the q override
+    q0 = env.dof_pos.clone()
+    full, out = _guarded(N, 1, 6, NJ)
+    Jq = env.get_jacobian(bodies=[tip], q=q0, out=out)
+    _guards_ok(full)
+    assert torch.equal(Jq, J)                                                  # the override at the current state: the state path's bits
+    Jl = Jq[:, 0, 0:3, :].double()
+    dx = torch.tensor([6e-4, -4.8e-4, 6.4e-4], dtype=torch.float64, device=Jl.device).expand(N, 3)      # |dx| = 1 mm
+    lam = 1e-4
+    A = Jl @ Jl.transpose(1, 2) + lam * torch.eye(3, dtype=torch.float64, device=Jl.device)
+    dq = (Jl.transpose(1, 2) @ torch.linalg.solve(A, dx.unsqueeze(2))).squeeze(2)
+    hk = kr.HandKin(env._model_struct)
+    b = env.model.body_names.index(tip)
+    q0n, dqn = q0.cpu().numpy().astype(np.float64), dq.cpu().numpy()
+    worst = 0.0
+    for e in range(0, N, 7):
+        moved = hk.body_frames(q0n[e] + dqn[e])[0][b] - hk.body_frames(q0n[e])[0][b]
+        worst = max(worst, float(np.linalg.norm(moved - dx[e].cpu().numpy())))
+    print(f"DLS step: the reference fingertip misses the 1 mm target displacement by {worst:.3g} m")
+    assert worst <= 0.05 * 1e-3
+    env.close()
