@@ -124,6 +124,14 @@ class DexSimCamera(C.Structure):
                 ("parent_joint", i32), ("eye", f32 * 3), ("target", f32 * 3)]
 
 
+IK_MAX_ITERS = 64   # DEXSIM_IK_MAX_ITERS
+
+
+class DexSimIK(C.Structure):
+    _fields_ = [("sites", i32), ("frame", i32), ("free_mask", u32), ("iters", i32), ("damping", f32), ("max_step", f32),
+                ("weight", f32 * NFINGER)]
+
+
 # every symbol include/dexsim.h declares (checked by tests/test_abi.py against the built library)
 EXPORTED_SYMBOLS = [
     "dexsim_struct_sizes", "dexsim_arena_layout", "dexsim_obs_key_info", "dexsim_reward_term_name",
@@ -136,6 +144,7 @@ EXPORTED_SYMBOLS = [
     "dexsim_set_step_stamp",
     "dexsim_camera_struct_size", "dexsim_render_layout", "dexsim_render",
     "dexsim_body_jacobian", "dexsim_mass_matrix",
+    "dexsim_ik_struct_size", "dexsim_solve_ik",
 ]
 
 
@@ -181,6 +190,8 @@ def declare_prototypes(lib):
     lib.dexsim_render.argtypes = [vp, P(DexSimCamera), vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.dexsim_body_jacobian.argtypes = [vp, vp, i32, vp, P(i32), i32, vp, vp]
     lib.dexsim_mass_matrix.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    lib.dexsim_ik_struct_size.argtypes = [P(sz)]
+    lib.dexsim_solve_ik.argtypes = [vp, vp, i32, vp, vp, P(DexSimIK), vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = i32
     lib.dexsim_error_string.argtypes = [i32]
@@ -200,3 +211,7 @@ def check_struct_sizes(lib):
     lib.dexsim_camera_struct_size(C.byref(cam))
     if cam.value != C.sizeof(DexSimCamera):
         raise RuntimeError(f"dexsim ABI mismatch: DexSimCamera is {cam.value} bytes in the library, {C.sizeof(DexSimCamera)} in python")
+    ik = C.c_size_t(0)
+    lib.dexsim_ik_struct_size(C.byref(ik))
+    if ik.value != C.sizeof(DexSimIK):
+        raise RuntimeError(f"dexsim ABI mismatch: DexSimIK is {ik.value} bytes in the library, {C.sizeof(DexSimIK)} in python")

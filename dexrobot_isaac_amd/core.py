@@ -414,3 +414,26 @@ class DexSimCore:
         mp = None if mass is None else self._kin_out("mass_matrix", "mass", mass, (k, _abi.NJ, _abi.NJ))
         gp = None if gravity is None else self._kin_out("mass_matrix", "gravity", gravity, (k, _abi.NJ))
         check(self.lib.dexsim_mass_matrix(self.h, ids, k, qp, mp, gp, self._stream()), "mass_matrix")
+
+    # ------------------------------------------------------------------ fingertip inverse kinematics
+    def solve_ik(self, targets, controls, env_ids=None, q=None, sites=0, frame=0, free_mask=0x3FFC0, weights=(1, 1, 1, 1, 1),
+                 iters=16, damping=1e-3, max_step=0.5, q_out=None, residual=None):
+        """Damped-least-squares IK of the five fingertip (sites=0) or fingerpad (sites=1) positions in control space, all `iters`
+        iterations in one launch: `targets` (k, 5, 3) f32 in the world (frame=0) or hand (frame=1) frame -> `controls` (k, 18) f32,
+        the 18 active targets of the action stage; optionally `q_out` (k, 26) = the coupled joint positions and `residual` (k, 5)
+        = |target - site| per finger.  Bit c of free_mask: control c is an unknown.  Rows as for body_jacobian: env_ids (None =
+        all envs) start from their current q, the rows of a (k, 26) `q` override from that.  dexsim_solve_ik."""
+        ids, qp, k = self._kin_rows("solve_ik", env_ids, q)
+        prm = _abi.DexSimIK()
+        prm.sites, prm.frame, prm.free_mask, prm.iters = int(sites), int(frame), int(free_mask), int(iters)
+        prm.damping, prm.max_step = float(damping), float(max_step)
+        w = [float(x) for x in weights]
+        if len(w) != _abi.NFINGER:
+            raise DexSimError(f"solve_ik: {_abi.NFINGER} weights, got {len(w)}")
+        prm.weight[:] = w
+        tp = self._kin_out("solve_ik", "targets", targets, (k, _abi.NFINGER, 3))
+        cp = self._kin_out("solve_ik", "controls", controls, (k, _abi.NACT))
+        qo = None if q_out is None else self._kin_out("solve_ik", "q_out", q_out, (k, _abi.NJ))
+        rp = None if residual is None else self._kin_out("solve_ik", "residual", residual, (k, _abi.NFINGER))
+        self._keep_ik = targets                     # alive until the kernel ran
+        check(self.lib.dexsim_solve_ik(self.h, ids, k, qp, tp, C.byref(prm), cp, qo, rp, self._stream()), "solve_ik")

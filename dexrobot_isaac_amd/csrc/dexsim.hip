@@ -871,3 +871,48 @@ extern "C" int dexsim_mass_matrix(dexsim_t h, const int64_t* env_ids, int k, con
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------- fingertip inverse kinematics
+// Behind every use of the step kernels, like the kernels above.
+// clang-format off
+#include "dexsim_ik.hip.inc"
+// clang-format on
+
+extern "C" int dexsim_ik_struct_size(size_t* out) {
+  if (!out) return fail(DEXSIM_ERR_ARG, "dexsim_ik_struct_size: null argument");
+  *out = sizeof(DexSimIK);
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_solve_ik(dexsim_t h, const int64_t* env_ids, int k, const float* q0, const float* targets, const DexSimIK* prm,
+                               float* controls, float* q_out, float* residual, void* stream) {
+  // the parameter checks need neither a handle nor a device
+  if (!targets || !controls || !prm) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: targets, controls and prm are required");
+  if (prm->sites < 0 || prm->sites > 1) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: sites must be 0 (fingertips) or 1 (fingerpads)");
+  if (prm->frame < 0 || prm->frame > 1) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: frame must be 0 (world) or 1 (hand)");
+  if (prm->free_mask == 0 || (prm->free_mask >> DEXSIM_NACT) != 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: free_mask must have at least one of its bits 0..17 set and none above");
+  if (prm->frame == 1 && (prm->free_mask & 63u) != 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: hand-frame targets (frame 1) need the base controls 0..5 fixed");
+  if (prm->iters < 1 || prm->iters > DEXSIM_IK_MAX_ITERS) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: iters must be in [1, DEXSIM_IK_MAX_ITERS]");
+  if (!(prm->damping > 0.f) || !std::isfinite(prm->damping)) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: damping must be positive");
+  if (!(prm->max_step > 0.f) || !std::isfinite(prm->max_step)) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: max_step must be positive");
+  float wsum = 0.f;
+  for (int f = 0; f < DEXSIM_NFINGER; f++) {
+    if (!(prm->weight[f] >= 0.f) || !std::isfinite(prm->weight[f])) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: a weight is negative");
+    wsum += prm->weight[f];
+  }
+  if (!(wsum > 0.f)) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: the weights are all zero");
+  if (k <= 0) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: k must be positive");
+  IkArgs K;
+  std::memset(&K, 0, sizeof K);
+  int rc = kin_rows("dexsim_solve_ik", h, env_ids, k, q0, &K.rows);
+  if (rc) return rc;
+  NEED_BOUND(h);
+  K.targets = targets; K.controls = controls; K.q_out = q_out; K.residual = residual;
+  K.prm = *prm; K.lam2 = prm->damping * prm->damping;
+  DeviceGuard guard(h->device);
+  k_ik_solve<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}

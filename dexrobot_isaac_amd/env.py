@@ -878,6 +878,89 @@ class DexHandEnv:
         core.mass_matrix(mass=M, env_ids=ids, q=q)
         return M
 
+    # ------------------------------------------------------------------ fingertip inverse kinematics
+    @property
+    def control_names(self):
+        """Names of the 18 active targets in their order: the six base joints, then the first DOF of each finger control's
+        coupling group (FINGER_COUPLING_MAP)."""
+        return list(self.model.dof_names[:6]) + [FINGER_COUPLING_MAP[c][0][0] for c in range(12)]
+
+    def solve_fingertip_ik(self, targets, env_ids=None, q=None, sites="tips", frame="world", free="fingers", weights=None,
+                           iters=16, damping=1e-3, max_step=0.5, return_info=False):
+        """Batched inverse kinematics for the five fingertips in control space, every iteration inside one kernel launch.
+        targets (k, 5, 3): wanted positions of the fingertip sites (sites="tips") or fingerpad sites (sites="pads"), thumb to
+        pinky, in the env's world frame (frame="world", as obs_dict["fingertip_poses_world"][..., :3]) or in the hand frame
+        (frame="hand", as fingertip_poses_hand / fingerpad_poses_hand; the base is then fixed).  Rows as for get_jacobian: the
+        envs `env_ids` (None = all) start from their current joint positions, the rows of a (k, 26) override `q` from that.
+        free: the controls that may move -- "fingers" (controls 6..17), "all", or a list of indices / names (control_names, or
+        the hardware names "th_rot", "ff_spr", ...); the others keep their start value.  weights: five values >= 0, 0 drops a
+        finger from the objective (a thumb-index pinch: (1, 1, 0, 0, 0)).  Damped least squares with damping `damping`; no
+        control changes by more than `max_step` per iteration; the result respects the active limits.  Base slides (m) and base
+        rotations (rad) share the one damping.
+
+        Returns controls (k, 18): the 18 active targets the action stage works in.  Feed them back as the raw targets of a
+        custom action rule -- env.action_processor.set_action_rule(lambda prev, rule, actions, cfg: controls) -- or, for a
+        policy-style action in position mode, through the limit scaling: action = 2 (u - lower) / (upper - lower) - 1 on the
+        controls the policy drives.  With return_info=True: (controls, {"q": (k, 26) coupled joint positions, "residual": (k, 5)
+        distance left per finger, dropped fingers included})."""
+        what = "solve_fingertip_ik"
+        core = self._core
+        if not hasattr(core, "solve_ik"):
+            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no solve_ik()")
+        core, ids, q, k = self._kindyn_rows(what, env_ids, q)
+        if sites not in ("tips", "pads"):
+            raise ValueError(f"{what}: sites must be 'tips' or 'pads', got {sites!r}")
+        if frame not in ("world", "hand"):
+            raise ValueError(f"{what}: frame must be 'world' or 'hand', got {frame!r}")
+        names = self.control_names
+        hw = {n: names.index(dofs[0]) for n, dofs in HARDWARE_MAPPING}
+        if isinstance(free, str) and free in ("fingers", "all"):
+            idx = list(range(6, _abi.NACT)) if free == "fingers" else list(range(_abi.NACT))
+        else:
+            if isinstance(free, (str, int)):
+                free = [free]
+            idx = []
+            for c in free:
+                if isinstance(c, str):
+                    if c not in names and c not in hw:
+                        raise ValueError(f"{what}: free: unknown control '{c}' (controls: {names}, or {sorted(hw)})")
+                    c = names.index(c) if c in names else hw[c]
+                c = int(c)
+                if not 0 <= c < _abi.NACT:
+                    raise ValueError(f"{what}: free: control index must be in [0, {_abi.NACT}), got {c}")
+                idx.append(c)
+            if not idx:
+                raise ValueError(f"{what}: free: at least one control must be free")
+        mask = 0
+        for c in idx:
+            mask |= 1 << c
+        if frame == "hand" and mask & 63:
+            raise ValueError(f"{what}: free: hand-frame targets need the base controls 0..5 fixed")
+        w = [1.0] * _abi.NFINGER if weights is None else [float(x) for x in torch.as_tensor(weights, dtype=torch.float32).view(-1).tolist()]
+        if len(w) != _abi.NFINGER or not all(x >= 0.0 and x == x and x != float("inf") for x in w) or not any(x > 0.0 for x in w):
+            raise ValueError(f"{what}: weights must be {_abi.NFINGER} finite values >= 0, not all 0, got {w}")
+        iters = int(iters)
+        if not 1 <= iters <= _abi.IK_MAX_ITERS:
+            raise ValueError(f"{what}: iters must be in [1, {_abi.IK_MAX_ITERS}], got {iters}")
+        if not float(damping) > 0.0 or not float(max_step) > 0.0:
+            raise ValueError(f"{what}: damping and max_step must be positive, got {damping} and {max_step}")
+        targets = torch.as_tensor(targets, dtype=torch.float32, device=core.device)
+        if tuple(targets.shape) != (k, _abi.NFINGER, 3):
+            raise ValueError(f"{what}: targets must have shape ({k}, {_abi.NFINGER}, 3), got {tuple(targets.shape)}")
+        controls = torch.empty((k, _abi.NACT), dtype=torch.float32, device=core.device)
+        info = {}
+        if return_info:
+            info = {"q": torch.empty((k, _abi.NJ), dtype=torch.float32, device=core.device),
+                    "residual": torch.empty((k, _abi.NFINGER), dtype=torch.float32, device=core.device)}
+        if ids is not None:   # a row whose id is out of range is left as it is by the kernel: give it a defined value
+            controls.fill_(float("nan"))
+            for t in info.values():
+                t.fill_(float("nan"))
+        core.solve_ik(targets.contiguous(), controls, env_ids=ids, q=q, sites=0 if sites == "tips" else 1,
+                      frame=0 if frame == "world" else 1, free_mask=mask, weights=w, iters=iters, damping=float(damping),
+                      max_step=float(max_step), q_out=info.get("q"), residual=info.get("residual"))
+        return (controls, info) if return_info else controls
+
     def close(self):
         if self._core is not None:
             self._core.close()

@@ -615,6 +615,51 @@ int dexsim_body_jacobian(dexsim_t h, const int64_t* env_ids, int k, const float*
                          void* stream);
 int dexsim_mass_matrix(dexsim_t h, const int64_t* env_ids, int k, const float* q, float* mass, float* gravity, void* stream);
 
+/* ------------------------------------------------------------------ fingertip inverse kinematics in control space
+ * Batched damped-least-squares IK for the five fingertip (or fingerpad) POSITIONS, solved for the 18 active targets of the action
+ * stage (the controls of DexSimConfig::active_lower / active_upper, coupled to the 26 DOFs as the action stage couples them), every
+ * iteration inside one launch.  The call is stream-ordered, never synchronises and allocates nothing, and writes no arena word,
+ * API tensor, statistics word, counter or the step stamp.  ROWS and the q0 OVERRIDE are those of dexsim_body_jacobian: row i is env
+ * env_ids[i] (NULL: env i, k == num_envs) and starts from its current q; with q0 != NULL, a device (k, 26) array, row i starts
+ * from q0[i] and env_ids is ignored.  A row whose id is outside [0, num_envs) leaves its output rows untouched.
+ *
+ * THE ITERATION.  q(u): DOF d = sum over the controls of scale * u_c (thumb DIP, finger DIPs: two DOFs per control; control 9
+ * spreads index, ring and, twice as far, pinky); DOF 14, driven by no control, is 0.  Start: u0_c = clamp(q0[first DOF of control
+ * c's group], active_lower[c], active_upper[c]) -- a q0 off the coupling manifold is projected onto it this way, for fixed controls
+ * too.  p_f(u): world position of finger f's site (site_parent, site_p).  With frame == 1 the targets are mapped to world once,
+ * through the pose of site 0 at u0; the base is fixed in that mode.  Per iteration, with F the free controls and J_f the
+ * 3 x |F| Jacobian of p_f with respect to u:
+ *     A = sum_f w_f J_f^T J_f + lambda^2 I,   b = sum_f w_f J_f^T (t_f - p_f)     (fingers summed in the order f = 0..4)
+ *     delta = A^-1 b  (Cholesky, no pivoting),   s = min(1, max_step / max_c |delta_c|),
+ *     u_F <- clamp(u_F + s delta, active_lower, active_upper).
+ * After `iters` iterations: controls = u, q_out = q(u), residual[f] = |t_f - p_f(u)| (unweighted, all five fingers, those with
+ * weight 0 included).  A row's result depends on that row alone and is reproducible bit for bit.
+ * UNITS.  The base slides (controls 0-2, metres) and base rotations (3-5, radians) share the one lambda and the one max_step with
+ * the finger controls (radians): with the base free, lambda damps a metre of slide as much as a radian of rotation.
+ *
+ * targets (k, 5, 3) f32; controls (k, 18) f32, required; q_out (k, 26) f32 or NULL; residual (k, 5) f32 or NULL.
+ * The controls are what the action stage consumes: DexSimBuffers::raw_targets (custom action rule), or, through
+ * action = 2 (u - lower) / (upper - lower) - 1, a policy-style action in DEXSIM_MODE_POSITION.
+ *
+ * DEXSIM_ERR_ARG (with a dexsim_last_error text; no device needed): NULL targets, controls or prm; sites or frame outside {0, 1};
+ * free_mask == 0 or a bit at position 18 or above; frame == 1 with a base bit (0..5) set; iters outside [1, DEXSIM_IK_MAX_ITERS];
+ * damping or max_step not positive; a negative or all-zero weight; a NULL handle; k <= 0; env_ids == NULL without q0 and
+ * k != num_envs.  DEXSIM_ERR_NOT_BOUND before dexsim_bind. */
+#define DEXSIM_IK_MAX_ITERS 64
+typedef struct DexSimIK {
+  int      sites;        /* 0 = fingertip sites (DexHandModel sites 1..5), 1 = fingerpad sites (6..10) */
+  int      frame;        /* 0 = targets in the env's world frame, 1 = in the hand frame: the pose of site 0 (right_hand_base),
+                            the frame of the obs keys fingertip_poses_hand / fingerpad_poses_hand */
+  uint32_t free_mask;    /* bit c set: control c (0..17, order of active_lower) is an unknown; others keep their start value */
+  int      iters;        /* [1, DEXSIM_IK_MAX_ITERS] */
+  float    damping;      /* lambda > 0 */
+  float    max_step;     /* > 0: largest |change| of any control in one iteration */
+  float    weight[5];    /* >= 0 per finger, not all 0; 0 drops the finger from the objective */
+} DexSimIK;
+int dexsim_ik_struct_size(size_t* out);
+int dexsim_solve_ik(dexsim_t h, const int64_t* env_ids, int k, const float* q0, const float* targets, const DexSimIK* prm,
+                    float* controls, float* q_out, float* residual, void* stream);
+
 const char* dexsim_error_string(int code);
 const char* dexsim_last_error(void);
 

@@ -1,0 +1,488 @@
+"""Fingertip inverse kinematics in control space on the device (dexsim_solve_ik, env.solve_fingertip_ik) against tests/ik_ref.py, a
+numpy statement of the iteration include/dexsim.h specifies, run in float64 and, for the roundoff figures, in float32.
+
+Test poses (ik_ref.HandIK.test_poses, 70 rows from a fixed seed): start controls uniform in the active limits with the base slides in
++-0.3 m and the base rotations in +-1 rad; targets = forward kinematics of the start controls perturbed by pert * U(-1, 1) *
+min(range, 1) on the free controls, clamped -- reachable by construction.
+
+Tolerances:
+  * one iteration: 4 x the largest difference between the reference's own float32 and float64 steps on the same 70 rows (the test
+    recomputes it; about 4e-6 with the fingers free, 5e-5 with all 18 controls free).  The factor 4 is the project's allowance for a
+    different factorisation of the same fp32 arithmetic plus sincos_joint (tests/test_kindyn.py); the kernel eliminates the ten
+    private finger controls before the eight shared ones.  An index, sign, coupling-scale or summation bug is at least 1e-3.
+  * convergence (32 iterations, lambda = 1e-3): on every row where the float64 reference ends at <= 1e-6 m, the device controls,
+    re-evaluated by the float64 forward kinematics, leave <= 1e-5 m on the weighted fingers: 10 x the selection bar, above the fp32
+    floor test_reference_converges measures (below 1.4e-6 m).  At least 90 % of the rows must be selected.
+Every GPU test uses N = 70: two workgroups, six live lanes in the second.  Every device output sits between two guard rows that must
+come back untouched.
+
+Two of the header's DEXSIM_ERR_ARG cases need a live handle (env_ids == NULL with k != num_envs) and so does DEXSIM_ERR_NOT_BOUND:
+test_addressing_and_reproducibility checks them on the device; the others are checked without one.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from dexrobot_isaac_amd import _abi, _lib
+from dexrobot_isaac_amd.build import build_lib
+from dexrobot_isaac_amd.config import build_sim_config, default_cfg
+from tests import ik_ref as ir
+
+N = 70
+NJ, NACT, NF = _abi.NJ, _abi.NACT, _abi.NFINGER
+GUARD = -7.0
+SEED = 11
+
+
+def _setup(n, task="BlindGrasping"):
+    cfg = default_cfg(task)
+    cfg["env"]["numEnvs"] = n
+    sc, model = build_sim_config(cfg)
+    return sc, model.to_struct()
+
+
+def _prm(**kw):
+    p = _abi.DexSimIK()
+    p.sites, p.frame, p.free_mask, p.iters, p.damping, p.max_step = 0, 0, ir.FINGERS_FREE, 16, 1e-3, 0.5
+    p.weight[:] = [1.0] * NF
+    for k, v in kw.items():
+        if k == "weight":
+            p.weight[:] = v
+        else:
+            setattr(p, k, v)
+    return p
+
+
+# ------------------------------------------------------------------------------------------------- CPU
+@pytest.fixture(scope="module")
+def lib():
+    build_lib()
+    return _lib.load()
+
+
+def test_abi_exports_and_argument_errors(lib):
+    for name in ("dexsim_ik_struct_size", "dexsim_solve_ik"):
+        assert name in _abi.EXPORTED_SYMBOLS
+        assert hasattr(lib, name), f"libdexsim.so does not export {name}"
+    size = C.c_size_t(0)
+    assert lib.dexsim_ik_struct_size(C.byref(size)) == 0 and size.value == C.sizeof(_abi.DexSimIK)
+    assert lib.dexsim_ik_struct_size(None) == 1
+    buf = (C.c_float * 64)()
+    p = C.c_void_p(C.addressof(buf))                                           # never read: every call below fails before a launch
+
+    def call(prm, h=None, k=1, targets=p, controls=p):
+        rc = lib.dexsim_solve_ik(h, None, k, None, targets, None if prm is None else C.byref(prm), controls, None, None, None)
+        return rc, lib.dexsim_last_error()
+
+    inf, nan = float("inf"), float("nan")
+    cases = [
+        (dict(targets=None), b"required"), (dict(controls=None), b"required"), (dict(prm=None), b"required"),
+        (dict(prm=_prm(sites=2)), b"sites"), (dict(prm=_prm(sites=-1)), b"sites"),
+        (dict(prm=_prm(frame=2)), b"frame"), (dict(prm=_prm(frame=-1)), b"frame"),
+        (dict(prm=_prm(free_mask=0)), b"free_mask"), (dict(prm=_prm(free_mask=1 << NACT)), b"free_mask"),
+        (dict(prm=_prm(frame=1, free_mask=ir.FINGERS_FREE | 1)), b"base controls"),
+        (dict(prm=_prm(frame=1, free_mask=ir.ALL_FREE)), b"base controls"),
+        (dict(prm=_prm(iters=0)), b"iters"), (dict(prm=_prm(iters=_abi.IK_MAX_ITERS + 1)), b"iters"),
+        (dict(prm=_prm(damping=0.0)), b"damping"), (dict(prm=_prm(damping=-1e-3)), b"damping"), (dict(prm=_prm(damping=nan)), b"damping"),
+        (dict(prm=_prm(max_step=0.0)), b"max_step"), (dict(prm=_prm(max_step=-0.5)), b"max_step"), (dict(prm=_prm(max_step=inf)), b"max_step"),
+        (dict(prm=_prm(weight=[1, 1, -1, 1, 1])), b"weight"), (dict(prm=_prm(weight=[0, 0, 0, 0, 0])), b"weights are all zero"),
+        (dict(prm=_prm(weight=[1, nan, 1, 1, 1])), b"weight"),
+        (dict(prm=_prm(), k=0), b"k must be positive"), (dict(prm=_prm(), k=-3), b"k must be positive"),
+        (dict(prm=_prm()), b"null handle"),
+    ]
+    for kw, text in cases:
+        kw.setdefault("prm", _prm())
+        rc, msg = call(**kw)
+        assert rc == 1 and text in msg, (kw, rc, msg)                          # DEXSIM_ERR_ARG with its text
+    assert _abi.IK_MAX_ITERS == 64
+
+
+def _stub_core(sim_cfg, model_struct, device="cpu"):
+    """Just enough of a core for DexHandEnv's own argument checks: records the calls, computes nothing."""
+    from oracle.py_backend import OracleCore
+
+    class Stub(OracleCore):
+        calls = []
+
+        def body_jacobian(self, out, env_ids=None, q=None, bodies=None):
+            pass
+
+        def solve_ik(self, targets, controls, **kw):
+            self.calls.append((tuple(targets.shape), tuple(controls.shape), kw))
+    return Stub(sim_cfg, model_struct, device)
+
+
+def test_env_argument_validation():
+    import torch
+    from dexrobot_isaac_amd import make_env
+    from oracle.py_backend import OracleCore
+    env = make_env("BaseTask", 3, "cpu", "cpu", 0, _core_factory=_stub_core)
+    t = torch.zeros(3, NF, 3)
+    bad = [
+        (dict(targets=torch.zeros(3, NF, 2)), "shape"), (dict(targets=torch.zeros(2, NF, 3)), "shape"),
+        (dict(targets=torch.zeros(4, NF, 3), q=torch.zeros(4, NJ - 1)), "shape"),
+        (dict(targets=t, sites="knuckles"), "sites"), (dict(targets=t, frame="palm"), "frame"),
+        (dict(targets=t, free="thumb"), "unknown control"), (dict(targets=t, free=[NACT]), "control index"),
+        (dict(targets=t, free=[-1]), "control index"), (dict(targets=t, free=[]), "at least one"),
+        (dict(targets=t, frame="hand", free="all"), "base controls"), (dict(targets=t, frame="hand", free=["ARTx", 7]), "base controls"),
+        (dict(targets=t, weights=[1, 1, 1, 1]), "weights"), (dict(targets=t, weights=[1, 1, -1, 1, 1]), "weights"),
+        (dict(targets=t, weights=[0, 0, 0, 0, 0]), "weights"),
+        (dict(targets=t, iters=0), "iters"), (dict(targets=t, iters=65), "iters"),
+        (dict(targets=t, damping=0.0), "positive"), (dict(targets=t, max_step=-1.0), "positive"),
+        (dict(targets=t, env_ids=[]), "empty"),
+    ]
+    for kw, text in bad:
+        with pytest.raises(ValueError, match=text):
+            env.solve_fingertip_ik(**kw)
+    assert not env._core.calls                                                 # nothing reached the core
+    assert len(env.control_names) == NACT and env.control_names[9] == "r_f_joint2_1"
+    u = env.solve_fingertip_ik(t)
+    assert u.shape == (3, NACT)
+    shape_t, shape_c, kw = env._core.calls[-1]
+    assert shape_t == (3, NF, 3) and shape_c == (3, NACT) and kw["free_mask"] == ir.FINGERS_FREE and kw["sites"] == 0 and kw["frame"] == 0
+    assert kw["iters"] == 16 and kw["q_out"] is None and kw["residual"] is None
+    u, info = env.solve_fingertip_ik(torch.zeros(2, NF, 3), env_ids=[2, 0], sites="pads", frame="hand", free=["r_f_joint2_1", "th_rot", 17],
+                                     weights=(1, 1, 0, 0, 0), return_info=True)
+    kw = env._core.calls[-1][2]
+    assert kw["free_mask"] == (1 << 9) | (1 << 6) | (1 << 17) and kw["sites"] == 1 and kw["frame"] == 1 and kw["weights"] == [1, 1, 0, 0, 0]
+    assert info["q"].shape == (2, NJ) and info["residual"].shape == (2, NF)
+    assert env.solve_fingertip_ik(torch.zeros(5, NF, 3), q=torch.zeros(5, NJ), free="all").shape == (5, NACT)
+    assert env._core.calls[-1][2]["free_mask"] == ir.ALL_FREE
+    plain = make_env("BaseTask", 2, "cpu", "cpu", 0, _core_factory=OracleCore)  # the CPU stand-in has no IK
+    with pytest.raises(NotImplementedError):
+        plain.solve_fingertip_ik(torch.zeros(2, NF, 3))
+
+
+@pytest.fixture(scope="module")
+def hk():
+    sc, ms = _setup(N)
+    return ir.HandIK(ms, sc)
+
+
+def test_batched_fk_is_render_refs_fk(hk):
+    """ik_ref evaluates all rows at once; its joint-by-joint formula is HandGeometry.fk's, held here to the last bits."""
+    _, q0, _ = hk.test_poses(6, seed=2)
+    o, R = hk.fk(q0.astype(np.float64))
+    for i in range(len(q0)):
+        o1, R1 = hk.geom.fk(q0[i].astype(np.float64))
+        assert np.abs(o[i] - o1).max() <= 1e-15 and np.abs(R[i] - R1).max() <= 1e-15
+    assert (hk.q_of_u(hk.u0_of_q(q0, np.float32), np.float32) == q0).all()      # the poses are on the coupling manifold
+    assert (q0[:, ir.HELD_DOF] == 0).all()
+
+
+def test_reference_jacobian_is_the_derivative_of_fk(hk):
+    u = hk.test_poses(5, seed=1)[0].astype(np.float64)
+    h = 1e-4
+    worst = 0.0
+    for sites in (0, 1):
+        J, _ = hk.jacobian(u, sites)
+        for c in range(NACT):
+            d = np.zeros(NACT)
+            d[c] = h
+            fd = (hk.site_pos(u + d, sites) - hk.site_pos(u - d, sites)) / (2 * h)
+            worst = max(worst, float(np.abs(fd - J[:, :, :, c]).max()))
+    print(f"control-space Jacobian against central differences of the forward kinematics: {worst:.3g}")
+    assert worst <= 1e-7
+
+
+CONV = dict(tips=(0, (1, 1, 1, 1, 1)), pads=(1, (1, 1, 1, 1, 1)), pinch=(0, (1, 1, 0, 0, 0)))
+
+
+def _conv_reference(hk, name):
+    """The float64 reference of a convergence case: poses, result and the rows it converged on."""
+    sites, w = CONV[name]
+    u0, q0, tg = hk.test_poses(N, SEED, sites=sites)
+    c64, _, r64 = hk.solve(q0, tg, sites=sites, iters=32, damping=1e-3, max_step=0.5, weight=w)
+    wm = np.array(w) > 0
+    return dict(sites=sites, w=w, wm=wm, u0=u0, q0=q0, tg=tg, c64=c64, sel=r64[:, wm].max(1) <= 1e-6)
+
+
+@pytest.mark.parametrize("name", list(CONV))
+def test_reference_converges(hk, name):
+    """The measurement the GPU bars rest on.  Measured over seeds 11 and 12, for the three cases: the float64 reference reaches a
+    worst-finger residual <= 1e-6 m on 98.6 - 100 % of the 70 rows; on those rows its float32 evaluation, re-evaluated in
+    float64, leaves at most 7e-7 m."""
+    r = _conv_reference(hk, name)
+    c32, _, _ = hk.solve(r["q0"], r["tg"], sites=r["sites"], iters=32, damping=1e-3, max_step=0.5, weight=r["w"], dtype=np.float32)
+    assert c32.dtype == np.float32
+    left = hk.residual64(r["u0"], c32, r["tg"], sites=r["sites"])[r["sel"]][:, r["wm"]].max()
+    print(f"{name}: float64 reference converged on {r['sel'].mean():.3f} of {N} rows; its float32 evaluation leaves {left:.3g} m there")
+    assert r["sel"].mean() >= 0.9
+    assert left <= 1.4e-6
+
+
+# ------------------------------------------------------------------------------------------------- GPU helpers
+def _guarded(k, *tail):
+    """A NaN-filled (k, *tail) float32 device view between one leading and one trailing guard row."""
+    import torch
+    full = torch.full((k + 2,) + tail, float("nan"), dtype=torch.float32, device="cuda:0")
+    full[0], full[-1] = GUARD, GUARD
+    return full, full[1:-1]
+
+
+def gpu_ik(core, k, targets, env_ids=None, q=None, want=("q", "residual"), **prm):
+    """core.solve_ik into guarded outputs: dict of numpy arrays controls (k, 18), q (k, 26), residual (k, 5)."""
+    import torch
+    fc, c = _guarded(k, NACT)
+    fq, qo = _guarded(k, NJ) if "q" in want else (None, None)
+    fr, r = _guarded(k, NF) if "residual" in want else (None, None)
+    t = torch.as_tensor(np.ascontiguousarray(targets, dtype=np.float32), device=core.device)
+    if q is not None:
+        q = torch.as_tensor(np.ascontiguousarray(q, dtype=np.float32), device=core.device)
+    core.solve_ik(t, c, env_ids=env_ids, q=q, q_out=qo, residual=r, **prm)
+    torch.cuda.synchronize()
+    for f in (fc, fq, fr):
+        if f is not None:
+            assert bool((f[0] == GUARD).all()) and bool((f[-1] == GUARD).all()), "a guard row was written"
+    return dict(controls=c.cpu().numpy(), q=None if qo is None else qo.cpu().numpy(), residual=None if r is None else r.cpu().numpy())
+
+
+def pose_core(core, q):
+    import torch
+    core.dof_state[:, :, 0] = torch.as_tensor(q, device=core.device)
+    core.dof_state[:, :, 1] = 0.0
+    core.set_dof_state_indexed(torch.arange(core.N))
+    assert (core.field("q").t().cpu().numpy() == q).all()
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+@pytest.fixture(scope="module")
+def rig(hk):
+    """A core of N envs posed at the start poses of the seed (they do not depend on the case: only the targets do)."""
+    from dexrobot_isaac_amd.core import DexSimCore
+    sc, ms = _setup(N)
+    core = DexSimCore(sc, ms, "cuda:0")
+    core.reset()
+    u0, q0, _ = hk.test_poses(N, SEED)
+    pose_core(core, q0)
+    return dict(core=core, hk=hk, u0=u0, q0=q0, conv={})
+
+
+def _conv_gpu(rig, name):
+    """Reference and device result of a convergence case, computed once and shared."""
+    if name not in rig["conv"]:
+        r = _conv_reference(rig["hk"], name)
+        assert (r["q0"] == rig["q0"]).all()
+        r["gpu"] = gpu_ik(rig["core"], N, r["tg"], sites=r["sites"], iters=32, damping=1e-3, max_step=0.5, weights=r["w"])
+        rig["conv"][name] = r
+    return rig["conv"][name]
+
+
+# ------------------------------------------------------------------------------------------------- GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,free,pert", [("fingers", ir.FINGERS_FREE, 0.3), ("all", ir.ALL_FREE, 0.1)])
+def test_one_iteration_against_reference(rig, name, free, pert):
+    hk, core = rig["hk"], rig["core"]
+    u0, q0, tg = hk.test_poses(N, SEED, free_mask=free, pert=pert)
+    assert (q0 == rig["q0"]).all()
+    kw = dict(free_mask=free, iters=1, damping=1e-2, max_step=0.5)
+    c64, q64, r64 = hk.solve(q0, tg, **kw)
+    c32, _, _ = hk.solve(q0, tg, dtype=np.float32, **kw)
+    e_ref = float(np.abs(c32.astype(np.float64) - c64).max())
+    out = gpu_ik(core, N, tg, **kw)
+    assert not any(np.isnan(v).any() for v in out.values()), "an element was not written"
+    err = float(np.abs((out["controls"].astype(np.float64) - u0) - (c64 - u0)).max())
+    print(f"{name} free, one iteration: device step off the float64 reference by {err:.3g} (reference float32 against float64: "
+          f"{e_ref:.3g}; largest step {np.abs(c64 - u0).max():.3g})")
+    assert np.abs(c64 - u0).max() > 0.05                                        # the step is there to be compared
+    assert err <= 4 * e_ref
+    # residual and q_out of that result
+    assert np.abs(out["residual"] - hk.residual64(u0, out["controls"], tg)).max() <= 1e-5
+    assert (out["q"] == hk.q_of_u(out["controls"], np.float32)).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CONV))
+def test_convergence(rig, name):
+    r = _conv_gpu(rig, name)
+    hk, out, sel, wm = rig["hk"], r["gpu"], r["sel"], r["wm"]
+    assert not any(np.isnan(v).any() for v in out.values()), "an element was not written"
+    left = hk.residual64(r["u0"], out["controls"], r["tg"], sites=r["sites"])   # float64 re-evaluation of the device controls
+    dres = float(np.abs(out["residual"][sel] - left[sel]).max())
+    print(f"{name}: {sel.sum()} of {N} rows selected; device controls leave {left[sel][:, wm].max():.3g} m on the weighted fingers; "
+          f"device residual off its float64 re-evaluation by {dres:.3g}")
+    assert sel.mean() >= 0.9
+    assert left[sel][:, wm].max() <= 1e-5
+    assert dres <= 1e-5                                                        # all five fingers, the dropped ones included
+    if not wm.all():
+        assert left[sel][:, ~wm].max() > 1e-3                                  # ... which were indeed left where they were
+
+
+def _check_contract(hk, u0, out, free):
+    c, q = out["controls"], out["q"]
+    assert (q == hk.q_of_u(c, np.float32)).all()                                # exact products with scale 1 or 2
+    for ctl, grp in enumerate(ir.COUPLING):
+        for d, s in grp:
+            assert (bits(q[:, d]) == bits(np.float32(s) * c[:, ctl])).all()
+    assert (bits(q[:, ir.HELD_DOF]) == 0).all()                                # +0.0f
+    assert (c >= hk.lower).all() and (c <= hk.upper).all()
+    fixed = [k for k in range(NACT) if not (free >> k) & 1]
+    assert (bits(c[:, fixed]) == bits(u0[:, fixed])).all()
+    if not free & 63:
+        assert (bits(q[:, :6]) == bits(u0[:, :6])).all()
+    moved = [k for k in range(NACT) if (free >> k) & 1]
+    assert (np.abs(c[:, moved] - u0[:, moved]).max(0) > 1e-4).all()            # every free control was used
+
+
+@pytest.mark.gpu
+def test_output_contract(rig):
+    hk, core, u0 = rig["hk"], rig["core"], rig["u0"]
+    _check_contract(hk, u0, _conv_gpu(rig, "tips")["gpu"], ir.FINGERS_FREE)
+    for free, pert in ((ir.ALL_FREE, 0.1), ((1 << 7) | (1 << 9) | (1 << 16) | (1 << 2), 0.3)):
+        _, _, tg = hk.test_poses(N, SEED, free_mask=ir.ALL_FREE, pert=pert)
+        out = gpu_ik(core, N, tg, free_mask=free, iters=8, damping=1e-2, max_step=0.05)
+        _check_contract(hk, u0, out, free)
+    # far targets: the limits hold and are reached, and no control moves by more than max_step an iteration
+    tg = _conv_gpu(rig, "tips")["tg"] + np.float32(0.5)
+    out = gpu_ik(core, N, tg, iters=3, damping=1e-3, max_step=0.1)
+    c = out["controls"]
+    assert (c >= hk.lower).all() and (c <= hk.upper).all() and ((c == hk.lower) | (c == hk.upper)).any()
+    assert np.abs(c - u0).max() <= 3 * 0.1 * (1 + 1e-5)                          # s d rounds a few ulp above max_step
+    # a q0 off the coupling manifold is projected onto it, for fixed controls too
+    q_off = rig["q0"].copy()
+    q_off[:, [9, 13, 18, 22, 14]] += np.float32(0.123)
+    q_off[:, 7] = np.float32(9.0)                                              # above the limit of control 7
+    out = gpu_ik(core, N, _conv_gpu(rig, "tips")["tg"], q=q_off, free_mask=1 << 10, iters=1)
+    want = u0.copy()
+    want[:, 7] = hk.upper[7]
+    fixed = [k for k in range(NACT) if k != 10]
+    assert (bits(out["controls"][:, fixed]) == bits(want[:, fixed])).all()
+    assert (out["q"] == hk.q_of_u(out["controls"], np.float32)).all()
+
+
+@pytest.mark.gpu
+def test_fixed_point_and_hand_frame(hk):
+    """A stepped env's own fingertips are a fixed point of the solve, in both frames, through the public surface.  The physics leaves
+    q off the coupling manifold by the PD tracking error (the two DOFs of a DIP control differ by ~1e-2 rad while they move), which
+    the start-value projection turns into millimetres of residual.  The check therefore uses the state q = C u: the stepped state
+    projected onto the manifold, written back, published and observed again (obs-only post block)."""
+    import torch
+    from dexrobot_isaac_amd import make_env
+    env = make_env("BlindGrasping", N, "cuda:0", "cuda:0", 0)
+    env.reset()
+    g = torch.Generator().manual_seed(9)
+    for _ in range(10):
+        env.step((2 * torch.rand(N, env.num_actions, generator=g) - 1).cuda())
+    core = env._core
+    q = core.field("q").t().cpu().numpy()
+    u0 = hk.u0_of_q(q, np.float32)
+    gap = float(np.abs(q - hk.q_of_u(u0, np.float32)).max())
+    qm = hk.q_of_u(u0, np.float32)
+    core.dof_state[:, :, 0] = torch.as_tensor(qm, device=core.device)
+    core.set_dof_state_indexed(torch.arange(N))
+    core.run_stage(_abi.STAGE["PUBLISH"])
+    core.post_physics(obs_only=True)
+    torch.cuda.synchronize()
+    assert (core.field("q").t().cpu().numpy() == qm).all()
+    assert np.abs(u0[:, 6:]).max() > 0.01                                      # the fingers have moved
+    worst = {}
+    for sites, key in (("tips", "fingertip_poses"), ("pads", "fingerpad_poses")):
+        for frame in ("hand", "world"):
+            tg = env.obs_dict[f"{key}_{frame}"].reshape(N, NF, 7)[:, :, :3].contiguous()
+            u, info = env.solve_fingertip_ik(tg, sites=sites, frame=frame, iters=1, return_info=True)
+            torch.cuda.synchronize()
+            res, du = float(info["residual"].max()), float(np.abs(u.cpu().numpy() - u0).max())
+            worst[(sites, frame)] = (res, du)
+            # the q override equal to the env's state: the state path's bits
+            u2, info2 = env.solve_fingertip_ik(tg, q=env.dof_pos.clone(), sites=sites, frame=frame, iters=1, return_info=True)
+            assert torch.equal(u.view(torch.int32), u2.view(torch.int32)) and torch.equal(info["q"].view(torch.int32), info2["q"].view(torch.int32))
+            assert torch.equal(info["residual"].view(torch.int32), info2["residual"].view(torch.int32))
+    print(f"stepped state off the coupling manifold by {gap:.3g} rad; at the projected state (residual m, |controls - u0|): {worst}")
+    for res, du in worst.values():
+        assert res < 1e-5 and du <= 1e-4
+    # a subset of envs, all controls free, world frame: still a fixed point
+    ids = [69, 3, 64]
+    tg = env.obs_dict["fingertip_poses_world"].reshape(N, NF, 7)[ids][:, :, :3].contiguous()
+    u, info = env.solve_fingertip_ik(tg, env_ids=ids, free="all", iters=1, return_info=True)
+    assert float(info["residual"].max()) < 1e-5 and np.abs(u.cpu().numpy() - u0[ids]).max() <= 1e-4
+    env.close()
+
+
+@pytest.mark.gpu
+def test_addressing_and_reproducibility(rig):
+    import torch
+    hk, core, q0 = rig["hk"], rig["core"], rig["q0"]
+    r = _conv_gpu(rig, "tips")
+    kw = dict(sites=0, iters=32, damping=1e-3, max_step=0.5, weights=r["w"])
+    again = gpu_ik(core, N, r["tg"], **kw)
+    for k in ("controls", "q", "residual"):
+        assert (bits(again[k]) == bits(r["gpu"][k])).all()                     # the same call twice: identical bits
+    ids = [69, 0, 64, 3, 63, 37]                                               # both workgroups, shuffled
+    by_id = gpu_ik(core, len(ids), r["tg"][ids], env_ids=ids, **kw)
+    by_q = gpu_ik(core, len(ids), r["tg"][ids], q=q0[ids], env_ids=[-1], **kw)  # env_ids is ignored with an override
+    for k in ("controls", "q", "residual"):
+        assert (bits(by_id[k]) == bits(r["gpu"][k][ids])).all() and (bits(by_q[k]) == bits(r["gpu"][k][ids])).all()
+    one = gpu_ik(core, 1, r["tg"][[37]], env_ids=[37], want=(), **kw)           # k = 1, the optional outputs left out
+    assert one["q"] is None and one["residual"] is None and (bits(one["controls"]) == bits(r["gpu"]["controls"][[37]])).all()
+    # q override with k = 130 (three workgroups): every row is its own problem
+    rep = np.concatenate([np.arange(N), np.arange(60)])
+    big = gpu_ik(core, len(rep), r["tg"][rep], q=q0[rep], **kw)
+    for k in ("controls", "q", "residual"):
+        assert (bits(big[k]) == bits(r["gpu"][k][rep])).all()
+    # ids outside [0, N) leave their rows as they are
+    bad = [5, -1, N, 69]
+    out = gpu_ik(core, 4, r["tg"][[5, 0, 0, 69]], env_ids=bad, **kw)
+    for k in ("controls", "q", "residual"):
+        assert np.isnan(out[k][1:3]).all() and (bits(out[k][[0, 3]]) == bits(r["gpu"][k][[5, 69]])).all()
+    # the argument errors that need a live handle
+    lib, h = core.lib, core.h
+    buf = torch.zeros(N, NF, 3, device=core.device)
+    ctl = torch.zeros(N, NACT, device=core.device)
+    tp, cp, prm = C.c_void_p(buf.data_ptr()), C.c_void_p(ctl.data_ptr()), _prm()
+    assert lib.dexsim_solve_ik(h, None, N - 1, None, tp, C.byref(prm), cp, None, None, None) == 1
+    assert b"k == num_envs" in lib.dexsim_last_error()
+    assert lib.dexsim_solve_ik(h, None, N, None, tp, C.byref(_prm(iters=65)), cp, None, None, None) == 1
+    h2 = C.c_void_p()
+    sc, ms = _setup(N)
+    assert lib.dexsim_create(C.byref(sc), C.byref(ms), core.dev_index, C.byref(h2)) == 0
+    assert lib.dexsim_solve_ik(h2, None, N, None, tp, C.byref(prm), cp, None, None, None) == 2   # DEXSIM_ERR_NOT_BOUND
+    assert lib.dexsim_destroy(h2) == 0
+    torch.cuda.synchronize()
+    assert not ctl.any()                                                       # none of them launched
+
+
+def _snapshot(core):
+    import torch
+    torch.cuda.synchronize()
+    names = ("arena", "stats", "counters", "obs_buf", "rew_buf", "reset_buf", "episode_step_count", "episode_length", "dof_state",
+             "root_state", "rigid_body_states", "contact_forces_all", "full_dof_targets", "masks")
+    snap = {n: getattr(core, n).clone() for n in names}
+    snap["stamp"] = core.get_step_stamp()
+    return snap
+
+
+def _same(a, b):
+    import torch
+    return all((a[k] == b[k]) if k == "stamp" else torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
+
+
+@pytest.mark.gpu
+def test_purity(hk):
+    import torch
+    from dexrobot_isaac_amd.core import DexSimCore
+    sc, ms = _setup(N)
+    core, twin = DexSimCore(sc, ms, "cuda:0"), DexSimCore(sc, ms, "cuda:0")
+    g = torch.Generator().manual_seed(4)
+    acts = [(2 * torch.rand(N, 18, generator=g) - 1).cuda() for _ in range(8)]
+    for c in (core, twin):
+        c.reset()
+        for a in acts[:3]:
+            c.step(a)
+    before = _snapshot(core)
+    _, q0, tg = hk.test_poses(N, SEED)
+    o1 = gpu_ik(core, N, tg, iters=4)
+    gpu_ik(core, 3, tg[:3], env_ids=[69, 1, 64], sites=1, frame=1, iters=2)
+    gpu_ik(core, N, tg, q=q0, free_mask=ir.ALL_FREE, iters=2)
+    o2 = gpu_ik(core, N, tg, iters=4)
+    assert _same(before, _snapshot(core))                                      # nothing of the instance changed
+    assert all((bits(o1[k]) == bits(o2[k])).all() for k in o1)
+    for a in acts[3:]:
+        core.step(a)
+        twin.step(a)
+    assert _same(_snapshot(core), _snapshot(twin))                             # ... and the run continues like a twin that never called it
+    for c in (core, twin):
+        c.close()
