@@ -125,6 +125,7 @@ class DexSimCamera(C.Structure):
 
 
 IK_MAX_ITERS = 64   # DEXSIM_IK_MAX_ITERS
+NPROX_GROUPS, NPROX_PAIRS = 15, 120   # DEXSIM_NPROX_GROUPS, DEXSIM_NPROX_PAIRS: the pair table of dexsim_query_proximity
 
 
 class DexSimIK(C.Structure):
@@ -145,6 +146,7 @@ EXPORTED_SYMBOLS = [
     "dexsim_camera_struct_size", "dexsim_render_layout", "dexsim_render",
     "dexsim_body_jacobian", "dexsim_mass_matrix",
     "dexsim_ik_struct_size", "dexsim_solve_ik",
+    "dexsim_proximity_pair", "dexsim_query_proximity",
 ]
 
 
@@ -192,6 +194,8 @@ def declare_prototypes(lib):
     lib.dexsim_mass_matrix.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.dexsim_ik_struct_size.argtypes = [P(sz)]
     lib.dexsim_solve_ik.argtypes = [vp, vp, i32, vp, vp, P(DexSimIK), vp, vp, vp, vp]
+    lib.dexsim_proximity_pair.argtypes = [i32, P(i32), P(i32), P(i32)]
+    lib.dexsim_query_proximity.argtypes = [vp, vp, i32, vp, vp, f32, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = i32
     lib.dexsim_error_string.argtypes = [i32]

@@ -437,3 +437,31 @@ class DexSimCore:
         rp = None if residual is None else self._kin_out("solve_ik", "residual", residual, (k, _abi.NFINGER))
         self._keep_ik = targets                     # alive until the kernel ran
         check(self.lib.dexsim_solve_ik(self.h, ids, k, qp, tp, C.byref(prm), cp, qo, rp, self._stream()), "solve_ik")
+
+    # ------------------------------------------------------------------ clearance queries
+    def proximity_pairs(self):
+        """The pair table of dexsim_query_proximity as a list of NPROX_PAIRS (capsule A, capsule B, group) triples."""
+        a, b, g = C.c_int(0), C.c_int(0), C.c_int(0)
+        out = []
+        for i in range(_abi.NPROX_PAIRS):
+            check(self.lib.dexsim_proximity_pair(i, C.byref(a), C.byref(b), C.byref(g)), "proximity_pair")
+            out.append((a.value, b.value, g.value))
+        return out
+
+    def proximity(self, cap_env=None, self_min=None, pair_dist=None, env_ids=None, q=None, box_pose=None, box_size=0.0):
+        """Clearances of the hand in one launch: `cap_env` (k, 18, 2, 8) f32 = every collision capsule against the box (record 0) and
+        the ground plane (record 1) as (signed distance, normal towards the capsule, witness on the other shape, axis parameter);
+        `self_min` (k, 15, 8) = the closest capsule pair of every finger pair and of the palm with every finger; `pair_dist`
+        (k, 120) = the distance of every pair of the pair table.  Any of the three may be None, not all.  Rows as for body_jacobian:
+        env_ids (None = all envs), or the rows of a (k, 26) `q` override.  The box: `box_pose` (k, 7) f32 (centre, quaternion xyzw)
+        when given, else the env's own box on the state path, else none; `box_size` > 0 overrides cfg.box_size.
+        dexsim_query_proximity."""
+        if cap_env is None and self_min is None and pair_dist is None:
+            raise DexSimError("proximity: at least one of cap_env, self_min and pair_dist is required")
+        ids, qp, k = self._kin_rows("proximity", env_ids, q)
+        bp = None if box_pose is None else self._kin_out("proximity", "box_pose", box_pose, (k, 7))
+        cp = None if cap_env is None else self._kin_out("proximity", "cap_env", cap_env, (k, _abi.NCAP, 2, 8))
+        sp = None if self_min is None else self._kin_out("proximity", "self_min", self_min, (k, _abi.NPROX_GROUPS, 8))
+        pp = None if pair_dist is None else self._kin_out("proximity", "pair_dist", pair_dist, (k, _abi.NPROX_PAIRS))
+        self._keep_prox = box_pose                  # alive until the kernel ran
+        check(self.lib.dexsim_query_proximity(self.h, ids, k, qp, bp, float(box_size), cp, sp, pp, self._stream()), "query_proximity")

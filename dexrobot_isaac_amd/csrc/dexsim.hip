@@ -916,3 +916,57 @@ extern "C" int dexsim_solve_ik(dexsim_t h, const int64_t* env_ids, int k, const 
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------- clearance queries
+// Behind every use of the step kernels, like the kernels above.
+// clang-format off
+#include "dexsim_proximity.hip.inc"
+// clang-format on
+
+// pair i of the pair table (include/dexsim.h), in the capsule order validate_model and dexsim_query_proximity insist on
+static void px_pair(int i, int* cap_a, int* cap_b, int* group) {
+  if (i < 90) {
+    const int g = i / 9, r = i - 9 * g;
+    *cap_a = px_finger_cap(px_group_fa(g), r / 3); *cap_b = px_finger_cap(px_group_fb(g), r % 3); *group = g;
+  } else {
+    const int j = i - 90, f = j / 6, r = j - 6 * f;
+    *cap_a = r / 2; *cap_b = px_finger_cap(f, 1 + r % 2); *group = 10 + f;
+  }
+}
+
+extern "C" int dexsim_proximity_pair(int i, int* cap_a, int* cap_b, int* group) {
+  if (!cap_a || !cap_b || !group) return fail(DEXSIM_ERR_ARG, "dexsim_proximity_pair: null argument");
+  if (i < 0 || i >= DEXSIM_NPROX_PAIRS) return fail(DEXSIM_ERR_ARG, "dexsim_proximity_pair: pair index out of range");
+  px_pair(i, cap_a, cap_b, group);
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_query_proximity(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* box_pose, float box_size,
+                                      float* cap_env, float* self_min, float* pair_dist, void* stream) {
+  // the checks of the outputs, of box_size and of k need neither a handle nor a device
+  if (!cap_env && !self_min && !pair_dist)
+    return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: at least one of cap_env, self_min and pair_dist is required");
+  if (((uintptr_t)cap_env & 15) != 0 || ((uintptr_t)self_min & 15) != 0 || ((uintptr_t)pair_dist & 15) != 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: the outputs must be 16-byte aligned");
+  if (!std::isfinite(box_size)) return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: box_size is not finite");
+  if (k <= 0) return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: k must be positive");
+  ProxArgs K;
+  std::memset(&K, 0, sizeof K);
+  int rc = kin_rows("dexsim_query_proximity", h, env_ids, k, q, &K.rows);
+  if (rc) return rc;
+  for (int c = 0; c < DEXSIM_NCAP; c++)
+    if (h->model.cap_fslot[c] != (c < 3 ? DEXSIM_FSLOT_PALM : c - 3))
+      return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: the model must have exactly three palm capsules (0-2) and one capsule per finger "
+                                  "link (capsule 3 + s in force slot s)");
+  const float size = box_size > 0.f ? box_size : h->cfg.box_size;
+  K.box_pose = box_pose;
+  K.box_env = !box_pose && !q && h->cfg.has_box;
+  if ((K.box_pose || K.box_env) && !(size > 0.f))
+    return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: a box needs a positive box_size or cfg.box_size");
+  NEED_BOUND(h);
+  K.hb = 0.5f * size;
+  K.cap_env = cap_env; K.self_min = self_min; K.pair_dist = pair_dist;
+  k_proximity<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}

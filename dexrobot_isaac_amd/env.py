@@ -314,6 +314,40 @@ class _TaskView:
         self.name = name
 
 
+class ProximityResult:
+    """What DexHandEnv.query_proximity returns: the three device tensors (None where not requested), the pair table and the names
+    behind the capsule and group indices."""
+    FINGER_NAMES = ("thumb", "index", "middle", "ring", "pinky")
+
+    def __init__(self, model, pairs, cap_env=None, self_min=None, pair_dist=None):
+        self.cap_env, self.self_min, self.pair_dist = cap_env, self_min, pair_dist
+        self.pairs = torch.as_tensor(pairs, dtype=torch.int64).view(_abi.NPROX_PAIRS, 3)   # (capsule A, capsule B, group), host
+        self._model = model
+
+    def capsule_body(self, c):
+        """Name of the rigid body capsule c belongs to (a row name of rigid_body_states)."""
+        c = int(c)
+        if not 0 <= c < _abi.NCAP:
+            raise IndexError(f"capsule index must be in [0, {_abi.NCAP}), got {c}")
+        slot = int(self._model.cap_fslot[c])
+        return self._model.body_names[[int(s) for s in self._model.body_fslot].index(slot)]
+
+    def group_fingers(self, g):
+        """The two sides of group g: a pair of finger names, or ("palm", finger name)."""
+        g = int(g)
+        if not 0 <= g < _abi.NPROX_GROUPS:
+            raise IndexError(f"group index must be in [0, {_abi.NPROX_GROUPS}), got {g}")
+        if g >= 10:
+            return ("palm", self.FINGER_NAMES[g - 10])
+        fa, fb = [(a, b) for a in range(5) for b in range(a + 1, 5)][g]
+        return (self.FINGER_NAMES[fa], self.FINGER_NAMES[fb])
+
+    @property
+    def min_pair(self):
+        """(k, 15) int64: the pair-table index of every group's closest pair (word 7 of self_min)."""
+        return self.self_min[..., 7].contiguous().view(torch.int32).to(torch.int64)
+
+
 class DexHandEnv:
     """Vectorised DexHand environment on one MI355X (one process per GPU; shard envs across ranks)."""
 
@@ -960,6 +994,65 @@ class DexHandEnv:
                       frame=0 if frame == "world" else 1, free_mask=mask, weights=w, iters=iters, damping=float(damping),
                       max_step=float(max_step), q_out=info.get("q"), residual=info.get("residual"))
         return (controls, info) if return_info else controls
+
+    # ------------------------------------------------------------------ clearance queries (dexsim_query_proximity)
+    def query_proximity(self, env_ids=None, q=None, box_pose=None, box_size=None, outputs=("cap_env", "self_min", "pair_dist"), out=None):
+        """Clearances of the hand against the box, the ground and itself, one kernel launch: is a configuration free of collision,
+        and how far is every link from the object, the ground and the other fingers?  Returns a ProximityResult with
+          cap_env   (k, 18, 2, 8): per collision capsule, record 0 against the box and record 1 against the ground z = 0 --
+                    [signed distance, unit normal towards the capsule (3), witness point on the other shape (3), axis parameter t];
+                    without a box the box record is (+inf, 0, ...)
+          self_min  (k, 15, 8): the closest capsule pair of the ten finger pairs and of the palm with each finger --
+                    [distance, normal from B to A (3), witness on B's surface (3), pair index as int32 bits]
+          pair_dist (k, 120): the distance of every pair of `pairs`, the (120, 3) table (capsule A, capsule B, group)
+        (the tensors not named in `outputs` are None).  Rows as for get_jacobian: the envs `env_ids` (None = all), or the rows of a
+        (k, 26) joint-position override `q`.  The box: `box_pose` (k, 7) = centre xyz + quaternion xyzw when given; "env" together
+        with a `q` of num_envs rows takes every env's own box ("check my IK result against my box"); None = the envs' own box
+        without `q`, no box with it.  box_size: edge length, None = the configured one.  out: a dict of preallocated tensors by
+        output name.  The engine's own hand self-collision does not exist: negative self distances are not resolved by the
+        physics."""
+        what = "query_proximity"
+        core = self._core
+        if not hasattr(core, "proximity"):
+            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no proximity()")
+        core, ids, q, k = self._kindyn_rows(what, env_ids, q)
+        names = ("cap_env", "self_min", "pair_dist")
+        if isinstance(outputs, str):
+            outputs = (outputs,)
+        outputs = tuple(outputs)
+        if not outputs or any(o not in names for o in outputs):
+            raise ValueError(f"{what}: outputs must be a non-empty subset of {names}, got {outputs}")
+        if isinstance(box_pose, str):
+            if box_pose != "env":
+                raise ValueError(f"{what}: box_pose must be a (k, 7) tensor, 'env' or None, got {box_pose!r}")
+            if q is None or k != self.num_envs:
+                raise ValueError(f"{what}: box_pose='env' needs a q override of num_envs = {self.num_envs} rows")
+            if not int(self._sim_cfg.has_box):
+                raise ValueError(f"{what}: box_pose='env' needs a task with a box")
+            box_pose = core.root_state[:, 1, :7].contiguous()
+        elif box_pose is not None:
+            box_pose = torch.as_tensor(box_pose, dtype=torch.float32, device=core.device)
+            if tuple(box_pose.shape) != (k, 7):
+                raise ValueError(f"{what}: box_pose must have shape ({k}, 7), got {tuple(box_pose.shape)}")
+            box_pose = box_pose.contiguous()
+        size = 0.0
+        if box_size is not None:
+            size = float(box_size)
+            if not (size > 0.0 and size != float("inf")):
+                raise ValueError(f"{what}: box_size must be a positive finite edge length, got {box_size}")
+        shapes = {"cap_env": (k, _abi.NCAP, 2, 8), "self_min": (k, _abi.NPROX_GROUPS, 8), "pair_dist": (k, _abi.NPROX_PAIRS)}
+        if out is not None and (not isinstance(out, dict) or any(o not in outputs for o in out)):
+            raise ValueError(f"{what}: out must be a dict of tensors keyed by the names in outputs, got {out if not isinstance(out, dict) else sorted(out)}")
+        bufs = {}
+        for o in outputs:
+            given = None if out is None else out.get(o)
+            bufs[o] = self._kindyn_out(what, given, shapes[o], core.device)
+            if given is None and ids is not None:   # a row whose id is out of range is left as it is by the kernel: give it a defined value
+                bufs[o].fill_(float("nan"))
+        core.proximity(env_ids=ids, q=q, box_pose=box_pose, box_size=size, **bufs)
+        if getattr(self, "_proximity_pairs", None) is None:
+            self._proximity_pairs = core.proximity_pairs()                     # a host table: read once
+        return ProximityResult(self.model, self._proximity_pairs, **bufs)
 
     def close(self):
         if self._core is not None:

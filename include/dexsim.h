@@ -660,6 +660,73 @@ int dexsim_ik_struct_size(size_t* out);
 int dexsim_solve_ik(dexsim_t h, const int64_t* env_ids, int k, const float* q0, const float* targets, const DexSimIK* prm,
                     float* controls, float* q_out, float* residual, void* stream);
 
+/* ------------------------------------------------------------------ clearance queries: hand / box, hand / ground, finger / finger
+ * "Is this configuration free of collision, and how far is each link from the object, the ground and the other fingers?" -- for
+ * planners (checking the joint positions dexsim_solve_ik returns), reward shaping and pre-grasp logic (per-link clearances) and
+ * grasp analysis (contact points and normals for J^T f with dexsim_body_jacobian).  The engine itself collides the hand with the box
+ * and the ground only -- it models no hand self-collision -- and its manifold is sub-step scratch, not API; this call is the public,
+ * exact counterpart.  One launch, stream-ordered, never synchronises, allocates nothing; a pure function of the persistent state
+ * (arena fields q, box_pos, box_quat) or of the caller's overrides: it writes no arena word, API tensor, statistics word, counter or
+ * the step stamp.
+ *
+ * ROWS and the Q OVERRIDE are those of dexsim_body_jacobian: with q == NULL row i is env env_ids[i] (NULL: env i, k == num_envs) and
+ * a row whose id is outside [0, num_envs) leaves its output rows untouched; with q != NULL, a device (k, 26) array, env_ids is
+ * ignored and k may be any positive number.
+ * THE BOX of a row: box_pose, a device (k, 7) f32 array (centre xyz, quaternion xyzw), when it is given; otherwise the row's env
+ * (box_pos, box_quat) when q == NULL and cfg.has_box; otherwise there is no box.  Edge length: box_size if it is > 0, else
+ * cfg.box_size.  The quaternion is normalised by the call (a zero quaternion is the identity).
+ * A row's result depends on that row alone and is reproducible bit for bit; a q / box_pose row equal to an env's state gives that
+ * env's output bit for bit.
+ *
+ * OUTPUTS, f32, 16-byte aligned; any may be NULL, not all three.
+ * cap_env (k, DEXSIM_NCAP, 2, 8): for capsule c in DexHandModel order, record 0 against the box, record 1 against the ground plane
+ * z = 0.  Words of a record:
+ *     0     signed distance d between the surfaces (negative: overlap)
+ *     1-3   unit normal n, world frame, pointing from the other shape towards the capsule
+ *     4-6   witness point p on the other shape's surface, world frame
+ *     7     t in [0, 1], the axis parameter of the capsule's witness: the axis point cap_p0 + t (cap_p1 - cap_p0) is
+ *           p + (d + r) n, the witness on the capsule's surface p + d n
+ *   Without a box the box record is (+inf, 0, 0, 0, 0, 0, 0, 0).
+ * self_min (k, DEXSIM_NPROX_GROUPS, 8): the closest pair of each group of the pair table: word 0 d; 1-3 n, pointing from capsule B
+ *   to capsule A; 4-6 the witness on B's surface; 7 the integer bits of the pair's index in the pair table.  Ties go to the lowest
+ *   pair index.
+ * pair_dist (k, DEXSIM_NPROX_PAIRS): d of every pair.
+ *
+ * PAIR TABLE (dexsim_proximity_pair: a host table, no handle needed).  Capsules 0-2 are the palm's, capsule 3 + 3 f + l is link l of
+ * finger f (l = 0 proximal, 1 middle, 2 distal): the capsule with cap_fslot == 3 f + l.  Groups 0-9 are the finger pairs (fa < fb)
+ * in lexicographic order, nine pairs each: pair 9 g + 3 la + lb is A = link la of finger fa against B = link lb of finger fb.
+ * Groups 10-14 pair the palm with finger f = group - 10, six pairs each: pair 90 + 6 f + 2 i + (lb - 1) is A = palm capsule i
+ * against B = link lb in {1, 2} of finger f; the proximal link is left out because it overlaps the palm by construction.  Links of
+ * one finger are never paired.  A model that does not have exactly three palm capsules and one capsule per finger link in that
+ * order (cap_fslot) is refused at the call.
+ *
+ * GEOMETRY, to fp32 roundoff; nothing here is iterated.
+ * Capsule / ground: d = min(z0, z1) - r; t = 0 or 1, the lower end of the axis (a tie: 0); n = (0, 0, 1); p = that end projected
+ *   onto z = 0.
+ * Capsule / box: in the box frame, with the axis P(t) = a + t e, the half edge hb and f(t) = |P - clamp(P, -hb, hb)|^2, the witness
+ *   parameter t* is the minimiser of f over [0, 1], the smallest t where the minimum is a flat stretch.  It is computed in closed
+ *   form (f' is piecewise linear and non-decreasing with at most six breakpoints, where a coordinate crosses +-hb).  Axis outside
+ *   the box: d = sqrt(f(t*)) - r, n = the normalised excess P - clamp(P) rotated to the world, p = clamp(P(t*)) in world coordinates.
+ *   Axis meeting the box (sqrt(f(t*)) <= 1e-6 m, the threshold of the engine's sphere / box routine): t* becomes the midpoint of the
+ *   stretch of the axis inside the box (slab clipping); depth = min_i (hb - |P_i(t*)|), the first axis winning a tie; d = -depth - r;
+ *   n = +- that axis of the box, the sign of P_i (+ at zero); p = P(t*) moved onto that face.  This is the engine's rule for a sphere
+ *   whose centre is inside the box; it is NOT a true penetration depth (the least translation that separates the shapes).  Such
+ *   records are the ones with d <= -r.
+ * Capsule / capsule: the clamped closest points c_A = a0 + s e_A, c_B = b0 + t e_B of the two axes by the standard two-stage clamping
+ *   (s from the unconstrained optimum, clamped; t optimal for that s, clamped; if t was clamped, s optimal for that t, clamped).
+ *   Parallel axes (|e_A|^2 |e_B|^2 - (e_A . e_B)^2 <= 1e-12 |e_A|^2 |e_B|^2): the first s is 0.  An axis with |e|^2 <= 1e-18 is a
+ *   point.  d = |c_A - c_B| - r_A - r_B, n = (c_A - c_B) / |c_A - c_B|, or (0, 0, 1) when the axis distance is below 1e-9 m.
+ *
+ * DEXSIM_ERR_ARG (with a dexsim_last_error text; no device needed): all three outputs NULL, a misaligned output, a non-finite
+ * box_size, k <= 0, a NULL handle, env_ids == NULL without q and k != num_envs, a model outside the pair table's capsule order, a box
+ * without a positive edge length (box_size <= 0 and cfg.box_size <= 0).  DEXSIM_ERR_NOT_BOUND before dexsim_bind. */
+#define DEXSIM_NPROX_GROUPS 15
+#define DEXSIM_NPROX_PAIRS 120
+/* pair i of the pair table, 0 <= i < DEXSIM_NPROX_PAIRS: capsule A, capsule B, group */
+int dexsim_proximity_pair(int i, int* cap_a, int* cap_b, int* group);
+int dexsim_query_proximity(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* box_pose, float box_size,
+                           float* cap_env, float* self_min, float* pair_dist, void* stream);
+
 const char* dexsim_error_string(int code);
 const char* dexsim_last_error(void);
 
