@@ -172,6 +172,22 @@ REWARD_TERMS = [
 ]
 
 
+# The keys ObservationEncoder.initialize accepts in policy_observation_keys are those of the dictionary it builds for its
+# dimension probe (observation_encoder.py:207-226), recorded per task in tests/golden/reference_policy_keys.json:
+# active_rule_targets is not in it (the step adds that entry after the probe), a task key needs its task, and the three task
+# observations that get_task_observations returns as (num_envs,) tensors (blind_grasping_task.py:549-653) fail the probe's
+# `tensor.shape[1]` with an IndexError.
+_RANK1_TASK_OBS_KEYS = ("avg_finger_to_object_distance", "avg_finger_to_object_height_diff", "hand_to_object_distance")
+
+
+def policy_observation_keys_accepted(task_name):
+    """The names `task.policy_observation_keys` may hold for `task_name`, in OBS_KEYS order."""
+    base = [k for k, _ in OBS_KEYS[:NUM_BASE_TASK_OBS_KEYS] if k != "active_rule_targets"]
+    if task_name == "BaseTask":
+        return base
+    return base + [k for k, _ in OBS_KEYS[NUM_BASE_TASK_OBS_KEYS:] if k not in _RANK1_TASK_OBS_KEYS]
+
+
 def obs_key_offsets():
     off, out = 0, {}
     for name, dim in OBS_KEYS:
@@ -252,12 +268,14 @@ def build_sim_config(cfg, model=None, dr=None):
 
     c.contact_binary_threshold = float(task["contact_binary_threshold"])
     offs = obs_key_offsets()
-    valid = [k for k, _ in OBS_KEYS[:NUM_BASE_TASK_OBS_KEYS]] if c.task == _abi.TASK_BASE else list(offs)
+    valid = policy_observation_keys_accepted(name)
     keys = task["policy_observation_keys"]
     if len(keys) > _abi.MAX_OBS_SEG:
         raise RuntimeError("too many policy_observation_keys")
     n = 0
     for i, k in enumerate(keys):
+        if c.task == _abi.TASK_BLIND_GRASPING and k in _RANK1_TASK_OBS_KEYS:
+            raise IndexError("tuple index out of range")        # observation_encoder.py:220 on a (num_envs,) tensor
         if k not in valid:
             raise RuntimeError(f"Observation key '{k}' MISSING during initialization - fail fast")
         off, dim = offs[k]
@@ -265,6 +283,10 @@ def build_sim_config(cfg, model=None, dr=None):
             dim = c.num_actions
         c.obs_seg_off[i], c.obs_seg_len[i] = off, dim
         n += dim
+    if n > _abi.OBS_ALL_DIM:
+        # the device's column table (obs_buf column -> obs_dict row) has one entry per obs_dict row: a list that repeats keys
+        # beyond that size is refused here, not written past the table's end
+        raise RuntimeError(f"policy_observation_keys give {n} observations; at most {_abi.OBS_ALL_DIM} are supported")
     c.n_obs_seg, c.num_obs = len(keys), n
 
     term = task["termination"]

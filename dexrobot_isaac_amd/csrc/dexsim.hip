@@ -184,6 +184,8 @@ int dexsim_create(const DexSimConfig* cfg, const DexHandModel* model, int device
       tot += cfg->obs_seg_len[s];
     }
     if (tot != cfg->num_obs) return fail(DEXSIM_ERR_ARG, "dexsim_create: num_obs != sum of segments");
+    /* segments may repeat rows, but obs_col_row (and its staged copy in k_post) has DEXSIM_OBS_ALL_DIM entries */
+    if (tot > DEXSIM_OBS_ALL_DIM) return fail(DEXSIM_ERR_ARG, "dexsim_create: more observations than the column table holds");
   }
   int rc = validate_model(*model);
   if (rc) return rc;

@@ -21,8 +21,18 @@ InitializationManager) is reference code executing unmodified.
 The orchestration the fake parent performs (step / reset / reset_idx call order) restates
 dexhand_env/tasks/dexhand_base.py:743-942, which cannot be imported (it pulls in the viewer/video stack).
 
-Output: tests/golden/l2_<scenario>.npz  (+ the cfg overrides as JSON inside the npz), and
-tests/golden/reference_cfg_<task>.json (the reference's cfg tree as composed; `generate_golden.py cfg` writes only these).
+Output: tests/golden/l2_<scenario>.npz  (+ the cfg overrides as JSON inside the npz),
+tests/golden/reference_cfg_<task>.json (the reference's cfg tree as composed; `generate_golden.py cfg` writes only these) and
+tests/golden/reference_policy_keys.json (which single policy_observation_keys entries the reference's initialisation accepts,
+per task, and what it raises for the others; `generate_golden.py keys`).
+
+Scenarios: seven at or near the shipped defaults (blind_default / _fast / _wide / _long, base_default / _position / _wide) and
+four far from them (CFG_SCENARIOS: blind_cfg_fingers, blind_cfg_base, base_cfg_fingers, base_cfg_base), which together
+change every setting build_sim_config translates from the task YAML.  The latter run on the `margins` L1 profile
+(make_margins_hook): per env role and episode step it puts each quantity a threshold reads on a chosen side of that
+threshold, between the scenario's value and the default, so that putting any single override back to its default changes
+what the reference computes (tests/test_oracle_golden.py::test_every_override_is_live).  Those fixtures also record every
+termination criterion's raw condition per step (crit_fail / crit_succ, active or not) and the binary observations.
 """
 import copy
 import json
@@ -416,6 +426,8 @@ def make_l1_script(rng, model, N, T, has_box, profile, extra_states=0):
                 for f in (0, 1):
                     cf[np.ix_(g2, [c5[f]])] = np.array([0.0, 0.4, 0.0], dtype=np.float32)
                 cf[g2, B - 1, :] = 0.0
+        elif profile == "margins":
+            pass    # generic state only: the quantities the thresholds read are placed by make_margins_hook, per episode step
         else:
             if k % 7 in (2, 3, 4):
                 cf[::2, c5[1], :] = rng.normal(0, 1.0, (len(range(0, N, 2)), 3))
@@ -423,8 +435,136 @@ def make_l1_script(rng, model, N, T, has_box, profile, extra_states=0):
                 cf[1::3, c5[4], :] = rng.normal(0, 2.0, (len(range(1, N, 3)), 3))
         if has_box:
             rbs[:, B - 1, :] = box
-        script.append({"q": q.copy(), "qd": qd, "rbs": rbs, "cf": cf, "box": box})
+        st = {"q": q.copy(), "qd": qd, "rbs": rbs, "cf": cf, "box": box}
+        if profile == "margins":
+            # generic values on a 2^-11 grid (exact in fp32): the N = 70 fixture compresses to a committable size, and nothing
+            # the thresholds read comes from here
+            for f in ("q", "qd", "rbs"):
+                st[f] = (np.round(st[f] * 2048.0) / 2048.0).astype(np.float32)
+        script.append(st)
     return script
+
+
+def mid(value, default, fallback):
+    """A value strictly between an overridden threshold and its default (so that reverting the override flips the outcome);
+    `fallback` where the scenario leaves the threshold at its default."""
+    return 0.5 * (value + default) if value != default else fallback
+
+
+NUM_ROLES = {"BlindGrasping": 12, "BaseTask": 4}
+
+
+def make_margins_hook(rng, model, cfg, has_box):
+    """L1 profile `margins`: every quantity a configurable threshold reads is placed per env ROLE (env % 12, BaseTask env % 4)
+    and per EPISODE step on a chosen side of that threshold, between the scenario's value and the default where the two differ.
+    The state is written relative to the box position the reference's own reset drew (drift is then a scripted quantity) and
+    keyed on the reference's own episode_step_count / current_stage, so an env replays its role after every reset.  Episode
+    step 0 (the state a reset's physics step and the first control step see) is clear of every threshold.
+
+    BlindGrasping roles (all start from a good pre-grasp pose: pads level with the box, centroid and drift inside tolerance):
+      0  thumb + index + middle contact with box load in stage 2, lifted above success_height_threshold in stage 3 -> success
+      1  as 0, lifted one step later (successes in consecutive steps: max_consecutive_successes)
+      2  two fingers only, the third one's force between contact_binary_threshold and its default (min_fingers_for_grasp);
+         lets go after 3 steps of stage 3 (stage3_grasp_lost)
+      3  as 0, lifted to just below success_height_threshold
+      4  pad heights beyond height_tolerance          5  centroid beyond centroid_tolerance
+      6  box drift at position_drift_tolerance's far side; then sensor contact without box load (stage2_contact_failed,
+         stage3_grasp_lost by the contact-duration route)
+      7  box speed beyond velocity_tolerance          8  hand beyond max_box_distance from episode step 1
+      9  hand base below handbase_threshold from episode step 2      10  a fingertip below fingertip_threshold at episode step 1
+      11 ring-finger force cycling below / between / above the two contact_binary_threshold values, little finger on and off,
+         no grasp (stage 2 time-out)
+    BaseTask roles: 0 nominal, 1 hand base low from episode step 3, 2 fingertip low at episode step 2, 3 index force cycling
+    like role 11's, the other fingers on every third step."""
+    from dexrobot_isaac_amd.config import default_cfg
+    task, dflt = cfg["task"], default_cfg(cfg["task"]["name"])["task"]
+    hb, tips, pads = model.hand_local_rigid_body_index, model.fingertip_local_indices, model.fingerpad_local_indices
+    c5 = model.body_indices([f"r_f_link{f}_4" for f in range(1, 6)])
+    hs = task["termination"]["height_safety"]
+    hb_dip = 0.5 * hs["handbase_threshold"] if hs["handbase_threshold"] > 0 else -0.02
+    ft_dip = 0.5 * hs["fingertip_threshold"] if hs["fingertip_threshold"] > 0 else -0.004
+    cbt, cbt_d = task["contact_binary_threshold"], dflt["contact_binary_threshold"]
+    f_on, f_mid, f_off = 2.0 * max(cbt, cbt_d), mid(cbt, cbt_d, 2.0 * cbt), 0.5 * min(cbt, cbt_d)
+    f32 = np.float32
+
+    def unit_force(n, mag):
+        v = rng.normal(0, 1, (n, 3))
+        return (mag * v / np.linalg.norm(v, axis=1, keepdims=True)).astype(f32)
+
+    def base_hook(env_, st):
+        N = st["q"].shape[0]
+        es, role = env_.episode_step_count.numpy().astype(int), np.arange(N) % NUM_ROLES["BaseTask"]
+        rbs, cf = st["rbs"], st["cf"]
+        cf[:] = 0
+        low = (role == 1) & (es >= 3)
+        rbs[low, hb, 2] = hb_dip
+        dip = (role == 2) & (es == 2)
+        rbs[dip, tips[3], 2] = ft_dip
+        r3 = role == 3
+        mag = np.choose(es % 3, [f_off, f_mid, f_on])
+        cf[r3, c5[1], :] = unit_force(int(r3.sum()), 1.0) * mag[r3, None].astype(f32)
+        for f in (0, 2, 3, 4):
+            on = r3 & ((es + f) % 3 == 0)
+            cf[on, c5[f], :] = unit_force(int(on.sum()), f_on)
+
+    def blind_hook(env_, st):
+        N = st["q"].shape[0]
+        B = st["rbs"].shape[1]
+        ts = env_.observation_encoder.task_states
+        cdt = env_.physics_manager.control_dt
+        es, role = env_.episode_step_count.numpy().astype(int), np.arange(N) % NUM_ROLES["BlindGrasping"]
+        stage = ts["current_stage"].numpy().astype(int)
+        steps_in_stage = np.rint(ts["time_in_stage"].numpy() / cdt).astype(int)
+        ib = env_.task.initial_box_positions.numpy().astype(f32)
+        rbs, cf, box = st["rbs"], st["cf"], st["box"]
+        qt, qd_ = task["quality_thresholds"], dflt["quality_thresholds"]
+        # ---- box: at the position the reset drew, small drift / speed; lifted in stage 3 for the grasping roles
+        box[:, :3] = ib + rng.normal(0, 0.0004, (N, 3)).astype(f32)
+        box[:, 7:10] = rng.normal(0, 0.0004, (N, 3))
+        r6, r7 = role == 6, role == 7
+        box[r6, 0] = ib[r6, 0] + mid(qt["position_drift_tolerance"], qd_["position_drift_tolerance"], 0.02)
+        box[r7, 7:10] = np.array([mid(qt["velocity_tolerance"], qd_["velocity_tolerance"], 0.008), 0, 0], dtype=f32)
+        sht = task["success_height_threshold"]
+        z_hi, z_lo = mid(sht, dflt["success_height_threshold"], sht + 0.05), 0.85 * sht
+        lifted = (stage == 3) & (role <= 3) & (steps_in_stage >= np.where(role == 1, 1, 0))
+        box[lifted, 2] = np.where(role[lifted] == 3, z_lo, z_hi)
+        # ---- hand base above the box; pads in a pre-grasp pose relative to the box, tips 3 cm above their pads
+        hand = rbs[:, hb, :3]
+        hand[:, :2] += ib[:, :2]
+        far = (role == 8) & (es >= 1)
+        hand[far, 0] += mid(task["max_box_distance"], dflt["max_box_distance"], 1.2)
+        low = (role == 9) & (es >= 2)
+        hand[low, 2] = hb_dip
+        ht_ok = 0.3 * min(qt["height_tolerance"], qd_["height_tolerance"])
+        dz = np.where(role == 4, mid(qt["height_tolerance"], qd_["height_tolerance"], 0.04), ht_ok)
+        yoff = np.where(role == 5, mid(qt["centroid_tolerance"], qd_["centroid_tolerance"], 0.1), 0.0)
+        for f in range(5):
+            off = np.stack([np.full(N, 0.02 * (f - 2)), yoff, dz], axis=1).astype(f32)
+            rbs[:, pads[f], :3] = box[:, :3] + off + rng.normal(0, 0.001, (N, 3)).astype(f32)
+            rbs[:, tips[f], :3] = rbs[:, pads[f], :3] + np.array([0, 0, 0.03], dtype=f32)
+        dip = (role == 10) & (es == 1)
+        rbs[dip, tips[2], 2] = ft_dip
+        # ---- contact forces
+        cf[:] = 0
+        cf[:, B - 1, 2] = 2.0 * max(cbt, cbt_d, 0.5)                     # the box rests on the ground: loaded
+        grasp = (role <= 3) & (stage >= 2) & ~((role == 2) & (stage == 3) & (steps_in_stage >= 3))
+        for f in (0, 1, 2):
+            m = grasp & ((f < 2) | (role != 2))
+            cf[m, c5[f], :] = unit_force(int(m.sum()), f_on)
+        m = grasp & (role == 2)
+        cf[m, c5[2], :] = unit_force(int(m.sum()), f_mid)
+        sensor_only = r6 & (stage >= 2)
+        for f in (0, 1):
+            cf[sensor_only, c5[f], :] = unit_force(int(sensor_only.sum()), f_on)
+        cf[sensor_only, B - 1, :] = 0.0
+        r11 = role == 11
+        mag = np.choose(es % 3, [f_off, f_mid, f_on])
+        cf[r11, c5[3], :] = unit_force(int(r11.sum()), 1.0) * mag[r11, None].astype(f32)
+        on4 = r11 & (es % 4 >= 2)
+        cf[on4, c5[4], :] = unit_force(int(on4.sum()), f_on)
+        rbs[:, B - 1, :] = box
+
+    return blind_hook if has_box else base_hook
 
 
 def pack_l1(s, model, has_box):
@@ -448,6 +588,72 @@ def pack_l1(s, model, has_box):
 
 
 # ----------------------------------------------------------------------------------------------- scenarios
+# ----------------------------------------------------------------------------------------------- non-default configurations
+# Scenarios far from the shipped defaults, run on the `margins` L1 profile.  Together they change every DexSimConfig field that
+# build_sim_config derives from the task YAML.  `termination.height_safety: null` is NOT among them: the reference tests
+# `"height_safety" in task_cfg["termination"]` and then subscripts the value (step_processor.py:141-150), so a null raises
+# TypeError on the first step.
+_T = "task.termination."
+_RW = "task.reward_weights."
+_RC = "task.reward_calculation."
+_QT = "task.quality_thresholds."
+_PP = "task.penetration_prevention."
+CFG_SCENARIOS = {
+    # fingers-only policy (12 actions), permuted key list with keys from neither default list, failure-criteria subset
+    "blind_cfg_fingers": {
+        "env.episodeLength": 18, "task.stage1_duration": 0.09, "task.stage2_duration": 0.11,
+        "task.stage_evaluation.stage2_contact_success_threshold": 0.05, "task.contact_duration_threshold": 0.07,
+        "task.policy_controls_hand_base": False,
+        "task.policy_observation_keys": ["grasp_state", "object_pos", "prev_actions", "contact_forces", "all_finger_dof_pos",
+                                         "stage_progress", "fingertip_poses_hand", "contact_binary", "base_dof_vel",
+                                         "first_three_fingerpad_centroid", "contact_duration"],
+        _T + "active_failure_criteria": ["stage1_pregrasp_failed", "box_too_far", "hitting_ground"],
+        _T + "height_safety.handbase_threshold": 0.2, _T + "height_safety.fingertip_threshold": 0.04,
+        "task.contact_binary_threshold": 0.3, "task.min_fingers_for_grasp": 3, "task.success_height_threshold": 0.12,
+        "task.max_box_distance": 0.5, "task.max_consecutive_successes": 1, "task.max_finger_joint_velocity": 2.5,
+        _RW + "alive": 0.3, _RW + "height_safety": 0.7, _RW + "finger_velocity": 0.2, _RW + "hand_velocity": 0.15,
+        _RW + "hand_angular_velocity": 0.25, _RW + "joint_limit": 0.6, _RW + "finger_acceleration": 0.35,
+        _RW + "hand_acceleration": 0.45, _RW + "hand_angular_acceleration": 0.55, _RW + "contact_stability": 0.4,
+        _RC + "height_alignment_decay": 9.0, _RC + "centroid_positioning_decay": 3.0, _RC + "object_stability_decay": 60.0,
+        _RC + "first_three_height_consistency_decay": 4000.0, _RC + "fingerpad_proximity_decay": 16.0,
+        _RC + "base_stability_decay": 1.5,
+        _QT + "height_tolerance": 0.015, _QT + "centroid_tolerance": 0.05, _QT + "position_drift_tolerance": 0.02,
+        _QT + "velocity_tolerance": 0.002,
+        _PP + "geometricPenetrationFactor": 2.0, _PP + "proximityMinDistanceFactor": 2.2, _PP + "penetrationDepthScale": 40.0},
+    # base-only policy (6 actions), sim.dt with a fractional contact_duration_threshold / control_dt (0.04 / 0.016 = 2.5),
+    # reset ranges, velocity limits, another criteria subset; N = 70 with explicit reset_idx events
+    "blind_cfg_base": {
+        "env.episodeLength": 9, "sim.dt": 0.008, "task.stage1_duration": 0.04, "task.stage2_duration": 0.04,
+        "task.stage_evaluation.stage2_contact_success_threshold": 0.008, "task.contact_duration_threshold": 0.04,
+        "task.policy_controls_fingers": False,
+        "task.policy_observation_keys": ["time_in_stage", "active_prev_targets", "prev_actions", "object_vel", "hand_pose",
+                                         "finger_to_object_distances", "thumb_contact", "other_fingers_contact",
+                                         "grasp_duration", "base_dof_target", "finger_to_object_height_diff", "episode_time"],
+        _T + "active_failure_criteria": ["stage3_grasp_lost", "stage2_contact_failed", "stage1_pregrasp_failed"],
+        "task.max_base_linear_velocity": 0.35, "task.max_base_angular_velocity": 1.1,
+        "task.hand_translation_range": 0.07, "task.hand_rotation_range": 0.3,
+        "task.finger_randomization.thumb_rotation_range": 1.0, "task.finger_randomization.other_finger_range": 0.3,
+        "env.box.initial_position.xy_range": 0.035, "env.box.initial_position.z": 0.031},
+    # BaseTask, fingers-only, position mode, non-default key list, height threshold, contact threshold
+    "base_cfg_fingers": {
+        "env.episodeLength": 9, "task.controlMode": "position", "task.policy_controls_hand_base": False,
+        "task.policy_observation_keys": ["contact_duration", "hand_pose_arr_aligned", "prev_actions", "all_finger_dof_vel",
+                                         "contact_binary", "all_finger_dof_target", "episode_time", "contact_forces"],
+        _T + "height_safety.handbase_threshold": 0.305, _T + "height_safety.fingertip_threshold": 0.06,
+        "task.contact_binary_threshold": 0.4, "task.max_finger_joint_velocity": 3.0},
+    # BaseTask, base-only, position_delta, velocity limits and reward weights
+    "base_cfg_base": {
+        "env.episodeLength": 7, "task.policy_controls_fingers": False,
+        "task.policy_observation_keys": ["active_prev_targets", "fingerpad_poses_hand", "prev_actions", "base_dof_pos",
+                                         "contact_force_magnitude", "active_finger_dof_target"],
+        "task.max_base_linear_velocity": 0.2, "task.max_base_angular_velocity": 0.6,
+        _RW + "alive": 0.25, _RW + "height_safety": 0.4, _RW + "finger_velocity": 0.3, _RW + "hand_velocity": 0.2,
+        _RW + "hand_angular_velocity": 0.05, _RW + "joint_limit": 0.9, _RW + "finger_acceleration": 0.15,
+        _RW + "hand_acceleration": 0.1, _RW + "hand_angular_acceleration": 0.2, _RW + "contact_stability": 0.6,
+        _RW + "termination_failure_penalty": 3.0, _RW + "termination_timeout_penalty": 1.5},
+}
+
+
 def scenario_cfg(name):
     from dexrobot_isaac_amd.config import default_cfg
     if name == "blind_default":
@@ -463,6 +669,8 @@ def scenario_cfg(name):
         cfg, over = default_cfg("BaseTask"), {"env.episodeLength": 20}
     elif name in ("base_position", "base_wide"):
         cfg, over = default_cfg("BaseTask"), {"task.controlMode": "position", "env.episodeLength": 50 if name == "base_position" else 9}
+    elif name in CFG_SCENARIOS:
+        cfg, over = default_cfg("BlindGrasping" if name.startswith("blind") else "BaseTask"), CFG_SCENARIOS[name]
     else:
         raise KeyError(name)
     for k, v in over.items():
@@ -472,6 +680,9 @@ def scenario_cfg(name):
             d = d[p]
         d[parts[-1]] = v
     return cfg, over
+
+
+BINARY_OBS_KEYS = ("contact_binary", "thumb_contact", "other_fingers_contact", "grasp_state")
 
 
 def run_scenario(name, N, T, seed, events=None, snap_steps=()):
@@ -486,7 +697,7 @@ def run_scenario(name, N, T, seed, events=None, snap_steps=()):
     has_box = task_name == "BlindGrasping"
     model = HandModel()
     rng = np.random.default_rng(seed)
-    profile = {"blind_fast": "fast", "blind_wide": "fast", "blind_long": "long"}.get(name, "default")
+    profile = {"blind_fast": "fast", "blind_wide": "fast", "blind_long": "long"}.get(name, "margins" if name in CFG_SCENARIOS else "default")
     script = make_l1_script(rng, model, N, T, has_box, profile, extra_states=len(events))
     torch.manual_seed(cfg["train"]["seed"])
     env = FakeParent(copy.deepcopy(cfg), model, task_name, script)
@@ -514,9 +725,20 @@ def run_scenario(name, N, T, seed, events=None, snap_steps=()):
             st["rbs"][:, -1, :] = st["box"]
         env.l1_hook = follow_box
 
+    crit_log = []
+    if profile == "margins":
+        env.l1_hook = make_margins_hook(rng, model, cfg, has_box)
+        # every criterion's raw condition as TerminationManager.evaluate receives it, active or not (for the coverage test)
+        real_evaluate = env.termination_manager.evaluate
+
+        def rec_evaluate(step_count, b_succ, t_succ, b_fail, t_fail):
+            crit_log.append(({**b_succ, **t_succ}, {**b_fail, **t_fail}))
+            return real_evaluate(step_count, b_succ, t_succ, b_fail, t_fail)
+        env.termination_manager.evaluate = rec_evaluate
+
     torch.rand = rec_rand
     rec = {k: [] for k in ("actions", "obs", "rew", "done", "targets", "active_prev_targets", "episode_step",
-                           "reset_samples", "rew_total", "task_state", "stats")}
+                           "reset_samples", "rew_total", "task_state", "stats", "crit_fail", "crit_succ", "binaries")}
     l1_main, l1_reset, reset_l1_used = [], [], []
     ev = {k: [] for k in ("step", "ids", "samples", "l1", "targets", "active_prev_targets", "episode_step", "task_state",
                           "prev_actions_obs")}
@@ -545,10 +767,13 @@ def run_scenario(name, N, T, seed, events=None, snap_steps=()):
         # ---- env.reset(): reset all (consumes script state 0 as its physics step), obs x2
         c0 = env.l1_cursor
         obs0 = env.reset().clone()
+        if profile == "margins":   # (reset() computes observations twice: the stage clock has ticked twice by now)
+            assert env.l1_cursor - c0 == 1, f"{name}: the margins profile's first state terminated envs inside reset()"
         reset0_samples = collect_samples(np.ones(N, dtype=bool))
         reset0_l1 = pack_l1(script[c0], model, has_box)
         # a reset inside reset()'s post_physics_step would consume one more state
         extra_in_reset = env.l1_cursor - c0 - 1
+        crit_log.clear()
         agen = np.random.default_rng(seed + 1)
         for t in range(T):
             if t in events:                                  # explicit reset_idx(ids) between two steps
@@ -593,6 +818,15 @@ def run_scenario(name, N, T, seed, events=None, snap_steps=()):
                                                    ts["success_duration_steps"].numpy().astype(np.float32),
                                                    ts["just_transitioned_to_stage2"].numpy().astype(np.float32),
                                                    ts["just_transitioned_to_stage3"].numpy().astype(np.float32)]))
+            if profile == "margins":
+                from dexrobot_isaac_amd._abi import FAILURE_CRITERIA, SUCCESS_CRITERIA
+                (cs, cfl), = crit_log
+                crit_log.clear()
+                zero = torch.zeros(N, dtype=torch.bool)
+                rec["crit_fail"].append(np.stack([cfl.get(k, zero).numpy().copy() for k in FAILURE_CRITERIA]))
+                rec["crit_succ"].append(np.stack([cs.get(k, zero).numpy().copy() for k in SUCCESS_CRITERIA]))
+                od_b = env.obs_dict_pre_reset if env.obs_dict_pre_reset is not None else env.obs_dict
+                rec["binaries"].append(np.concatenate([od_b[k].reshape(N, -1).numpy() for k in BINARY_OBS_KEYS if k in od_b], axis=1))
             if t in snap_steps:
                 od_now = env.obs_dict_pre_reset if env.obs_dict_pre_reset is not None else env.obs_dict
                 if env.obs_dict_pre_reset is not None:
@@ -635,7 +869,9 @@ def run_scenario(name, N, T, seed, events=None, snap_steps=()):
         names = sorted(set().union(*[set(d) for d in snaps["rc"]]))
         out["snap_rc"] = np.stack([np.stack([d.get(k, np.full(N, np.nan, dtype=np.float32)) for k in names]) for d in snaps["rc"]])
         out["snap_rc_names"] = json.dumps(names)
-    sparse_l1r = name in ("blind_wide", "base_wide", "blind_long")
+    if profile == "margins":
+        out["binary_keys"] = json.dumps([k for k in BINARY_OBS_KEYS if k in env.obs_dict])
+    sparse_l1r = name in ("blind_wide", "base_wide", "blind_long") or name in CFG_SCENARIOS
     if sparse_l1r:
         idx, n_used = [], 0
         for s_ in l1_reset:
@@ -697,6 +933,33 @@ def record_composed_cfg():
         print(f"cfg {task}: wrote {path}")
 
 
+def record_accepted_policy_keys():
+    """Which single `policy_observation_keys` entries the reference's own initialisation accepts, per task: FakeParent (the
+    reference's InitializationManager -> ObservationEncoder.initialize, observation_encoder.py:207-234) is constructed with a
+    one-key list for every name of OBS_KEYS.  Written as lists of names to reference_policy_keys.json (refused names with the
+    exception type and message the reference raised)."""
+    from dexrobot_isaac_amd.config import OBS_KEYS, default_cfg
+    from dexrobot_isaac_amd.hand_model import HandModel
+    model, out = HandModel(), {}
+    for task in ("BaseTask", "BlindGrasping"):
+        accepted, refused = [], {}
+        for key, _ in OBS_KEYS:
+            cfg = default_cfg(task)
+            cfg["env"]["numEnvs"] = 2
+            cfg["task"]["policy_observation_keys"] = [key]
+            try:
+                FakeParent(cfg, model, task, [])
+                accepted.append(key)
+            except (RuntimeError, IndexError) as e:
+                refused[key] = f"{type(e).__name__}: {e}"
+        out[task] = {"accepted": accepted, "refused": refused}
+        print(f"policy keys {task}: {len(accepted)} accepted, refused {sorted(refused)}")
+    path = os.path.join(HERE, "reference_policy_keys.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     if not os.path.isdir(REF):
         print("reference not present; nothing generated")
@@ -708,13 +971,20 @@ def main():
     sys.path.insert(0, REF)
     n = pin_quaternion_standins()
     print(f"reference utils/test_coordinate_transforms.py: all cases passed against stand-ins ({n} PASSED lines)")
+    if not only or "keys" in only:
+        record_accepted_policy_keys()
     # round-1 scenarios (N = 6..12) + round-2 scenarios: two workgroups incl. a padded one (N = 70), explicit reset_idx
     # events, per-step snapshots of every obs_dict key / reward component, and a default-length FSM run (stage 2, 3, success)
     table = [("blind_default", 8, 40, 11, None, ()), ("blind_fast", 12, 60, 12, None, ()),
              ("base_default", 6, 45, 13, None, ()), ("base_position", 6, 20, 14, None, ()),
              ("blind_wide", 70, 26, 15, {9: [3, 17, 65, 69], 20: [0, 64]}, (2, 6, 8, 13, 17, 21, 25)),
              ("base_wide", 70, 10, 16, {4: [1, 66]}, (0, 5, 9)),
-             ("blind_long", 6, 345, 17, None, (197, 198, 199, 226, 227, 228, 327, 328, 344))]
+             ("blind_long", 6, 345, 17, None, (197, 198, 199, 226, 227, 228, 327, 328, 344)),
+             # non-default configurations on the margins profile (CFG_SCENARIOS); snapshots include steps with resets
+             ("blind_cfg_fingers", 12, 40, 21, None, (1, 4, 7, 10, 11, 16, 27)),
+             ("blind_cfg_base", 70, 11, 22, {3: [2, 12, 64, 69], 7: [0, 65]}, (4, 9)),
+             ("base_cfg_fingers", 8, 20, 23, None, (2, 3, 8, 15)),
+             ("base_cfg_base", 8, 16, 24, {5: [1, 6]}, (2, 3, 6, 12))]
     for name, N, T, seed, events, snap in table:
         if only and name not in only:
             continue

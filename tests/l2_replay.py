@@ -22,7 +22,8 @@ def scenario_config(npz, num_envs=None):
     return cfg
 
 
-ALL_SCENARIOS = ["blind_default", "blind_fast", "base_default", "base_position", "blind_wide", "base_wide", "blind_long"]
+ALL_SCENARIOS = ["blind_default", "blind_fast", "base_default", "base_position", "blind_wide", "base_wide", "blind_long",
+                 "blind_cfg_fingers", "blind_cfg_base", "base_cfg_fingers", "base_cfg_base"]
 
 
 def check_reward_table(rc, names, values, cmp, tag):
@@ -121,6 +122,12 @@ def replay(backend, npz, atol=2e-5, rtol=1e-5, check=True):
         cmp("rew_total", backend.get("rew_comp")[52], npz["rew_total"][t], a=2e-3, r=2e-6)
         if "stats" in npz.files:                            # success / failure / timeout rate, consecutive successes
             cmp("stats", backend.stats()[[12, 13, 14, 15]], npz["stats"][t][:4], a=1e-6)
+        if "crit_fail" in npz.files:                        # margins scenarios: every criterion's raw condition, active or not,
+            cmp("crit_fail", backend.get("crit_failure"), npz["crit_fail"][t], a=0.0, r=0.0)      # and the binary observations
+            cmp("crit_succ", backend.get("crit_success"), npz["crit_succ"][t], a=0.0, r=0.0)
+            oa = backend.get("obs_all")
+            got = np.concatenate([oa[offs[k][0]:offs[k][0] + offs[k][1]] for k in json.loads(str(npz["binary_keys"]))]).T
+            cmp("binaries", got, npz["binaries"][t], a=0.0, r=0.0)
         if t in snaps:                                      # every obs_dict key and every reward component of this step
             oa = backend.get("obs_all")
             want, col = npz["snap_obs_all"][snaps[t]], 0

@@ -91,3 +91,16 @@ def test_bad_arguments_are_rejected(lib):
     assert lib.dexsim_create(C.byref(sc), C.byref(ms), 0, C.byref(h)) == 1
     assert b"prismatic" in lib.dexsim_last_error()
     assert lib.dexsim_step(None, None, None) == 1
+
+
+def test_observation_table_longer_than_the_column_table_is_rejected(lib):
+    """Twelve in-range segments that sum to 393 columns: dexsim_create must refuse them before it fills obs_col_row[392]."""
+    sc, model = build_sim_config(default_cfg("BaseTask"))
+    ms = model.to_struct()
+    h = C.c_void_p()
+    for i in range(12):
+        sc.obs_seg_off[i], sc.obs_seg_len[i] = 194, 35          # fingertip_poses_world
+    sc.obs_seg_len[11] = 8
+    sc.n_obs_seg, sc.num_obs = 12, 11 * 35 + 8
+    assert lib.dexsim_create(C.byref(sc), C.byref(ms), 0, C.byref(h)) == 1
+    assert b"column table" in lib.dexsim_last_error()

@@ -128,14 +128,13 @@ def test_reset_idx_and_hooks():
 
 def test_pre_action_rule_follows_the_reference_ordering():
     """step_processor.py:56-77: the custom pre-action rule runs between compute_observations and
-    concatenate_observations, on the terminal obs_dict and the PRE-reset active_prev_targets, and its output is what the
-    policy sees when active_rule_targets is a policy observation key; reset() runs it in both observation passes
-    (dexhand_base.py:805-838)."""
+    concatenate_observations, on the terminal obs_dict and the PRE-reset active_prev_targets, and its output is the
+    obs_dict's active_rule_targets entry (the reference refuses that name as a policy observation key: obs_buf cannot carry
+    it); reset() runs it in both observation passes (dexhand_base.py:805-838)."""
     cfg = default_cfg("BlindGrasping")
     cfg["env"]["episodeLength"] = 4                              # time-outs -> in-step resets at step 3
-    cfg["task"]["policy_observation_keys"] = list(cfg["task"]["policy_observation_keys"]) + ["active_rule_targets"]
     env = make_env("BlindGrasping", 5, "cpu", "cpu", 0, cfg=cfg, _core_factory=OracleCore)
-    assert env.num_observations == 158 + 18
+    assert env.num_observations == 158
     seen = []
 
     def rule(prev, state):
@@ -147,17 +146,63 @@ def test_pre_action_rule_follows_the_reference_ordering():
     env.action_processor.set_pre_action_rule(rule)
     env.reset()
     assert len(seen) == 2                                        # both observation passes of reset()
-    sl = env.observation_encoder.component_slice_indices["active_rule_targets"]
-    assert torch.allclose(env.obs_buf[:, sl[0] + 3], torch.full((5,), 0.27))
+    assert torch.allclose(env.get_observations_dict()["active_rule_targets"][:, 3], torch.full((5,), 0.27))
     done_seen = False
     for t in range(5):
         obs, rew, done, _ = env.step(0.5 * torch.ones(5, 18))
         prev, ob_prev, _ = seen[-1]
         assert torch.equal(prev, ob_prev)                        # the rule got the pre-reset targets (the obs_dict entry)
-        assert torch.allclose(obs[:, sl[0] + 3], torch.full((5,), 0.25 + 0.01 * len(seen)))   # ... and the policy sees its output
-        assert torch.allclose(env.action_processor.active_rule_targets[:, 3], obs[:, sl[0] + 3])
+        art = env.get_observations_dict()["active_rule_targets"]
+        assert torch.allclose(art[:, 3], torch.full((5,), 0.25 + 0.01 * len(seen)))   # ... and obs_dict carries its output
+        assert torch.allclose(env.action_processor.active_rule_targets[:, 3], art[:, 3])
         if bool(done.any()):
             done_seen = True
             # after an in-step reset the field holds the post-reset targets, the rule was still given the terminal ones
             assert not torch.equal(env.action_processor.active_prev_targets, ob_prev)
     assert done_seen
+
+
+@pytest.mark.parametrize("task", ["BaseTask", "BlindGrasping"])
+def test_policy_observation_keys_accepted_are_the_references(golden_dir, task):
+    """build_sim_config accepts as a policy observation key exactly the names the reference's own ObservationEncoder.initialize
+    accepted (recorded by tests/golden/generate_golden.py in reference_policy_keys.json), and raises the reference's exception
+    with the reference's message for every other name of OBS_KEYS."""
+    import builtins
+    import json
+    import os
+    import re
+    from dexrobot_isaac_amd.config import OBS_KEYS, build_sim_config, obs_key_offsets, policy_observation_keys_accepted
+    with open(os.path.join(golden_dir, "reference_policy_keys.json")) as f:
+        rec = json.load(f)[task]
+    names = [k for k, _ in OBS_KEYS]
+    assert sorted(rec["accepted"] + list(rec["refused"])) == sorted(names)
+    assert "active_rule_targets" in rec["refused"]
+    assert policy_observation_keys_accepted(task) == rec["accepted"]
+    for key in names:
+        cfg = default_cfg(task)
+        cfg["task"]["policy_observation_keys"] = [key]
+        if key in rec["accepted"]:
+            sc, _ = build_sim_config(cfg)
+            dim = int(sc.num_actions) if key == "prev_actions" else obs_key_offsets()[key][1]
+            assert (int(sc.n_obs_seg), int(sc.num_obs), int(sc.obs_seg_off[0])) == (1, dim, obs_key_offsets()[key][0])
+        else:
+            exc, msg = rec["refused"][key].split(": ", 1)
+            with pytest.raises(getattr(builtins, exc), match=re.escape(msg)):
+                build_sim_config(cfg)
+            with pytest.raises(getattr(builtins, exc), match=re.escape(msg)):      # ... also behind accepted keys
+                cfg["task"]["policy_observation_keys"] = ["base_dof_pos", key]
+                build_sim_config(cfg)
+
+
+def test_policy_observation_keys_longer_than_the_column_table_are_refused():
+    """A key list may repeat keys (the reference concatenates them again), but obs_buf's column table holds one entry per
+    obs_dict row (392): the largest list that fits is accepted, one more key is refused by build_sim_config."""
+    from dexrobot_isaac_amd import _abi
+    from dexrobot_isaac_amd.config import build_sim_config
+    cfg = default_cfg("BaseTask")
+    cfg["task"]["policy_observation_keys"] = ["fingertip_poses_world"] * 11 + ["hand_pose"]          # 11 * 35 + 7 = 392
+    sc, _ = build_sim_config(cfg)
+    assert int(sc.num_obs) == _abi.OBS_ALL_DIM == 392 and int(sc.n_obs_seg) == 12
+    cfg["task"]["policy_observation_keys"] = ["fingertip_poses_world"] * 11 + ["hand_pose", "episode_time"]
+    with pytest.raises(RuntimeError, match="at most 392"):
+        build_sim_config(cfg)

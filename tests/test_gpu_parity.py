@@ -42,6 +42,10 @@ def test_hip_l2_replays_reference_golden(golden_dir, name):
     assert any(k.startswith("final:") for k in err) and any(k.startswith("final_rc:") for k in err) and "stats" in err
     if name in ("blind_wide", "base_wide"):
         assert any(k.startswith("ev:") for k in err) and any(k.startswith("snap:") for k in err) and any(k.startswith("snap_rc:") for k in err)
+    if "_cfg_" in name:       # non-default configurations: snapshots, every criterion's raw condition, the binary observations
+        assert any(k.startswith("snap:") for k in err) and any(k.startswith("snap_rc:") for k in err)
+        assert err["crit_fail"] == 0 and err["crit_succ"] == 0 and err["binaries"] == 0
+        assert ("ev:targets" in err) == (name in ("blind_cfg_base", "base_cfg_base"))
 
 
 def _random_state(rng, model, n, near_box=True):
@@ -710,12 +714,17 @@ def test_fused_step_equals_staged_step_bitwise(task, substeps):
     every output and the whole carried state must be BIT-identical.  k_actions runs the production action block itself, so
     this ties the fused production post block (7 waves, box-wave pre-tasks) to the stand-alone k_post that the golden
     replays exercise, and the action block inside a physics launch to the same block launched alone."""
-    import torch
-    from tests.hip_backend import HipBackend
     n = 200                                                  # 4 workgroups, the last one padded
     sc, model = _mk(task, n, **{"env.episodeLength": 7, "sim.substeps": substeps})
     assert int(sc.substeps) == substeps
+    _fused_equals_staged_bitwise(sc, model, task, n)
+
+
+def _fused_equals_staged_bitwise(sc, model, task, n):
+    import torch
+    from tests.hip_backend import HipBackend
     ms = model.to_struct()
+    na = int(sc.num_actions)
     a, b = HipBackend(sc, ms), HipBackend(sc, ms)
     a.reset(); b.reset()
     g = torch.Generator(device="cuda:0").manual_seed(77)
@@ -725,7 +734,7 @@ def test_fused_step_equals_staged_step_bitwise(task, substeps):
              (("box_pos", "box_quat", "box_lin", "current_stage", "time_in_stage") if task == "BlindGrasping" else ())
     resets = 0
     for t in range(10):
-        act = 2 * torch.rand(n, 18, device="cuda:0", generator=g) - 1
+        act = 2 * torch.rand(n, na, device="cuda:0", generator=g) - 1
         a.core.step(act)
         b.core.process_actions(act)
         b.core.physics_step(False)
@@ -739,6 +748,27 @@ def test_fused_step_equals_staged_step_bitwise(task, substeps):
             assert np.array_equal(a.get(f), b.get(f)), (t, f)
         resets += int(a.core.reset_buf.sum())
     assert resets >= n                                       # time-outs at step 6: the reset path was part of the comparison
+
+
+def _golden_cfg(golden_dir, name, n, **over):
+    """The resolved cfg of a golden scenario (its recorded cfg_overrides on the task defaults) for n envs."""
+    from tests.l2_replay import scenario_config
+    cfg = scenario_config(np.load(os.path.join(golden_dir, f"l2_{name}.npz"), allow_pickle=False), num_envs=n)
+    cfg["env"].update(over)
+    return cfg
+
+
+@pytest.mark.parametrize("name,task,na,nobs", [("blind_cfg_fingers", "BlindGrasping", 12, 106), ("base_cfg_base", "BaseTask", 6, 82)])
+def test_fused_step_equals_staged_step_bitwise_at_non_default_configurations(golden_dir, name, task, na, nobs):
+    """test_fused_step_equals_staged_step_bitwise (same body, same fields) away from the defaults: the golden replays pin the
+    stand-alone stages at these configurations, this ties the production step's fused action and post blocks to them.
+    blind_cfg_fingers: fingers-only policy (12 actions), an 11-key permuted observation list with keys from neither default
+    list, a failure-criteria subset, every threshold / decay / weight changed; base_cfg_base: base-only policy (6 actions),
+    six non-default keys, changed velocity limits and weights.  N = 200, episodeLength 7, 10 steps with in-step resets."""
+    n = 200
+    sc, model = build_sim_config(_golden_cfg(golden_dir, name, n, episodeLength=7))
+    assert (int(sc.num_actions), int(sc.num_obs), int(sc.episode_length)) == (na, nobs, 7)
+    _fused_equals_staged_bitwise(sc, model, task, n)
 
 
 @pytest.mark.parametrize("zero_targets", [False, True], ids=["targets", "zero_targets"])
@@ -1367,3 +1397,55 @@ def test_make_env_product_path_tight_without_contacts():
         resets += int(dr.sum())
     assert resets >= 2 * n
     env.close()
+
+
+@pytest.mark.gpu
+def test_make_env_product_path_at_a_non_default_configuration(golden_dir):
+    """The product surface (make_env().step()) at the base_cfg_fingers configuration -- BaseTask, fingers-only policy (12
+    actions), position mode, an 8-key non-default observation list, height and contact thresholds, finger velocity limit --
+    against the oracle behind the same surface: obs 1e-4 abs, reward and every reward component 1e-4 abs + 1e-5 rel (the
+    bounds of test_make_env_product_path_tight_without_contacts: no contacts here either), done flags / extras masks /
+    episode_length exact, 12 steps with in-step resets at episodeLength 8.  A third env in env.obsDict = 'policy' mode returns
+    the same bits as the default mode and serves the configured keys, concatenated, as obs_buf.  The action copy and the
+    prev_actions segment of obs_buf (12 wide) hold the step's actions exactly."""
+    import torch
+    from dexrobot_isaac_amd import make_env
+    from oracle.py_backend import OracleCore
+    n = 96
+    cfg = _golden_cfg(golden_dir, "base_cfg_fingers", n, episodeLength=8)
+    keys = cfg["task"]["policy_observation_keys"]
+    pcfg = _golden_cfg(golden_dir, "base_cfg_fingers", n, episodeLength=8, obsDict="policy")
+    env = make_env("BaseTask", n, "cuda:0", "cuda:0", 0, cfg=cfg)
+    pol = make_env("BaseTask", n, "cuda:0", "cuda:0", 0, cfg=pcfg)
+    ref = make_env("BaseTask", n, "cpu", "cpu", 0, cfg=cfg, _core_factory=OracleCore)
+    assert (env.num_actions, ref.num_actions, env.num_observations, ref.num_observations) == (12, 12, 85, 85)
+    assert keys[2] == "prev_actions" and keys != default_cfg("BaseTask")["task"]["policy_observation_keys"]
+    o0 = env.reset()
+    np.testing.assert_allclose(o0.cpu().numpy(), ref.reset().numpy(), atol=1e-5)
+    assert torch.equal(pol.reset(), o0)
+    lo, hi = env.observation_encoder.component_slice_indices["prev_actions"]
+    assert hi - lo == 12
+    g = torch.Generator().manual_seed(21)
+    resets = 0
+    for t in range(12):
+        a = 2 * torch.rand(n, 12, generator=g) - 1
+        og, rg, dg, ig = env.step(a.cuda())
+        op, rp, dp, _ = pol.step(a.cuda())
+        orr, rr, dr, ir = ref.step(a)
+        assert torch.equal(og, op) and torch.equal(rg, rp) and torch.equal(dg, dp)
+        assert torch.equal(env.actions.cpu(), a) and torch.equal(og[:, lo:hi].cpu(), a) and torch.equal(orr[:, lo:hi], a)
+        np.testing.assert_allclose(og.cpu().numpy(), orr.numpy(), atol=1e-4)
+        np.testing.assert_allclose(rg.cpu().numpy(), rr.numpy(), atol=1e-4, rtol=1e-5)
+        assert (dg.cpu() == dr).all()
+        for k in ("success", "failure", "timeout"):
+            assert (ig[k].cpu() == ir[k]).all()
+        assert (ig["episode_length"].cpu() == ir["episode_length"]).all()
+        assert set(ig["reward_components"]) == set(ir["reward_components"])
+        for k, v in ir["reward_components"].items():
+            np.testing.assert_allclose(ig["reward_components"][k].cpu().numpy(), v.numpy(), atol=1e-4, rtol=1e-5, err_msg=k)
+        for e in (env, pol):
+            od = e.get_observations_dict()
+            assert torch.equal(torch.cat([od[k] for k in keys], dim=1), e.obs_buf)
+        resets += int(dr.sum())
+    assert set(pol.get_observations_dict()) == set(keys) and resets >= n
+    env.close(), pol.close()
