@@ -1623,8 +1623,11 @@ __global__ __launch_bounds__(64) void k_solve(Arena A, const DevParams* __restri
   for (int k = 0; k < min(kmax, 4); k++) nbg += (k < nc && (__float_as_int(s_hdr[(4 * k) * 64 + lane]) & 3) == 2) ? 1 : 0;
   if (hand_mask == 0 && kmax <= 4 && kmax <= kst) {
     // ---- only box/ground contacts in the whole wavefront: one block, nothing is split (the early box solve of the fused kernel)
+    // (nc_lane = nc: a lane with fewer contacts than the wave's kmax has zero rows staged for the slots behind its own, but the block
+    // computes 1/D itself -- 1 / (1/m + 1e-9) for a zero lever arm -- so a slot taken as present would act as a frictionless support
+    // under the box centre whenever the box moves down)
     BoxBlock bb;
-    bb.load<true>(kmax, inv_m, inv_I, s_lam, s_hdr, s_row, CROW_W, 20, lane, -1, true);
+    bb.load<true>(kmax, inv_m, inv_I, s_lam, s_hdr, s_row, CROW_W, 20, lane, nc, true);
     f2 v01 = {vb[0], vb[1]}, v23 = {vb[2], wb[0]}, v45 = {wb[1], wb[2]};
     bb.warm(v01, v23, v45, f2{inv_m, inv_I});
 #pragma unroll 1

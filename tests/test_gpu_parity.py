@@ -487,19 +487,25 @@ def test_step_timing_and_step_stage_entry_points():
     assert t > 0
 
 
-@pytest.mark.parametrize("near_box", [False, True], ids=["hand_clear", "contacts"])
+@pytest.mark.parametrize("near_box", [False, True, "box_alone", "hand_on_box"], ids=["hand_clear", "contacts", "tumbled_box_alone", "hand_on_tumbled_box"])
 def test_fused_physics_launch_equals_four_single_substep_launches(near_box):
     """k_physics4 inlines the sub-step body four times; four k_physics1 launches run the same body once each.  State after
     one sim.dt must be bit-identical (the early box solve splits its sweeps around a barrier but performs the same
-    arithmetic sequence; contact forces do not feed back)."""
+    arithmetic sequence; contact forces do not feed back).  The tumbled samples (tests/tumbled_states.py, N = 256) add corner
+    lists other than 0-3, slots that change their corner within the four sub-steps, and edge / vertex hand contacts."""
     import torch
     from dexrobot_isaac_amd import _abi
     from tests.hip_backend import HipBackend
-    n = 192
+    tumbled = isinstance(near_box, str)
+    n = 256 if tumbled else 192
     sc, model = _mk("BlindGrasping", n)
     ms = model.to_struct()
     a, b = HipBackend(sc, ms), HipBackend(sc, ms)
-    st = _random_state(np.random.default_rng(23), model, n, near_box=near_box)
+    if tumbled:
+        from tests.tumbled_states import sample
+        st = sample(near_box, n, 11)
+    else:
+        st = _random_state(np.random.default_rng(23), model, n, near_box=near_box)
     for k, v in st.items():
         a.set(k, v)
         b.set(k, v)

@@ -1,0 +1,157 @@
+"""Seeded states with a TUMBLED box for the physics parity tests (tests/test_tumbled_box.py, tests/test_gpu_parity.py).  Plain numpy.
+
+test_gpu_parity._random_state only yaws the box, so it always rests on its -z face: the box wave then lists corners 0, 1, 2, 3 or
+nothing, a cache slot 80 + k never changes its corner, and the hand meets faces.  The states here put the box on one or two corners, on
+another face, on an edge and anywhere in between, with the lowest corner within the contact band of the ground, so that the corner list,
+its warm-start tags and the edge / vertex branches of the narrowphase all see more than one input.
+
+Every array is [rows][n] float64 holding float32-representable numbers: the fp64 oracle, the fp32 oracle and the kernels start from the
+very same state.  Quaternions are (x, y, z, w).
+"""
+import functools
+
+import numpy as np
+
+CORNERS = np.array([[(1 if i & 1 else -1), (1 if i & 2 else -1), (1 if i & 4 else -1)] for i in range(8)], dtype=np.float64)
+
+
+def _f32(x):
+    return np.asarray(x, dtype=np.float32).astype(np.float64)
+
+
+def quat_mul(a, b):
+    """Hamilton product a * b of (x, y, z, w) rows ((n, 4) arrays): the rotation b followed by the rotation a."""
+    ax, ay, az, aw = a.T
+    bx, by, bz, bw = b.T
+    return np.stack([aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx,
+                     aw * bz + ax * by - ay * bx + az * bw,
+                     aw * bw - ax * bx - ay * by - az * bz], 1)
+
+
+def axis_quat(axis, angle):
+    """(n, 4) rotations by `angle` (n,) about the coordinate axis `axis` (0, 1, 2; a number or an (n,) array)."""
+    angle = np.asarray(angle, dtype=np.float64)
+    q = np.zeros((angle.shape[0], 4))
+    q[np.arange(angle.shape[0]), np.broadcast_to(axis, angle.shape)] = np.sin(0.5 * angle)
+    q[:, 3] = np.cos(0.5 * angle)
+    return q
+
+
+def quat_to_mat(q):
+    """(n, 3, 3) world <- box rotation matrices of (n, 4) unit quaternions."""
+    x, y, z, w = q.T
+    return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], 1),
+                     np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], 1),
+                     np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1)], 1)
+
+
+def box_orientations(rng, n):
+    """(n, 4) unit quaternions: a random yaw composed with one of four classes, env i of class i % 4 (equal quarters, every class in
+    every workgroup):
+      0 random     uniform on the sphere
+      1 on an edge 45 deg about x, N(0, 0.02 rad) noise
+      2 other face +90 / -90 / 180 deg about x or 90 deg about y, times tilts of N(0, 0.004 rad) about x and about y (the four ground
+                   contacts get different gaps)
+      3 toppling   a tilt of U(0.02, pi/4 - 0.02) about x or y"""
+    cls = np.arange(n) % 4
+    q = np.zeros((n, 4))
+    rnd = rng.normal(size=(n, 4))
+    rnd /= np.linalg.norm(rnd, axis=1, keepdims=True)
+    edge = axis_quat(0, np.pi / 4 + rng.normal(0, 0.02, n))
+    pick = rng.integers(0, 4, n)
+    face = axis_quat(np.where(pick == 3, 1, 0), np.array([np.pi / 2, -np.pi / 2, np.pi, np.pi / 2])[pick])
+    face = quat_mul(axis_quat(0, rng.normal(0, 0.004, n)), quat_mul(axis_quat(1, rng.normal(0, 0.004, n)), face))
+    topple = axis_quat(rng.integers(0, 2, n), rng.uniform(0.02, np.pi / 4 - 0.02, n))
+    for c, src in enumerate((rnd, edge, face, topple)):
+        q[cls == c] = src[cls == c]
+    q = quat_mul(axis_quat(2, rng.uniform(-np.pi, np.pi, n)), q)
+    return q / np.linalg.norm(q, axis=1, keepdims=True)
+
+
+def corner_heights(quat, box_size):
+    """(n, 8) heights of the eight corners (index order of the kernels: bit 0 x, bit 1 y, bit 2 z) above the box centre."""
+    return 0.5 * box_size * np.einsum("nj,cj->nc", quat_to_mat(quat)[:, 2, :], CORNERS)
+
+
+def _place_box(rng, st, n, box_size, low_mm):
+    """Tumbled orientation; the height puts the lowest corner at U(low_mm) millimetres above the ground."""
+    quat = _f32(box_orientations(rng, n))
+    quat = _f32(quat / np.linalg.norm(quat, axis=1, keepdims=True))        # float32 numbers, unit to float32 roundoff
+    st["box_quat"] = quat.T.copy()
+    st["box_pos"][2] = 1e-3 * rng.uniform(low_mm[0], low_mm[1], n) - corner_heights(quat, box_size).min(1)
+
+
+def _base_state(rng, model, n, near_box):
+    from tests.test_gpu_parity import _random_state
+    return _random_state(rng, model, n, near_box=near_box)
+
+
+def hand_clear_state(rng, model, n, box_size=0.05):
+    """The box alone: the hand holds still well above it (a moving hand comes down on things within ~6 sub-steps), the box tumbles
+    with its lowest corner at U(-0.5, 1.5) mm."""
+    st = _base_state(rng, model, n, False)
+    st["q"][2] = rng.uniform(0.0, 0.2, n)
+    st["q"] = _f32(st["q"])
+    st["qd"] = np.zeros((26, n))
+    st["targets"] = st["q"].copy()
+    _place_box(rng, st, n, box_size, (-0.5, 1.5))
+    st["box_ang"] = rng.normal(0, 1.5, (3, n))
+    st["box_lin"] = rng.normal(0, 0.05, (3, n))
+    return {k: _f32(v) for k, v in st.items()}
+
+
+def hand_on_box_state(rng, model, sc, ms, n):
+    """The hand on a tumbled box (lowest corner at U(-0.3, 0.8) mm).  The hand's height is found per env on a SEPARATE fp64 oracle
+    instance (an instance that placed the hand keeps its warm-start cache): the slide q[2] goes down from +0.05 to -0.44 in 2 mm
+    rungs, the env takes the first rung at which its list has an entry that is not box / ground, minus U(0, 2) mm."""
+    from oracle.oracle import Oracle
+    st = _base_state(rng, model, n, True)
+    st["q"][:2] = rng.uniform(-0.04, 0.04, (2, n))
+    st["box_pos"][:2] *= 0.5
+    st["qd"] *= 0.3
+    st["box_ang"] = rng.normal(0, 0.5, (3, n))
+    _place_box(rng, st, n, float(sc.box_size), (-0.3, 0.8))
+    st = {k: _f32(v) for k, v in st.items()}
+    lad = Oracle(sc, ms, f64=True)
+    rungs = _f32(np.arange(0.05, -0.44 - 1e-9, -0.002))
+    first = np.full(n, -1)
+    nbg = None
+    for i, z in enumerate(rungs):
+        for k, v in st.items():                      # the sub-step integrates: every rung starts from the state itself
+            lad.set(k, v)
+        q = st["q"].copy()
+        q[2] = z
+        lad.set("q", q)
+        lad.substep(last=True)
+        nc = lad.get("ncontact")[0].astype(int)
+        if nbg is None:                              # top rung: the hand is far above everything, the list is the box's corners
+            nbg = nc
+            assert all((lad.contacts(e)[:, 8] == 2).all() for e in range(n))
+        first = np.where((first < 0) & (nc > nbg), i, first)
+        if (first >= 0).all():
+            break
+    assert (first >= 0).all(), "a hand never reached box or ground"
+    st["q"][2] = _f32(rungs[first] - 1e-3 * rng.uniform(0.0, 2.0, n))
+    tg = st["q"] + rng.normal(0, 0.03, (26, n))
+    tg[2] = st["q"][2] - 0.01
+    st["targets"] = _f32(tg)
+    return st
+
+
+@functools.lru_cache(maxsize=None)
+def _cached(kind, n, seed):
+    from dexrobot_isaac_amd.config import build_sim_config, default_cfg
+    cfg = default_cfg("BlindGrasping")
+    cfg["env"]["numEnvs"] = n
+    sc, model = build_sim_config(cfg)
+    rng = np.random.default_rng(seed)
+    if kind == "box_alone":
+        return hand_clear_state(rng, model, n, float(sc.box_size))
+    assert kind == "hand_on_box"
+    return hand_on_box_state(rng, model, sc, model.to_struct(), n)
+
+
+def sample(kind, n=256, seed=11):
+    """The "box_alone" / "hand_on_box" state of n envs (default BlindGrasping configuration), built once per process; a fresh copy."""
+    return {k: v.copy() for k, v in _cached(kind, n, seed).items()}
