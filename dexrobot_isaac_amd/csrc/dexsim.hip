@@ -757,6 +757,7 @@ extern "C" int dexsim_set_step_stamp(dexsim_t h, int stamp) {
 // Templates instantiated here, behind every use of the step kernels, so that the code object keeps the step path's kernels where
 // they were (like the state kernels above).
 // clang-format off
+#include "dexsim_chain.hip.inc"
 #include "dexsim_render.hip.inc"
 // clang-format on
 
@@ -913,7 +914,6 @@ extern "C" int dexsim_solve_ik(dexsim_t h, const int64_t* env_ids, int k, const 
   NEED_BOUND(h);
   K.targets = targets; K.controls = controls; K.q_out = q_out; K.residual = residual;
   K.prm = *prm; K.lam2 = prm->damping * prm->damping;
-  DeviceGuard guard(h->device);
   k_ik_solve<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
   LAUNCH_CHECK();
   return DEXSIM_OK;

@@ -2,9 +2,8 @@
 // least squares on the 18 active targets of the action stage, every iteration inside one launch.  Not on the step path; reads q
 // (arena rows or the caller's override) and the model, writes caller-owned memory only.
 //
-// The conventions are those of dexsim_kindyn.hip.inc: 64 rows per workgroup, wave f walks finger f (kd_load_q, kd_base_walk,
-// kd_finger_joint, sincos_joint), positions relative to the palm joint's origin o5, LDS as [word][row] with stride KD_LD, a `valid`
-// flag per row that only gates stores.  Plain __syncthreads() only: no atomics, no spins.
+// The workgroup is that of dexsim_chain.hip.inc: 64 rows x 5 waves, wave f walks finger f, o5-relative positions, [word][row] LDS,
+// a `valid` flag per row that only gates stores.  Plain __syncthreads() only: no atomics, no spins.
 //
 // A finger's site moves with at most 9 controls, its LOCAL columns: 0-5 the base controls, 6 its "spread" control (control 6 for
 // the thumb, the shared control 9 for index, ring and pinky -- the pinky's DOF turns twice as far --, none for the middle finger,
@@ -50,6 +49,18 @@ __host__ DI constexpr int ik_control(int f, int s) {
 }
 // scale of the finger's first DOF on its spread control
 __host__ DI constexpr float ik_spread_scale(int f) { return f == 2 ? 0.f : f == 4 ? 2.f : 1.f; }
+// the finger whose first DOF is the first of its spread group: that DOF gives the control its start value, that wave stores it
+__host__ DI constexpr bool ik_spread_first(int f) { return f <= 1; }
+
+// control of row i of the shared system: the base controls, then the spread controls in the order of their first fingers
+__host__ DI constexpr int ik_sys_control(int i) { return i < 6 ? i : ik_control(i - 6, 0); }
+static_assert(IK_NSYS == 8 && ik_spread_first(0) && ik_spread_first(1), "the shared system's rows 6 and 7 are the thumb's and the index's spread control");
+// row of the shared system that local column i (< IK_NSH) of finger ff lands on (-1: the middle finger's empty spread column)
+__host__ DI constexpr int ik_sys_row(int ff, int i) {
+  const int c = i < 6 ? i : ik_control(ff, 0);
+  for (int r = 0; r < IK_NSYS; r++) if (ik_sys_control(r) == c) return r;
+  return -1;
+}
 
 // The table above IS kCoupling, read finger by finger: checked here so that the two cannot drift apart.
 constexpr bool ik_table_matches_coupling() {
@@ -60,14 +71,14 @@ constexpr bool ik_table_matches_coupling() {
     else {
       bool hit = false;
       for (int i = 0; i < kCoupling[cs].n; i++) hit = hit || (kCoupling[cs].dof[i] == d0 && kCoupling[cs].scale[i] == ik_spread_scale(f));
-      if (!hit) return false;
+      if (!hit || ik_spread_first(f) != (kCoupling[cs].dof[0] == d0)) return false;
     }
     if (kCoupling[cm].n != 1 || kCoupling[cm].dof[0] != d0 + 1 || kCoupling[cm].scale[0] != 1.f) return false;
     if (kCoupling[cd].n != 2 || kCoupling[cd].dof[0] != d0 + 2 || kCoupling[cd].dof[1] != d0 + 3 || kCoupling[cd].scale[0] != 1.f ||
         kCoupling[cd].scale[1] != 1.f) return false;
   }
   for (int c = 0; c < 6; c++) if (kCoupling[c].n != 1 || kCoupling[c].dof[0] != c) return false;
-  return kCoupling[9].dof[0] == 10 && kCoupling[6].dof[0] == 6;   // the first DOF of a spread group gives its start value
+  return true;
 }
 static_assert(ik_table_matches_coupling(), "k_ik_solve: the per-finger control table differs from kCoupling");
 
@@ -87,8 +98,8 @@ struct IkEval { V3 e; V3 J[IK_NLOC]; float qf[4]; };
 template <bool kJac>
 DI void ik_eval(const DevParams* __restrict__ P, const float* u, int f, int site, int frame, V3 tgt, IkEval& E) {
   const DexHandModel& M = P->model;
-  const float sc = f == 2 ? 0.f : f == 4 ? 2.f : 1.f;
-  E.qf[0] = f == 2 ? 0.f : sc * u[6];   // kHeldDof: +0.0f
+  const float sc = ik_spread_scale(f);
+  E.qf[0] = ik_control(f, 0) < 0 ? 0.f : sc * u[6];   // kHeldDof: +0.0f
   E.qf[1] = u[7];
   E.qf[2] = E.qf[3] = u[8];
   KinBase B;
@@ -148,9 +159,6 @@ DI void ik_chol_solve(float* A, const float* b, float* x) {
   }
 }
 
-// row of the shared system that local column i of finger ff lands on (-1: the middle finger's empty spread column)
-DI constexpr int ik_sys_row(int ff, int i) { return i < 6 ? i : ff == 0 ? 6 : ff == 2 ? -1 : 7; }
-
 template <int ff>
 DI void ik_add_complement(float* A, float* b, const float* src) {
 #pragma unroll
@@ -173,15 +181,16 @@ __global__ __launch_bounds__(KD_THREADS) void k_ik_solve(const DevParams* __rest
   const int site = (K.prm.sites ? 6 : 1) + f, frame = K.prm.frame;
   const unsigned free_mask = K.prm.free_mask;
   const int row = min(blockIdx.x * 64 + lane, K.rows.k - 1);   // every lane reads a legal address
-  // the controls of the wave's local columns (wave-uniform); the middle finger's column 6 is empty: never free, its u is not used
-  const int cs = f == 0 ? 6 : 9, cm = f == 0 ? 7 : f == 1 ? 10 : f == 2 ? 12 : f == 3 ? 14 : 16;
+  // the controls of the wave's local columns (wave-uniform); an empty column (the middle finger's spread) is never free and its u
+  // is not used: it reads control 0, a legal index
   int ctl[IK_NLOC];
   bool fr[IK_NLOC];
   float lo[IK_NLOC], hi[IK_NLOC];
 #pragma unroll
   for (int i = 0; i < IK_NLOC; i++) {
-    ctl[i] = i < 6 ? i : i == 6 ? cs : cm + (i - 7);
-    fr[i] = ((free_mask >> ctl[i]) & 1u) != 0 && !(i == 6 && f == 2);
+    const int c = i < 6 ? i : ik_control(f, i - 6);
+    ctl[i] = max(c, 0);
+    fr[i] = ((free_mask >> ctl[i]) & 1u) != 0 && c >= 0;
     lo[i] = C.active_lower[ctl[i]]; hi[i] = C.active_upper[ctl[i]];
   }
 
@@ -193,9 +202,9 @@ __global__ __launch_bounds__(KD_THREADS) void k_ik_solve(const DevParams* __rest
 #pragma unroll
       for (int j = 0; j < 6; j++) s_w[(IK_U + j) * KD_LD + lane] = clampf(qb[j], lo[j], hi[j]);
     }
-    if (f <= 1) s_w[(IK_U + cs) * KD_LD + lane] = clampf(qf[0], lo[6], hi[6]);
-    s_w[(IK_U + cm) * KD_LD + lane] = clampf(qf[1], lo[7], hi[7]);
-    s_w[(IK_U + cm + 1) * KD_LD + lane] = clampf(qf[2], lo[8], hi[8]);
+    if (ik_spread_first(f)) s_w[(IK_U + ctl[6]) * KD_LD + lane] = clampf(qf[0], lo[6], hi[6]);
+    s_w[(IK_U + ctl[7]) * KD_LD + lane] = clampf(qf[1], lo[7], hi[7]);
+    s_w[(IK_U + ctl[8]) * KD_LD + lane] = clampf(qf[2], lo[8], hi[8]);
   }
   __syncthreads();
   float u[IK_NLOC];
@@ -257,24 +266,24 @@ __global__ __launch_bounds__(KD_THREADS) void k_ik_solve(const DevParams* __rest
       ik_add_complement<4>(As, bs, src + IK_B(4) * KD_LD);
 #pragma unroll
       for (int i = 0; i < IK_NSYS; i++) {
-        const bool fi = (free_mask >> (i < 7 ? i : 9)) & 1u;
+        const bool fi = (free_mask >> ik_sys_control(i)) & 1u;
         As[IK_TRI(i, i)] = fi ? As[IK_TRI(i, i)] + K.lam2 : 1.f;
       }
       ik_chol_solve<IK_NSYS>(As, bs, xs);
 #pragma unroll
-      for (int i = 0; i < IK_NSYS; i++) s_w[(IK_D + (i < 7 ? i : 9)) * KD_LD + lane] = xs[i];
+      for (int i = 0; i < IK_NSYS; i++) s_w[(IK_D + ik_sys_control(i)) * KD_LD + lane] = xs[i];
     }
     __syncthreads();
     {   // ---- the private steps: d_D = L^-T (z - Y^T d_S)
       float t1 = z1, t2 = z2;
 #pragma unroll
       for (int i = 0; i < IK_NSH; i++) {
-        const float ds = (i == 6 && f == 2) ? 0.f : s_w[(IK_D + ctl[i]) * KD_LD + lane];
+        const float ds = (i == 6 && ik_control(f, 0) < 0) ? 0.f : s_w[(IK_D + ctl[i]) * KD_LD + lane];
         t1 -= y1[i] * ds; t2 -= y2[i] * ds;
       }
       const float d8 = t2 * r2, d7 = (t1 - l21 * d8) * r1;
-      s_w[(IK_D + cm) * KD_LD + lane] = d7;
-      s_w[(IK_D + cm + 1) * KD_LD + lane] = d8;
+      s_w[(IK_D + ctl[7]) * KD_LD + lane] = d7;
+      s_w[(IK_D + ctl[8]) * KD_LD + lane] = d8;
     }
     __syncthreads();
     {   // ---- s = min(1, max_step / max |d|), u <- clamp(u + s d)
@@ -298,27 +307,13 @@ __global__ __launch_bounds__(KD_THREADS) void k_ik_solve(const DevParams* __rest
 #pragma unroll
       for (int j = 0; j < 6; j++) { s_w[(IK_Q + j) * KD_LD + lane] = u[j]; s_w[(IK_U + j) * KD_LD + lane] = u[j]; }
     }
-    if (f <= 1) s_w[(IK_U + cs) * KD_LD + lane] = u[6];
-    s_w[(IK_U + cm) * KD_LD + lane] = u[7];
-    s_w[(IK_U + cm + 1) * KD_LD + lane] = u[8];
+    if (ik_spread_first(f)) s_w[(IK_U + ctl[6]) * KD_LD + lane] = u[6];
+    s_w[(IK_U + ctl[7]) * KD_LD + lane] = u[7];
+    s_w[(IK_U + ctl[8]) * KD_LD + lane] = u[8];
   }
   __syncthreads();
 
-  const size_t row0 = (size_t)blockIdx.x * 64;
-  for (int idx = threadIdx.x; idx < 64 * DEXSIM_NACT; idx += KD_THREADS) {
-    const int r = idx / DEXSIM_NACT, c = idx - r * DEXSIM_NACT;
-    if (s_valid[r]) GPTR(K.controls)[(row0 + r) * DEXSIM_NACT + c] = s_w[(IK_U + c) * KD_LD + r];
-  }
-  if (K.q_out) {
-    for (int idx = threadIdx.x; idx < 64 * DEXSIM_NJ; idx += KD_THREADS) {
-      const int r = idx / DEXSIM_NJ, j = idx - r * DEXSIM_NJ;
-      if (s_valid[r]) GPTR(K.q_out)[(row0 + r) * DEXSIM_NJ + j] = s_w[(IK_Q + j) * KD_LD + r];
-    }
-  }
-  if (K.residual) {
-    for (int idx = threadIdx.x; idx < 64 * DEXSIM_NFINGER; idx += KD_THREADS) {
-      const int r = idx / DEXSIM_NFINGER, c = idx - r * DEXSIM_NFINGER;
-      if (s_valid[r]) GPTR(K.residual)[(row0 + r) * DEXSIM_NFINGER + c] = s_w[(IK_RES + c) * KD_LD + r];
-    }
-  }
+  kd_flush<false>(s_w, s_valid, IK_U, DEXSIM_NACT, K.controls);
+  if (K.q_out) kd_flush<false>(s_w, s_valid, IK_Q, DEXSIM_NJ, K.q_out);
+  if (K.residual) kd_flush<false>(s_w, s_valid, IK_RES, DEXSIM_NFINGER, K.residual);
 }

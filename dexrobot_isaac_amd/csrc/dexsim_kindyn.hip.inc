@@ -3,11 +3,10 @@
 //
 // Two kernels, neither on the step path; both read q (arena rows or the caller's override) and write caller-owned memory only.
 // The outputs are large AoS rows (up to 37 x 156 words of Jacobian, 676 words of M per row), so each kernel works in two phases
-// inside a workgroup of 64 rows x 5 waves:
+// inside the workgroup of dexsim_chain.hip.inc (64 rows x 5 waves, [word][row] LDS, o5-relative positions):
 //
-//   phase A  lanes along the rows; wave f walks the chain of finger f exactly as publish_body and k_render_scene do (6 base
-//            joints, 4 finger joints, sincos_joint, never jframe) and leaves the COMPACT per-row data in LDS as [word][row]
-//            (row stride KD_LD = 65 words: a phase-A write is 64 consecutive banks, a phase-B read of many words of one row is too):
+//   phase A  lanes along the rows; wave f walks the chain of finger f (kd_base_walk, kd_finger_joint) and leaves the COMPACT
+//            per-row data in LDS (a phase-A write is 64 consecutive banks, a phase-B read of many words of one row is too):
 //              k_kin_jacobian  26 world axes, 26 joint origins, the origins of the <= KJ_CHUNK bodies of this workgroup's chunk
 //              k_kin_mass      the 191 unique words of M (21 base + 5 x (10 finger + 24 base-finger)) and 26 gravity words
 //   phase B  all 5 waves along the CONTIGUOUS output index: expand to the dense layout -- cross product a_c x (p_b - o_c) or
@@ -15,84 +14,10 @@
 //
 // Plain __syncthreads() only: no atomics, no spins.  A row >= k or with an id outside [0, num_envs) never writes caller memory.
 //
-// Numerics: every position is taken RELATIVE TO THE PALM JOINT'S ORIGIN o5 (the finger walk starts at 0, the base origins are
-// suffix sums of the walk's own increments), so levers and composite centres are differences of numbers of hand size (< 0.4 m),
+// Numerics: with positions relative to o5 (the finger walk starts at 0, the base origins are suffix sums of the walk's own
+// increments) levers and composite centres are differences of numbers of hand size (< 0.4 m),
 // not of world coordinates; the composites of the CRBA are formed about their own centres of mass in these coordinates.  The
 // spawn position therefore never enters.  Link inertias are general symmetric tensors (rotate_inertia), not DevParams::inertia_diag.
-
-#define KD_LD 65          /* LDS row stride in words: [word][row], padded by one */
-#define KD_THREADS 320    /* 5 waves: wave f walks finger f */
-
-// ---- rows of a call: which env (or which override row) lane l describes
-struct KinRows {
-  const int64_t* env_ids;   // k ids or NULL = identity (state path only)
-  const float* q;           // (k, 26) override or NULL = the arena's q of the row's env
-  int k;
-};
-
-// hand body -> the joint frame it is welded to, as publish_body places them (-1 = the fixed spawn frame)
-__host__ DI int kd_body_joint(int b) {
-  if (b <= 6) return b == 6 ? 5 : b - 1;
-  const int f = (b - 7) / 6, l = (b - 7) - 6 * f;
-  return 6 + 4 * f + (l < 3 ? l : 3);
-}
-
-struct KinBase { V3 a[6], orel[6]; Q4 q[6]; };   // world axes, origins relative to o5, frame orientations of the base joints
-
-// the row's q: 6 base joints + the 4 joints of finger f.  `valid` rows only decide about stores: every lane reads a legal address
-DI bool kd_load_q(const Arena& A, const KinRows& R, int N, int NR, int f, float* qb, float* qf) {
-  const int l = blockIdx.x * 64 + (threadIdx.x & 63);
-  bool valid = l < R.k;
-  if (R.q) {
-    const size_t row = (size_t)min(l, R.k - 1) * DEXSIM_NJ;
-#pragma unroll
-    for (int j = 0; j < 6; j++) qb[j] = GPTR(R.q)[row + j];
-#pragma unroll
-    for (int j = 0; j < 4; j++) qf[j] = GPTR(R.q)[row + 6 + 4 * f + j];
-  } else {
-    long long id = l;
-    if (R.env_ids) id = GPTR(R.env_ids)[min(l, R.k - 1)];
-    valid = valid && id >= 0 && id < NR;
-    const int e = valid ? (int)id : 0;
-#pragma unroll
-    for (int j = 0; j < 6; j++) qb[j] = FLD(q, j);
-#pragma unroll
-    for (int j = 0; j < 4; j++) qf[j] = FLD(q, 6 + 4 * f + j);
-  }
-  return valid;
-}
-
-DI void kd_base_walk(const DevParams* __restrict__ P, const float* qb, KinBase& B) {
-  Q4 qc = q4p(P->model.spawn_quat);
-  V3 inc[6];   // o_j - o_(j-1)
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    V3 d = mul(q2mat(qc), v3p(P->jc[j].poff));
-    const Q4 qz = qmul(qc, q4p(P->jc[j].qoff));
-    const V3 ax = v3p(P->jc[j].axis);
-    const V3 aw = mul(q2mat(qz), ax);
-    Q4 qn = qz;
-    if (j < 3) d += qb[j] * aw;
-    else { float s, c; sincos_joint(0.5f * qb[j], &s, &c); qn = qmul(qz, Q4{ax.x * s, ax.y * s, ax.z * s, c}); }
-    B.a[j] = aw; B.q[j] = qn; inc[j] = d; qc = qn;
-  }
-  B.orel[5] = v3(0, 0, 0);
-#pragma unroll
-  for (int j = 4; j >= 0; j--) B.orel[j] = B.orel[j + 1] - inc[j + 1];
-}
-
-// one joint of a finger chain: parent frame (of, qf) -> this joint's origin, world axis and frame
-DI void kd_finger_joint(const JC& c, float qj, V3& of, Q4& qf, V3& aw) {
-  of = of + mul(q2mat(qf), v3p(c.poff));
-  const Q4 qz = qmul(qf, q4p(c.qoff));
-  const V3 ax = v3p(c.axis);
-  aw = mul(q2mat(qz), ax);
-  float s, cs;
-  sincos_joint(0.5f * qj, &s, &cs);
-  qf = qmul(qz, Q4{ax.x * s, ax.y * s, ax.z * s, cs});
-}
-
-#define KD_PUT3(w, v) { s_w[((w) + 0) * KD_LD + lane] = (v).x; s_w[((w) + 1) * KD_LD + lane] = (v).y; s_w[((w) + 2) * KD_LD + lane] = (v).z; }
 
 // -------------------------------------------------------------------------------------------------- body Jacobians
 #define KJ_CHUNK 10                      /* bodies per workgroup (grid y): 37 bodies = 10 + 10 + 10 + 7 */
@@ -180,13 +105,14 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_jacobian(const DevParams* __
 }
 
 // -------------------------------------------------------------------------------------------------- mass matrix and gravity force
-// LDS words per finger f at KM_FINGER(f): [0, 10) lower triangle of the finger's 4 x 4 block (row l, column l2 <= l at
-// l (l + 1) / 2 + l2), [10, 34) coupling of finger joint l with base joint k at 10 + 6 l + k, [34, 38) gravity.  The base pass
-// (wave 0) reads the five finger composites from KM_BASE + [0, 50) and then writes its own 21 + 6 words over them: that column of
-// the region belongs to its lane alone.
-#define KM_FWORDS 38
-#define KM_FINGER(f) ((f) * KM_FWORDS)
-#define KM_BASE (DEXSIM_NFINGER * KM_FWORDS)   /* [0, 21) lower triangle of the base block, [21, 27) gravity */
+// LDS words: the gravity force of joint j at KM_GRAV + j, as it leaves.  Per finger f at KM_FINGER(f): [0, 10) lower triangle of
+// the finger's 4 x 4 block (row l, column l2 <= l at l (l + 1) / 2 + l2), [10, 34) coupling of finger joint l with base joint k at
+// 10 + 6 l + k.  The base pass (wave 0) reads the five finger composites from KM_BASE + [0, 50) and then writes the 21 words of
+// its own block over them: that column of the region belongs to its lane alone.
+#define KM_GRAV 0                              /* [26] gravity force */
+#define KM_FWORDS 34
+#define KM_FINGER(f) (DEXSIM_NJ + (f) * KM_FWORDS)
+#define KM_BASE KM_FINGER(DEXSIM_NFINGER)      /* [0, 21) lower triangle of the base block */
 #define KM_COMP_WORDS 10                       /* m, c (3), I (6) of a finger's composite */
 #define KM_WORDS (KM_BASE + DEXSIM_NFINGER * KM_COMP_WORDS)
 #define KM_ROW (DEXSIM_NJ * DEXSIM_NJ)
@@ -255,7 +181,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_mass(const DevParams* __rest
 #pragma unroll
       for (int k = 0; k < 6; k++)
         s_w[(F + 10 + 6 * i + k) * KD_LD + lane] = k < 3 ? dot(B.a[k], Pm) : dot(B.a[k], L + cross(comp[i].c - B.orel[k], Pm));
-      s_w[(F + 34 + i) * KD_LD + lane] = -dot(g, Pm);
+      s_w[(KM_GRAV + 6 + 4 * f + i) * KD_LD + lane] = -dot(g, Pm);
     }
     {   // the finger's composite for the base pass
       const int W = KM_BASE + KM_COMP_WORDS * f;
@@ -280,17 +206,19 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_mass(const DevParams* __rest
         c.I = S6{w[4 * KD_LD], w[5 * KD_LD], w[6 * KD_LD], w[7 * KD_LD], w[8 * KD_LD], w[9 * KD_LD]};
         comp_add(H, c);
       }
-      float out[27];
+      float out[21], grav[6];
 #pragma unroll
       for (int i = 0; i < 6; i++) {
         const V3 Pm = H.m * (i < 3 ? B.a[i] : cross(B.a[i], H.c - B.orel[i]));
         const V3 L = i < 3 ? v3(0, 0, 0) : mul(H.I, B.a[i]);
 #pragma unroll
         for (int k = 0; k <= i; k++) out[i * (i + 1) / 2 + k] = k < 3 ? dot(B.a[k], Pm) : dot(B.a[k], L + cross(H.c - B.orel[k], Pm));
-        out[21 + i] = -dot(g, Pm);
+        grav[i] = -dot(g, Pm);
       }
 #pragma unroll
-      for (int i = 0; i < 27; i++) s_w[(KM_BASE + i) * KD_LD + lane] = out[i];   // over the composites: all of them are in registers
+      for (int i = 0; i < 21; i++) s_w[(KM_BASE + i) * KD_LD + lane] = out[i];   // over the composites: all of them are in registers
+#pragma unroll
+      for (int i = 0; i < 6; i++) s_w[(KM_GRAV + i) * KD_LD + lane] = grav[i];
     }
   }
   __syncthreads();
@@ -310,12 +238,5 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_mass(const DevParams* __rest
       st4_global(K.mass + (row0 + r) * KM_ROW + 4 * (size_t)u, v[0], v[1], v[2], v[3]);
     }
   }
-  if (K.gravity) {
-    for (int idx = threadIdx.x; idx < 64 * DEXSIM_NJ; idx += KD_THREADS) {
-      const int r = idx / DEXSIM_NJ, j = idx - r * DEXSIM_NJ;
-      if (!s_valid[r]) continue;
-      const int w = j < 6 ? KM_BASE + 21 + j : KM_FINGER((j - 6) >> 2) + 34 + ((j - 6) & 3);
-      GPTR(K.gravity)[(row0 + r) * DEXSIM_NJ + j] = s_w[w * KD_LD + r];
-    }
-  }
+  if (K.gravity) kd_flush<false>(s_w, s_valid, KM_GRAV, DEXSIM_NJ, K.gravity);
 }

@@ -3,10 +3,9 @@
 // pose, like the camera and the kinematics tensors: one kernel, not on the step path; it reads q (arena rows or the caller's
 // override) and the box pose (arena rows or the caller's) and writes caller-owned memory only.
 //
-// One workgroup of 64 rows x 5 waves, as k_kin_*:
-//   phase A  lanes along the rows; wave f walks the chain of finger f (kd_load_q / kd_base_walk / kd_finger_joint: 6 base joints,
-//            4 finger joints, sincos_joint) and leaves the axis ends of its three capsules in LDS as [word][row] (row stride KD_LD),
-//            RELATIVE TO THE PALM JOINT'S ORIGIN o5; waves 0-2 also place one palm capsule each, wave 0 leaves o5 (world) once.
+// One workgroup in the shape of dexsim_chain.hip.inc (64 rows x 5 waves, [word][row] LDS, o5-relative positions):
+//   phase A  lanes along the rows; wave f walks the chain of finger f (kd_load_q / kd_base_walk / kd_finger_joint) and leaves the
+//            axis ends of its three capsules in LDS; waves 0-2 also place one palm capsule each, wave 0 leaves o5 (world) once.
 //            Every hand-internal difference of phase B is therefore a difference of numbers of hand size (< 0.4 m), not of world
 //            coordinates, and the box enters through (o5 - centre) alone.
 //   phase B  lanes stay on the rows.  Wave w takes the finger groups 2 w and 2 w + 1 and the palm group 10 + w (9 + 9 + 6 = 24
@@ -14,7 +13,7 @@
 //            the pairs of a group do not depend on each other (only the strict-less minimum chains them), so the scheduler
 //            interleaves their chains: a lone wave issues a dependent instruction only every few cycles (collide_capsules3).
 //            Records leave as two 16-byte stores per lane; pair_dist goes through LDS and leaves as contiguous 16-byte stores of
-//            all five waves (phase C), like kindyn's phase B.
+//            all five waves (phase C, kd_flush).
 // Plain __syncthreads() only: no atomics, no spins.  A row >= k or with an id outside [0, num_envs) never writes caller memory.
 //
 // Geometry (the contract is in include/dexsim.h):
@@ -283,14 +282,8 @@ __global__ __launch_bounds__(KD_THREADS) void k_proximity(const DevParams* __res
     }
   }
 
-  if (K.pair_dist) {   // ---- phase C: quad u of row r is words [4 u, 4 u + 4) of that row's DEXSIM_NPROX_PAIRS contiguous words
+  if (K.pair_dist) {   // ---- phase C
     __syncthreads();   // K.pair_dist is the same for every thread of the launch
-    const size_t row0 = (size_t)blockIdx.x * 64;
-    for (int idx = threadIdx.x; idx < 64 * (DEXSIM_NPROX_PAIRS / 4); idx += KD_THREADS) {
-      const int r = idx / (DEXSIM_NPROX_PAIRS / 4), u = idx - r * (DEXSIM_NPROX_PAIRS / 4);
-      if (!s_valid[r]) continue;
-      const float* const w = s_w + (PX_PD + 4 * u) * KD_LD + r;
-      st4_global(K.pair_dist + (row0 + r) * DEXSIM_NPROX_PAIRS + 4 * (size_t)u, w[0], w[KD_LD], w[2 * KD_LD], w[3 * KD_LD]);
-    }
+    kd_flush<true>(s_w, s_valid, PX_PD, DEXSIM_NPROX_PAIRS, K.pair_dist);
   }
 }

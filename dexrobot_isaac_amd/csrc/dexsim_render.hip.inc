@@ -3,9 +3,9 @@
 // Everything the engine collides is analytic (18 capsules, one cube, the ground plane), so an image is ~20 closed-form ray tests per
 // pixel.  Two kernels, neither on the step path; both read persistent state only and write caller-owned memory only:
 //
-//   k_render_scene  one lane per rendered env (64 envs per wave, q rows read coalesced like publish_body): walks the chain from q --
-//                   spawn frame, 6 base joints, 5 x 4 finger joints, sincos_joint; never jframe, which is sub-step scratch holding
-//                   pre-integration frames -- places the capsules and the box, resolves the camera and writes the env's SCENE
+//   k_render_scene  one lane per rendered env (64 envs per wave, q rows read coalesced like publish_body): walks the chain from q
+//                   in world coordinates -- spawn frame, 6 base joints, 5 x 4 finger joints through joint_frame
+//                   (dexsim_chain.hip.inc); never jframe, which is sub-step scratch holding pre-integration frames -- places the capsules and the box, resolves the camera and writes the env's SCENE
 //                   RECORD (include/dexsim.h), including everything that is the same for all rays of the image: all rays share
 //                   the eye, so o = eye - a, u x o, |o|^2 - r^2 ... are per capsule, not per ray.
 //   k_render_rays   grid (ceil(W H / 256), k), 256 threads = 4 waves, one lane per pixel, row-major.  All lanes of a wave belong
@@ -90,16 +90,12 @@ __global__ __launch_bounds__(64) void k_render_scene(const DevParams* __restrict
   Q4 qc = q4p(M.spawn_quat);
   V3 oc = v3p(M.spawn_pos);
 #pragma unroll
-  for (int j = 0; j < 6; j++) {   // base chain, as publish_body walks it
+  for (int j = 0; j < 6; j++) {   // base chain: world origins, (o + d) + q aw like publish_body
     const float qj = FLD(q, j);
-    const M3 Rp = q2mat(qc);
-    V3 on = oc + mul(Rp, v3p(P->jc[j].poff));
-    const Q4 qz = qmul(qc, q4p(P->jc[j].qoff));
-    const V3 ax = v3p(P->jc[j].axis);
-    Q4 qn = qz;
-    if (j < 3) on += qj * mul(q2mat(qz), ax);
-    else { float s, c; sincos_joint(0.5f * qj, &s, &c); qn = qmul(qz, Q4{ax.x * s, ax.y * s, ax.z * s, c}); }
-    qc = qn; oc = on;
+    const JointFrame F = joint_frame(P->jc[j], qj, qc, j < 3);
+    V3 on = oc + F.d;
+    if (j < 3) on += qj * F.aw;
+    qc = F.qn; oc = on;
     if (j == pj) { po = oc; pR = q2mat(qc); }
   }
   const Q4 q5 = qc; const V3 o5 = oc;
@@ -114,13 +110,8 @@ __global__ __launch_bounds__(64) void k_render_scene(const DevParams* __restrict
 #pragma unroll
     for (int lk = 0; lk < DEXSIM_NFJ; lk++) {
       const int j = 6 + 4 * f + lk;
-      const float qj = FLD(q, j);
-      const V3 on = of + mul(q2mat(qf), v3p(P->jc[j].poff));
-      const Q4 qz = qmul(qf, q4p(P->jc[j].qoff));
-      const V3 ax = v3p(P->jc[j].axis);
-      float s, c;
-      sincos_joint(0.5f * qj, &s, &c);
-      qf = qmul(qz, Q4{ax.x * s, ax.y * s, ax.z * s, c}); of = on;
+      V3 aw;
+      kd_finger_joint(P->jc[j], FLD(q, j), of, qf, aw);
       const M3 Rj = q2mat(qf);
       if (j == pj) { po = of; pR = Rj; }
       if (lk >= 1) place_cap(3 + 3 * f + lk - 1, of, Rj);

@@ -840,11 +840,12 @@ class DexHandEnv:
         return self.render_camera("video", [0], ("rgba",))["rgba"][0, :, :, :3].cpu().numpy()
 
     # ------------------------------------------------------------------ Jacobians, mass matrix, gravity force
-    def _kindyn_rows(self, what, env_ids, q):
-        """The HIP core, (ids, q) as device tensors and the number of output rows k, for get_jacobian / get_mass_matrix."""
+    def _kindyn_rows(self, what, method, env_ids, q):
+        """The HIP core (it must have `method`), (ids, q) as device tensors and the number of output rows k, for the queries
+        that are functions of q: get_jacobian, get_mass_matrix, solve_fingertip_ik, query_proximity."""
         core = self._core
-        if not hasattr(core, "body_jacobian"):
-            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no body_jacobian()")
+        if not hasattr(core, method):
+            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no {method}()")
         if q is not None:
             q = torch.as_tensor(q, dtype=torch.float32, device=core.device)
             if q.dim() != 2 or q.shape[1] != _abi.NJ or q.shape[0] < 1:
@@ -871,7 +872,7 @@ class DexHandEnv:
         "r_f_link2_tip"; None = all 37 in order.  Rows 0-2: world linear velocity of the body origin, 3-5: world angular
         velocity; column j: DOF j of dof_state, so jac[i, b] @ dof_vel[env] == rigid_body_states[env, b, 7:13].  Rows: the
         envs `env_ids` (None = all), or the rows of a (k, 26) joint-position override `q` (env_ids is then ignored)."""
-        core, ids, q, k = self._kindyn_rows("get_jacobian", env_ids, q)
+        core, ids, q, k = self._kindyn_rows("get_jacobian", "body_jacobian", env_ids, q)
         if bodies is None:
             idx = None
             nb = _abi.NUM_HAND_BODIES
@@ -899,7 +900,7 @@ class DexHandEnv:
         """gym.acquire_mass_matrix_tensor / refresh_mass_matrix_tensors for the hand: the (k, 26, 26) joint-space inertia M(q)
         (no armature, no PD terms).  gravity=True returns (M, g) with g (k, 26) the gravity force dV/dq: the generalized force
         a controller adds to hold the hand.  Rows as for get_jacobian.  out: M, or the pair (M, g) when gravity=True."""
-        core, ids, q, k = self._kindyn_rows("get_mass_matrix", env_ids, q)
+        core, ids, q, k = self._kindyn_rows("get_mass_matrix", "mass_matrix", env_ids, q)
         if gravity:
             if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
                 raise ValueError("get_mass_matrix: with gravity=True, out must be the pair (M, g)")
@@ -938,10 +939,7 @@ class DexHandEnv:
         controls the policy drives.  With return_info=True: (controls, {"q": (k, 26) coupled joint positions, "residual": (k, 5)
         distance left per finger, dropped fingers included})."""
         what = "solve_fingertip_ik"
-        core = self._core
-        if not hasattr(core, "solve_ik"):
-            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no solve_ik()")
-        core, ids, q, k = self._kindyn_rows(what, env_ids, q)
+        core, ids, q, k = self._kindyn_rows(what, "solve_ik", env_ids, q)
         if sites not in ("tips", "pads"):
             raise ValueError(f"{what}: sites must be 'tips' or 'pads', got {sites!r}")
         if frame not in ("world", "hand"):
@@ -1012,10 +1010,7 @@ class DexHandEnv:
         output name.  The engine's own hand self-collision does not exist: negative self distances are not resolved by the
         physics."""
         what = "query_proximity"
-        core = self._core
-        if not hasattr(core, "proximity"):
-            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no proximity()")
-        core, ids, q, k = self._kindyn_rows(what, env_ids, q)
+        core, ids, q, k = self._kindyn_rows(what, "proximity", env_ids, q)
         names = ("cap_env", "self_min", "pair_dist")
         if isinstance(outputs, str):
             outputs = (outputs,)

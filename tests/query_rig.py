@@ -1,0 +1,69 @@
+"""What the tests of the query kernels share (test_render, test_kindyn, test_ik, test_proximity): the queries are pure functions of
+q that write caller-owned memory only, so every suite poses cores the same way, puts its outputs between guard rows and checks that
+nothing of the instance changed.  A plain module: no fixtures."""
+import numpy as np
+
+from dexrobot_isaac_amd.config import build_sim_config, default_cfg
+
+GUARD = -7.0
+
+
+def setup(n, task="BlindGrasping"):
+    cfg = default_cfg(task)
+    cfg["env"]["numEnvs"] = n
+    sc, model = build_sim_config(cfg)
+    return sc, model.to_struct()
+
+
+def guarded(k, *tail):
+    """A NaN-filled (k, *tail) float32 device view between one leading and one trailing guard row."""
+    import torch
+    full = torch.full((k + 2,) + tail, float("nan"), dtype=torch.float32, device="cuda:0")
+    full[0], full[-1] = GUARD, GUARD
+    return full, full[1:-1]
+
+
+def guards_ok(full):
+    import torch
+    torch.cuda.synchronize()
+    assert bool((full[0] == GUARD).all()) and bool((full[-1] == GUARD).all()), "a guard row was written"
+
+
+def pose_core(core, q, box=None, box_quat=None, qd=None):
+    """Pose every env through the API tensors and the indexed setters.  The box: (n, 7) centre + quaternion xyzw, or (n, 3)
+    positions with `box_quat` (n, 4); its velocities are zeroed."""
+    import torch
+    ids = torch.arange(core.N)
+    core.dof_state[:, :, 0] = torch.as_tensor(q, device=core.device)
+    core.dof_state[:, :, 1] = 0.0 if qd is None else torch.as_tensor(qd, device=core.device)
+    core.set_dof_state_indexed(ids)
+    if box is not None:
+        if box_quat is not None:
+            box = np.concatenate([box, box_quat], axis=1)
+        core.root_state[:, 1, :7] = torch.as_tensor(box, device=core.device)
+        core.root_state[:, 1, 7:] = 0.0
+        core.set_root_state_indexed(ids)
+    torch.cuda.synchronize()
+    assert (core.field("q").t().cpu().numpy() == q).all()
+    if box is not None:
+        assert (core.field("box_pos").t().cpu().numpy() == box[:, :3]).all() and (core.field("box_quat").t().cpu().numpy() == box[:, 3:]).all()
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+def snapshot(core):
+    """Every tensor of the instance a query could reach, and the step stamp."""
+    import torch
+    torch.cuda.synchronize()
+    names = ("arena", "stats", "counters", "obs_buf", "rew_buf", "reset_buf", "episode_step_count", "episode_length", "dof_state",
+             "root_state", "rigid_body_states", "contact_forces_all", "full_dof_targets", "masks")
+    snap = {n: getattr(core, n).clone() for n in names}
+    snap["stamp"] = core.get_step_stamp()
+    return snap
+
+
+def same(a, b):
+    import torch
+    return all((a[k] == b[k]) if k == "stamp" else torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)

@@ -26,20 +26,12 @@ import pytest
 
 from dexrobot_isaac_amd import _abi, _lib
 from dexrobot_isaac_amd.build import build_lib
-from dexrobot_isaac_amd.config import build_sim_config, default_cfg
 from tests import ik_ref as ir
+from tests.query_rig import bits, guarded as _guarded, guards_ok as _guards_ok, pose_core, same as _same, setup as _setup, snapshot as _snapshot
 
 N = 70
 NJ, NACT, NF = _abi.NJ, _abi.NACT, _abi.NFINGER
-GUARD = -7.0
 SEED = 11
-
-
-def _setup(n, task="BlindGrasping"):
-    cfg = default_cfg(task)
-    cfg["env"]["numEnvs"] = n
-    sc, model = build_sim_config(cfg)
-    return sc, model.to_struct()
 
 
 def _prm(**kw):
@@ -104,9 +96,6 @@ def _stub_core(sim_cfg, model_struct, device="cpu"):
 
     class Stub(OracleCore):
         calls = []
-
-        def body_jacobian(self, out, env_ids=None, q=None, bodies=None):
-            pass
 
         def solve_ik(self, targets, controls, **kw):
             self.calls.append((tuple(targets.shape), tuple(controls.shape), kw))
@@ -213,14 +202,6 @@ def test_reference_converges(hk, name):
 
 
 # ------------------------------------------------------------------------------------------------- GPU helpers
-def _guarded(k, *tail):
-    """A NaN-filled (k, *tail) float32 device view between one leading and one trailing guard row."""
-    import torch
-    full = torch.full((k + 2,) + tail, float("nan"), dtype=torch.float32, device="cuda:0")
-    full[0], full[-1] = GUARD, GUARD
-    return full, full[1:-1]
-
-
 def gpu_ik(core, k, targets, env_ids=None, q=None, want=("q", "residual"), **prm):
     """core.solve_ik into guarded outputs: dict of numpy arrays controls (k, 18), q (k, 26), residual (k, 5)."""
     import torch
@@ -231,23 +212,10 @@ def gpu_ik(core, k, targets, env_ids=None, q=None, want=("q", "residual"), **prm
     if q is not None:
         q = torch.as_tensor(np.ascontiguousarray(q, dtype=np.float32), device=core.device)
     core.solve_ik(t, c, env_ids=env_ids, q=q, q_out=qo, residual=r, **prm)
-    torch.cuda.synchronize()
     for f in (fc, fq, fr):
         if f is not None:
-            assert bool((f[0] == GUARD).all()) and bool((f[-1] == GUARD).all()), "a guard row was written"
+            _guards_ok(f)
     return dict(controls=c.cpu().numpy(), q=None if qo is None else qo.cpu().numpy(), residual=None if r is None else r.cpu().numpy())
-
-
-def pose_core(core, q):
-    import torch
-    core.dof_state[:, :, 0] = torch.as_tensor(q, device=core.device)
-    core.dof_state[:, :, 1] = 0.0
-    core.set_dof_state_indexed(torch.arange(core.N))
-    assert (core.field("q").t().cpu().numpy() == q).all()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 @pytest.fixture(scope="module")
@@ -443,21 +411,6 @@ def test_addressing_and_reproducibility(rig):
     assert lib.dexsim_destroy(h2) == 0
     torch.cuda.synchronize()
     assert not ctl.any()                                                       # none of them launched
-
-
-def _snapshot(core):
-    import torch
-    torch.cuda.synchronize()
-    names = ("arena", "stats", "counters", "obs_buf", "rew_buf", "reset_buf", "episode_step_count", "episode_length", "dof_state",
-             "root_state", "rigid_body_states", "contact_forces_all", "full_dof_targets", "masks")
-    snap = {n: getattr(core, n).clone() for n in names}
-    snap["stamp"] = core.get_step_stamp()
-    return snap
-
-
-def _same(a, b):
-    import torch
-    return all((a[k] == b[k]) if k == "stamp" else torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
 
 
 @pytest.mark.gpu

@@ -18,19 +18,11 @@ import pytest
 
 from dexrobot_isaac_amd import _abi, _lib
 from dexrobot_isaac_amd.build import build_lib
-from dexrobot_isaac_amd.config import build_sim_config, default_cfg
 from tests import kindyn_ref as kr
+from tests.query_rig import bits, guarded as _guarded, guards_ok as _guards_ok, pose_core, same as _same, setup as _setup, snapshot as _snapshot
 
 N = 70
 NB, NJ = _abi.NUM_HAND_BODIES, _abi.NJ
-GUARD = -7.0
-
-
-def _setup(n, task="BlindGrasping"):
-    cfg = default_cfg(task)
-    cfg["env"]["numEnvs"] = n
-    sc, model = build_sim_config(cfg)
-    return sc, model.to_struct()
 
 
 # ------------------------------------------------------------------------------------------------- CPU
@@ -131,20 +123,6 @@ def test_env_argument_validation():
 
 
 # ------------------------------------------------------------------------------------------------- GPU helpers
-def _guarded(k, *tail):
-    """A NaN-filled (k, *tail) float32 device view between one leading and one trailing guard row."""
-    import torch
-    full = torch.full((k + 2,) + tail, float("nan"), dtype=torch.float32, device="cuda:0")
-    full[0], full[-1] = GUARD, GUARD
-    return full, full[1:-1]
-
-
-def _guards_ok(full):
-    import torch
-    torch.cuda.synchronize()
-    assert bool((full[0] == GUARD).all()) and bool((full[-1] == GUARD).all()), "a guard row was written"
-
-
 def gpu_jac(core, k, env_ids=None, q=None, bodies=None):
     full, out = _guarded(k, NB if bodies is None else len(bodies), 6, NJ)
     core.body_jacobian(out, env_ids=env_ids, q=q, bodies=bodies)
@@ -160,18 +138,6 @@ def gpu_mass(core, k, env_ids=None, q=None, mass=True, gravity=True):
         if f is not None:
             _guards_ok(f)
     return (None if M is None else M.cpu().numpy()), (None if g is None else g.cpu().numpy())
-
-
-def pose_core(core, q, qd=None):
-    import torch
-    core.dof_state[:, :, 0] = torch.as_tensor(q, device=core.device)
-    core.dof_state[:, :, 1] = 0.0 if qd is None else torch.as_tensor(qd, device=core.device)
-    core.set_dof_state_indexed(torch.arange(core.N))
-    assert (core.field("q").t().cpu().numpy() == q).all()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 def _case(ms, sc, seed):
@@ -238,7 +204,7 @@ def test_contract_with_published_body_states(posed):
     core, q = c["core"], c["q"]
     rng = np.random.default_rng(5)
     qd = rng.uniform(-1, 1, (N, NJ)).astype(np.float32)
-    pose_core(core, q, qd)
+    pose_core(core, q, qd=qd)
     core.refresh_body_states()
     torch.cuda.synchronize()
     rbs = core.rigid_body_states[:, :NB].cpu().numpy().astype(np.float64)
@@ -258,7 +224,7 @@ def test_contract_with_published_body_states(posed):
     qn = q.copy()
     qn[:, 0:2] = np.float32(0.25) * q[:, 0:2]
     qn[:, 2] = np.float32(-0.5) + np.float32(0.25) * q[:, 2]
-    pose_core(core, qn, qd)
+    pose_core(core, qn, qd=qd)
     core.refresh_body_states()
     torch.cuda.synchronize()
     pos = core.rigid_body_states[:, :NB, 0:3].cpu().numpy().astype(np.float64)
@@ -267,7 +233,7 @@ def test_contract_with_published_body_states(posed):
         q2 = qn.copy()
         q2[:, j] += np.float32(1e-2)
         step = q2[:, j].astype(np.float64) - qn[:, j].astype(np.float64)      # what the slide really moved by, in float32
-        pose_core(core, q2, qd)
+        pose_core(core, q2, qd=qd)
         core.refresh_body_states()
         torch.cuda.synchronize()
         pos2 = core.rigid_body_states[:, :NB, 0:3].cpu().numpy().astype(np.float64)
@@ -360,21 +326,6 @@ def test_addressing(posed):
     assert lib.dexsim_body_jacobian(h, None, N, None, (C.c_int * 1)(3), 0, p, None) == 1
     assert lib.dexsim_mass_matrix(h, None, N, None, None, None, None) == 1
     assert b"mass and gravity" in lib.dexsim_last_error()
-
-
-def _snapshot(core):
-    import torch
-    torch.cuda.synchronize()
-    names = ("arena", "stats", "counters", "obs_buf", "rew_buf", "reset_buf", "episode_step_count", "episode_length", "dof_state",
-             "root_state", "full_dof_targets", "masks")
-    snap = {n: getattr(core, n).clone() for n in names}
-    snap["stamp"] = core.get_step_stamp()
-    return snap
-
-
-def _same(a, b):
-    import torch
-    return all((a[k] == b[k]) if k == "stamp" else torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
 
 
 @pytest.mark.gpu

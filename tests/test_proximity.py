@@ -30,22 +30,14 @@ import pytest
 
 from dexrobot_isaac_amd import _abi, _lib
 from dexrobot_isaac_amd.build import build_lib
-from dexrobot_isaac_amd.config import build_sim_config, default_cfg
 from tests import proximity_ref as pr
+from tests.query_rig import bits, guarded as _guarded, guards_ok as _guards_ok, pose_core, same as _same, setup as _setup, snapshot as _snapshot
 
 N = 70
 NJ, NCAP, NG, NP = _abi.NJ, _abi.NCAP, _abi.NPROX_GROUPS, _abi.NPROX_PAIRS
-GUARD = -7.0
 SEED = 23
 SHAPES = {"cap_env": (NCAP, 2, 8), "self_min": (NG, 8), "pair_dist": (NP,)}
 ALL = ("cap_env", "self_min", "pair_dist")
-
-
-def _setup(n, task="BlindGrasping"):
-    cfg = default_cfg(task)
-    cfg["env"]["numEnvs"] = n
-    sc, model = build_sim_config(cfg)
-    return sc, model.to_struct()
 
 
 # ------------------------------------------------------------------------------------------------- CPU
@@ -181,9 +173,6 @@ def _stub_core(sim_cfg, model_struct, device="cpu"):
     class Stub(OracleCore):
         calls = []
 
-        def body_jacobian(self, out, env_ids=None, q=None, bodies=None):
-            pass
-
         def proximity_pairs(self):
             return pr.pair_table()
 
@@ -297,43 +286,15 @@ def test_reference_roundoff_and_selection(hp, poses):
 
 
 # ------------------------------------------------------------------------------------------------- GPU helpers
-def _guarded(k, tail):
-    """A NaN-filled (k, *tail) float32 device view between one leading and one trailing guard row."""
-    import torch
-    full = torch.full((k + 2,) + tail, float("nan"), dtype=torch.float32, device="cuda:0")
-    full[0], full[-1] = GUARD, GUARD
-    return full, full[1:-1]
-
-
 def gpu_query(core, k, env_ids=None, q=None, box=None, size=0.0, want=ALL):
     """core.proximity into guarded outputs: dict of numpy arrays by output name."""
     import torch
-    bufs = {o: _guarded(k, SHAPES[o]) for o in want}
+    bufs = {o: _guarded(k, *SHAPES[o]) for o in want}
     dev = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32), device=core.device)
     core.proximity(env_ids=env_ids, q=dev(q), box_pose=dev(box), box_size=size, **{o: v for o, (_, v) in bufs.items()})
-    torch.cuda.synchronize()
     for full, _ in bufs.values():
-        assert bool((full[0] == GUARD).all()) and bool((full[-1] == GUARD).all()), "a guard row was written"
+        _guards_ok(full)
     return {o: v.cpu().numpy() for o, (_, v) in bufs.items()}
-
-
-def pose_core(core, q, box=None):
-    import torch
-    core.dof_state[:, :, 0] = torch.as_tensor(q, device=core.device)
-    core.dof_state[:, :, 1] = 0.0
-    core.set_dof_state_indexed(torch.arange(core.N))
-    if box is not None:
-        core.root_state[:, 1, :7] = torch.as_tensor(box, device=core.device)
-        core.root_state[:, 1, 7:] = 0.0
-        core.set_root_state_indexed(torch.arange(core.N))
-    torch.cuda.synchronize()
-    assert (core.field("q").t().cpu().numpy() == q).all()
-    if box is not None:
-        assert (core.field("box_pos").t().cpu().numpy() == box[:, :3]).all() and (core.field("box_quat").t().cpu().numpy() == box[:, 3:]).all()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 def _err(dev, ref, mask=None):
@@ -419,21 +380,6 @@ def test_against_reference(rig, hp, poses):
     inside = r64["box"]["meets"] & sel["box_d"]
     assert (out["cap_env"][:, :, 0, 0][inside] <= -r[None, :].repeat(N, 0)[inside].astype(np.float32)).all()
     assert m["box_d"] < 6.5e-3 and m["pair_d"] < 6.5e-3
-
-
-def _snapshot(core):
-    import torch
-    torch.cuda.synchronize()
-    names = ("arena", "stats", "counters", "obs_buf", "rew_buf", "reset_buf", "episode_step_count", "episode_length", "dof_state",
-             "root_state", "rigid_body_states", "contact_forces_all", "full_dof_targets", "masks")
-    snap = {n: getattr(core, n).clone() for n in names}
-    snap["stamp"] = core.get_step_stamp()
-    return snap
-
-
-def _same(a, b):
-    import torch
-    return all((a[k] == b[k]) if k == "stamp" else torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
 
 
 @pytest.mark.gpu

@@ -23,6 +23,7 @@ from dexrobot_isaac_amd import _abi, _lib
 from dexrobot_isaac_amd.build import build_lib
 from dexrobot_isaac_amd.config import build_sim_config, default_cfg
 from tests import render_ref as rr
+from tests.query_rig import pose_core, same as _same, snapshot as _snapshot
 
 MAX_UNSTABLE = 0.03
 
@@ -136,21 +137,6 @@ def make_poses(geom, n, box_size, seed):
             target[e] = [cen[0], cen[1], eye[e, 2]]
     f32 = lambda x: x.astype(np.float32)
     return q, f32(box_pos), f32(box_quat), f32(eye), f32(target)
-
-
-def pose_core(core, q, box_pos=None, box_quat=None):
-    """Pose every env through the API tensors and the indexed setters (as test_body_states_and_indexed_setters does)."""
-    import torch
-    ids = torch.arange(core.N)
-    core.dof_state[:, :, 0] = torch.as_tensor(q, device=core.device)
-    core.dof_state[:, :, 1] = 0.0
-    core.set_dof_state_indexed(ids)
-    if box_pos is not None:
-        core.root_state[:, 1, :] = 0.0
-        core.root_state[:, 1, 0:3] = torch.as_tensor(box_pos, device=core.device)
-        core.root_state[:, 1, 3:7] = torch.as_tensor(box_quat, device=core.device)
-        core.set_root_state_indexed(ids)
-    assert (core.field("q").t().cpu().numpy() == q).all()
 
 
 def make_camera(W, H, hfov=60.0, near=0.01, far=10.0, parent=-1, eye=(0, 0, 0), target=(1, 0, 0)):
@@ -368,21 +354,6 @@ def test_no_box_and_static_box():
         compare_scene(core, scene, geom, q, [box] * n, cams)
         compare_images(refs, tol_abs, tol_rel, depth, rgba, seg, "static box" if over else "no box")
         core.close()
-
-
-def _snapshot(core):
-    import torch
-    torch.cuda.synchronize()
-    names = ("arena", "stats", "counters", "obs_buf", "rew_buf", "reset_buf", "episode_step_count", "episode_length", "dof_state",
-             "root_state", "full_dof_targets", "masks")
-    snap = {n: getattr(core, n).clone() for n in names}
-    snap["stamp"] = core.get_step_stamp()
-    return snap
-
-
-def _same(a, b):
-    import torch
-    return all((a[k] == b[k]) if k == "stamp" else torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
 
 
 @pytest.mark.gpu
