@@ -7,6 +7,7 @@
 #include "dexsim_device.h"
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <type_traits>
@@ -47,6 +48,7 @@ struct DexSim {
   Arena arena;
   ApiPtrs api;
   bool bound;
+  bool model_struct;           // the model has the structure of the specialised chain forms: the MS step kernels (dexsim_create)
   hipEvent_t ev0, ev1;
   const float* last_actions;   // device pointer of the last dexsim_step (DEXSIM_STAGE_STEP re-launches the same kernel)
   hipEvent_t tev[128];         // dexsim_step_timing: ring of 64 (start, stop) pairs
@@ -270,12 +272,27 @@ int dexsim_create(const DexSimConfig* cfg, const DexHandModel* model, int device
   hp.inertia_diag = 1;
   for (int j = 6; j < DEXSIM_NJ; j++)
     for (int i = 3; i < 6; i++) if (model->inertia[j][i] != 0.f) hp.inertia_diag = 0;
+  {   // structural zeros and ones of the model, by exact comparison: the specialised chain forms (MS kernels, see base_chain())
+    auto is3 = [](const float* v, float x, float y, float z) { return v[0] == x && v[1] == y && v[2] == z; };
+    auto qoff_identity = [&](int j) { return is3(model->jqoff[j], 0.f, 0.f, 0.f) && model->jqoff[j][3] == 1.f; };
+    bool ms = true;
+    for (int j = 4; j < 6; j++)   // frames 4 and 5 sit on frame 3 (co-located origins), axes +e_y and +e_z
+      ms = ms && qoff_identity(j) && is3(model->jpoff[j], 0.f, 0.f, 0.f) && is3(model->jaxis[j], 0.f, j == 4 ? 1.f : 0.f, j == 5 ? 1.f : 0.f);
+    for (int j = 0; j < 3; j++)   // world axes of the prismatic joints: exactly e_x, e_y, e_z
+      ms = ms && is3(hp.base_A[j], j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
+    for (int j = 6; j < DEXSIM_NJ; j++)   // flexion joints (1-3 of every finger): axis +-e_y
+      if ((j - 6) % 4 >= 1) ms = ms && model->jaxis[j][0] == 0.f && std::fabs(model->jaxis[j][1]) == 1.f && model->jaxis[j][2] == 0.f;
+    const char* gen = std::getenv("DEXSIM_GENERAL_MODEL_PATH");   // read once, here: "1" runs the general forms for any model
+    h->model_struct = ms && !(gen && gen[0] == '1');
+  }
   HIP_TRY(hipMalloc(&h->d_params, sizeof(DevParams)));
   HIP_TRY(hipMemcpy(h->d_params, &hp, sizeof(DevParams), hipMemcpyHostToDevice));
   const void* const big_lds_kernels[] = {
       reinterpret_cast<const void*>(&k_solve), reinterpret_cast<const void*>(&k_post),
-      reinterpret_cast<const void*>(&k_physics4<false>), reinterpret_cast<const void*>(&k_physics4<true>),
-      reinterpret_cast<const void*>(&k_physics1<false>), reinterpret_cast<const void*>(&k_physics1<true>)};
+      reinterpret_cast<const void*>(&k_physics4<false, false>), reinterpret_cast<const void*>(&k_physics4<true, false>),
+      reinterpret_cast<const void*>(&k_physics1<false, false>), reinterpret_cast<const void*>(&k_physics1<true, false>),
+      reinterpret_cast<const void*>(&k_physics4<false, true>), reinterpret_cast<const void*>(&k_physics4<true, true>),
+      reinterpret_cast<const void*>(&k_physics1<false, true>), reinterpret_cast<const void*>(&k_physics1<true, true>)};
   for (const void* k : big_lds_kernels) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS_BYTES));
   HIP_TRY(hipEventCreate(&h->ev0));
   HIP_TRY(hipEventCreate(&h->ev1));
@@ -396,7 +413,8 @@ static int physics_step(dexsim_t h, int gate_on_reset, int tail, void* stream, c
     const float* act = i == 0 ? actions : nullptr;
     ApiPtrs api = h->api;
     if (api.actions_copy == act) api.actions_copy = nullptr;   // `act` is __restrict__: never alias it with the copy sink
-    auto* k = i < n4 ? (gate_on_reset ? k_physics4<true> : k_physics4<false>) : (gate_on_reset ? k_physics1<true> : k_physics1<false>);
+    auto* k = h->model_struct ? (i < n4 ? (gate_on_reset ? k_physics4<true, true> : k_physics4<false, true>) : (gate_on_reset ? k_physics1<true, true> : k_physics1<false, true>))
+                              : (i < n4 ? (gate_on_reset ? k_physics4<true, false> : k_physics4<false, false>) : (gate_on_reset ? k_physics1<true, false> : k_physics1<false, false>));
     k<<<grid, block, lds, (hipStream_t)stream>>>(h->arena, api, h->d_params, h->api.counters, act, t, h->NS, h->N);
     LAUNCH_CHECK();
   }
@@ -486,7 +504,7 @@ static int launch_stage(dexsim_t h, int stage, void* stream) {
     case DEXSIM_STAGE_SOLVE: return launch_solve(h, stream);
     case DEXSIM_STAGE_PUBLISH: return launch_publish(h, 0, stream);
     case DEXSIM_STAGE_SUBSTEP:   // one sub-step as its own launch, counting its contacts
-      k_physics1<false><<<dim3(h->NS / 64), dim3(448), FS_LDS_BYTES, (hipStream_t)stream>>>(
+      (h->model_struct ? k_physics1<false, true> : k_physics1<false, false>)<<<dim3(h->NS / 64), dim3(448), FS_LDS_BYTES, (hipStream_t)stream>>>(
           h->arena, h->api, h->d_params, h->api.counters, nullptr, 0, h->NS, h->N);
       break;
     case DEXSIM_STAGE_PHYSICS: return physics_step(h, 0, 0, stream);

@@ -199,6 +199,12 @@ DI float div_n(float a, float b) {
 DI float sqrt_n(float x) { return opaque(__builtin_amdgcn_sqrtf(x)); }
 // rsq_n: x and the result normal (for 1.f / sqrtf(x) where the root has no other use: the operators are one v_rsq_f32 there)
 DI float rsq_n(float x) { return __builtin_amdgcn_rsqf(x); }
+// mulr: a product that is rounded on its own -- never contracted into a neighbouring add.  The specialised chain forms (model
+// structure, see base_chain) use it where the general expression rounds the surviving product before the next add.
+DI float mulr(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
 // norm_n: |a| for a vector that is exactly zero or of model scale (a capsule axis): dot(a, a) zero or normal
 DI float norm_n(V3 a) { return sqrt_n(dot(a, a)); }
 DI float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }

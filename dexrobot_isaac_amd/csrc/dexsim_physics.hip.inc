@@ -274,6 +274,38 @@ struct BaseChain {
 // products with w = alpha = 0).  dexsim_create folds them in double precision (DevParams::base_*); joints 4, 5 stay generic.
 // s_q / s_qd (fused kernel, bodies 2-4): q, qd of the base joints from the LDS words the palm wave left there at the end of the
 // previous body, instead of from the arena (an L2 round trip behind that body's stores)
+//
+// Model structure (template parameter MS of the step kernels).  The chains multiply by model constants that are exactly zero or
+// one, which the compiler cannot know: they arrive through s_load, and without nsz / nnan it may not fold x * 0 anyway.
+// dexsim_create classifies the model's floats by exact comparison and picks the kernel, so the chains stay straight-line code (a
+// wave-uniform dispatch between two copies of the finger chain inside one kernel cost 14 VGPRs and 112 B of scratch).  MS holds when
+//   base     joints 4 and 5 have identity qoff, zero poff and axes +e_y / +e_z (joint frames 3-5 share one origin), and the world
+//            axes base_A[0..2] of the prismatic joints are exactly e_x, e_y, e_z;
+//   fingers  joints 1-3 of every finger have axis +-e_y.
+// Every dropped term is an exact zero and every dropped factor an exact one, so a result equals the general form's for finite
+// inputs (the sign of an exact zero may differ).  Where two products survive, the form spells out the rounding sequence the
+// general expression compiles to (-ffp-contract=fast): one product rounded on its own (mulr), the other fused onto it (fmaf).
+// Which of two products the compiler rounds depends on the expression AND its surroundings, so every form here was read off the
+// general kernel's code at that site and is pinned by tests/test_model_structure.py (`==` against the general kernels).  Forms
+// that could not be kept equal (the finger joints' identity qoff, one-component axis quaternion, poff and com along x) are
+// listed in profiles/model_structure/README.md: a specialised joint changes how the compiler contracts the q2mat next to it.
+// qmul(a, {0, s, 0, c}) and qmul(a, {0, 0, s, c}): a joint rotation about e_y / e_z
+DI Q4 qmul_axis_y(Q4 a, float s, float c) {
+  return {fmaf(-a.z, s, mulr(a.x, c)), fmaf(a.y, c, mulr(a.w, s)), fmaf(a.z, c, mulr(a.x, s)), fmaf(-a.y, s, mulr(a.w, c))};
+}
+DI Q4 qmul_axis_z(Q4 a, float s, float c) {
+  return {fmaf(a.y, s, mulr(a.x, c)), fmaf(a.y, c, -mulr(a.x, s)), fmaf(a.z, c, mulr(a.w, s)), fmaf(-a.z, s, mulr(a.w, c))};
+}
+// columns y and z of q2mat(q), in the rounding order of the general base chain's q2mat at joints 4 and 5
+DI V3 q2mat_col_y(Q4 q) {
+  return {2.f * fmaf(q.x, q.y, -mulr(q.z, q.w)), fmaf(fmaf(q.z, q.z, mulr(q.x, q.x)), -2.f, 1.f), 2.f * fmaf(q.y, q.z, mulr(q.x, q.w))};
+}
+DI V3 q2mat_col_z(Q4 q) {
+  return {2.f * fmaf(q.x, q.z, mulr(q.y, q.w)), 2.f * fmaf(q.y, q.z, -mulr(q.x, q.w)), fmaf(fmaf(q.y, q.y, mulr(q.x, q.x)), -2.f, 1.f)};
+}
+
+// MS: frame j = 4, 5 sits on frame j - 1 (identity qoff, no lever arm), its axis e_y / e_z is a column of that frame's rotation
+template <bool MS>
 DI void base_chain(const Arena& A, const DevParams* __restrict__ P, V3 grav, int N, int e, BaseChain& B, bool write_jframe,
                    const float* s_q = nullptr, const float* s_qd = nullptr, int lane = 0) {
   // all loads before the (conditional) jframe stores below: a load cannot be hoisted above a possibly aliasing store
@@ -301,6 +333,16 @@ DI void base_chain(const Arena& A, const DevParams* __restrict__ P, V3 grav, int
   V3 w = B.qdb[3] * B.ab[3], al = {0, 0, 0}, ao = {-grav.x, -grav.y, -grav.z};
 #pragma unroll
   for (int j = 4; j < 6; j++) {
+    if (MS) {
+      const V3 aw = j == 4 ? q2mat_col_y(qc) : q2mat_col_z(qc);
+      float s, c;
+      sincos_joint(0.5f * B.qb[j], &s, &c);
+      const Q4 qn = j == 4 ? qmul_axis_y(qc, s, c) : qmul_axis_z(qc, s, c);
+      const V3 cw = cross(w, aw);
+      al += B.qdb[j] * cw; w += B.qdb[j] * aw;
+      B.ab[j] = aw; B.ob[j] = oc; qc = qn;
+      continue;
+    }
     M3 Rp = q2mat(qc);
     V3 on = oc + mul(Rp, v3p(P->jc[j].poff));
     Q4 qz = qmul(qc, q4p(P->jc[j].qoff));
@@ -528,6 +570,8 @@ DI void finger_load(const Arena& A, int f, int N, int e, FingerIn& in) {
 // tok_seq > 0 (fused sub-step): the finger decides itself whether it can touch anything in this sub-step (sphere_clear =
 // the hand-level verdict; else the per-capsule bounds) and publishes the verdict as LDS token FS_FLAG + f; a clear finger
 // skips the joint-frame / factor hand-off that only the rows of its own contacts read.  Returns the verdict.
+// MS: the model structure the chain may rely on (see base_chain); false is the general form.
+template <bool MS>
 DI bool finger_dynamics(const Arena& A, const DevParams* __restrict__ P, const BaseChain& B, const FingerIn& in, float* sh, const int dlb,
                         float* s_uf, int lane, int f, int N, int e, int tok_seq = 0, bool sphere_clear = false,
                         V3 bpos = V3{0, 0, 0}, const M3& Rb = M3{{1, 0, 0, 0, 1, 0, 0, 0, 1}}, float* Gk = nullptr) {
@@ -552,7 +596,9 @@ DI bool finger_dynamics(const Arena& A, const DevParams* __restrict__ P, const B
     sincos_joint(0.5f * ql[l], &s, &c);
     Q4 qn = qmul(qz, Q4{ax.x * s, ax.y * s, ax.z * s, c});
     M3 R = q2mat(qn);
-    V3 aw = mul(R, ax);   // (the joint's own rotation leaves its axis where the fixed offset put it: no second matrix from qz)
+    // (the joint's own rotation leaves its axis where the fixed offset put it: no second matrix from qz)
+    // MS, flexion joints: the axis +-e_y picks a signed column of R (each product exact: never fused into a neighbour)
+    V3 aw = MS && l >= 1 ? V3{mulr(R.m[1], ax.y), mulr(R.m[4], ax.y), mulr(R.m[7], ax.y)} : mul(R, ax);
     V3 r = on - of;
     V3 aoj = aof + cross(alf, r) + cross(wf, cross(wf, r));
     V3 cw = cross(wf, aw);
@@ -609,9 +655,16 @@ DI bool finger_dynamics(const Arena& A, const DevParams* __restrict__ P, const B
       float v = dot(a[k], Lm + cross(cc.c - o[k], Pm));
       Fm[l * 4 + k] = v; Fm[k * 4 + l] = v;
     }
+    if (MS) {   // prismatic axes e_x, e_y, e_z: a component each; joint frames 3-5 share their origin: one lever-arm product
+      const V3 Xm = Lm + cross(cc.c - B.ob[3], Pm);
+      Cm[l] = Pm.x; Cm[4 + l] = Pm.y; Cm[8 + l] = Pm.z;
 #pragma unroll
-    for (int i = 0; i < 6; i++)
-      Cm[i * 4 + l] = i < 3 ? dot(B.ab[i], Pm) : dot(B.ab[i], Lm + cross(cc.c - B.ob[i], Pm));
+      for (int i = 3; i < 6; i++) Cm[i * 4 + l] = dot(B.ab[i], Xm);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 6; i++)
+        Cm[i * 4 + l] = i < 3 ? dot(B.ab[i], Pm) : dot(B.ab[i], Lm + cross(cc.c - B.ob[i], Pm));
+    }
   }
   comp_put(sh, lane, DL_COMP(dlb, f), cc, B.o5);
   if (tok_seq > 0) {   // composite + wrench are in LDS: count this finger in for the palm wave's schur_precompute
@@ -1160,14 +1213,14 @@ __global__ __launch_bounds__(384) void k_dynamics(Arena A, const DevParams* __re
   BaseChain B;
   FingerIn fin;
   if (wv < 5) finger_load(A, wv, N, e, fin);
-  base_chain(A, P, grav, N, e, B, wv == 5);
+  base_chain<false>(A, P, grav, N, e, B, wv == 5);
 
   // ---- phase 1: five finger waves + the palm/box wave, in parallel
   int nc = 0;
   V3 bpos = {0, 0, 0}; M3 Rb = q2mat(Q4{0, 0, 0, 1});
   float hb = 0.f, bmu = 0.f;
   if (wv < 5) {
-    finger_dynamics(A, P, B, fin, sh, dlb, nullptr, lane, wv, N, e);
+    finger_dynamics<false>(A, P, B, fin, sh, dlb, nullptr, lane, wv, N, e);
   } else {
     const M3 R5 = q2mat(B.q5);
     Comp comp5;
@@ -2400,7 +2453,7 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
 // previous body's stores on every wave, go away.  carry_in: this body starts from the carried state; carry != nullptr: it
 // leaves its end state behind (carry_out).
 struct SubstepCarry { float ql[4], qdl[4], tg[4]; };
-template <bool LAST>
+template <bool LAST, bool MS>
 // seq: 1-based index of this body within the launch (token of the wave-5 -> wave-6 hand_free hand-off, see FS_FLAG)
 // post_pre (last sub-step of the fused control step only): the box wave, idle during the publication, already runs the
 // post-physics tasks that do not depend on it (POST_PRE_MASK) into the observation tile at the bottom of the LDS
@@ -2454,14 +2507,14 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   if (wv != 6) {   // the box wave needs neither the base chain nor the fingers: it starts on the box right away
     if (carry_in) {
       if (has_box) bpos_h = {SH(FS_CARRY_BP), SH(FS_CARRY_BP + 1), SH(FS_CARRY_BP + 2)};
-      base_chain(A, P, grav, N, e, B, false, sh + FS_CARRY_Q * 64, sh + FS_CARRY_QD * 64, lane);
+      base_chain<MS>(A, P, grav, N, e, B, false, sh + FS_CARRY_Q * 64, sh + FS_CARRY_QD * 64, lane);
       if (wv < 5) {
 #pragma unroll
         for (int l = 0; l < 4; l++) { fin.ql[l] = carry.ql[l]; fin.qdl[l] = carry.qdl[l]; fin.tg[l] = carry.tg[l]; }
       }
     } else {
       if (has_box) bpos_h = {FLD(box_pos, 0), FLD(box_pos, 1), FLD(box_pos, 2)};
-      base_chain(A, P, grav, N, e, B, false);
+      base_chain<MS>(A, P, grav, N, e, B, false);
       if (wv < 5) finger_load(A, wv, N, e, fin);
     }
     sphere = hand_clear(P, B, bpos_h);
@@ -2489,7 +2542,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   V3 bpos = {0, 0, 0}; M3 Rb = q2mat(Q4{0, 0, 0, 1});
   float hb = 0.f, bmu = 0.f;
   if (wv < 5) {
-    finger_dynamics(A, P, B, fin, sh, dlb, s_uf, lane, wv, N, e, seq, sphere, bpos_h, Rb_h, Gkeep);
+    finger_dynamics<MS>(A, P, B, fin, sh, dlb, s_uf, lane, wv, N, e, seq, sphere, bpos_h, Rb_h, Gkeep);
   } else if (wv == 5) {   // the palm
     const M3 R5 = q2mat(B.q5);
     Comp comp5;
@@ -2983,7 +3036,8 @@ DI void physics_epilogue(const ApiPtrs& T, const DevParams* __restrict__ P, int 
 // every first touch of the next kernel an Infinity-Cache / HBM miss, ~4k cycles).
 // act != nullptr (ungated first launch of dexsim_step): ActionProcessor.process_actions runs first, three action channels per
 // wavefront (actions_block, the body of k_actions too), so that the whole control step up to the reset gate is ONE launch.
-template <bool GATED>
+// MS: the model has the structure of base_chain's specialised forms (classified by dexsim_create, which picks the kernel)
+template <bool GATED, bool MS>
 __global__ __launch_bounds__(448) void k_physics4(Arena A, ApiPtrs T, const DevParams* __restrict__ P, int* __restrict__ cnt,
                                                   const float* __restrict__ act, int tail, int N, int NR) {
   extern __shared__ float sh[];
@@ -2992,13 +3046,13 @@ __global__ __launch_bounds__(448) void k_physics4(Arena A, ApiPtrs T, const DevP
   __syncthreads();   // targets are read by every wave of the first sub-step
   if (!GATED || cnt[CNT_ANY_RESET] == T.stamp) {
     SubstepCarry K;
-    substep_body<false>(P->arena, T, P, cnt, N, NR, sh, 1, 64, false, true, K, false, true);    // stamp_base: rows of the diagnostic cycle stamps (profile build only)
+    substep_body<false, MS>(P->arena, T, P, cnt, N, NR, sh, 1, 64, false, true, K, false, true);    // stamp_base: rows of the diagnostic cycle stamps (profile build only)
     __syncthreads();
-    substep_body<false>(P->arena, T, P, cnt, N, NR, sh, 2, 128, false, true, K, true, true);
+    substep_body<false, MS>(P->arena, T, P, cnt, N, NR, sh, 2, 128, false, true, K, true, true);
     __syncthreads();
-    substep_body<false>(P->arena, T, P, cnt, N, NR, sh, 3, 192, false, true, K, true, true);
+    substep_body<false, MS>(P->arena, T, P, cnt, N, NR, sh, 3, 192, false, true, K, true, true);
     __syncthreads();
-    substep_body<true>(P->arena, T, P, cnt, N, NR, sh, 4, 256, !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, true, false);
+    substep_body<true, MS>(P->arena, T, P, cnt, N, NR, sh, 4, 256, !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, true, false);
     if (!GATED && (tail & TAIL_POST)) {
       __syncthreads();     // publication (site poses, hand twist) -> observations; LDS changes hands
       post_block(P->arena, T, P, cnt, sh, 0, 1, N, NR, POST_PRE_MASK);
@@ -3013,7 +3067,7 @@ __global__ __launch_bounds__(448) void k_physics4(Arena A, ApiPtrs T, const DevP
 
 // One sub-step in one launch, the same launch otherwise: the substeps % 4 sub-steps at the end of a physics step, and
 // DEXSIM_STAGE_SUBSTEP.
-template <bool GATED>
+template <bool GATED, bool MS>
 __global__ __launch_bounds__(448) void k_physics1(Arena A, ApiPtrs T, const DevParams* __restrict__ P, int* __restrict__ cnt,
                                                   const float* __restrict__ act, int tail, int N, int NR) {
   extern __shared__ float sh[];
@@ -3022,7 +3076,7 @@ __global__ __launch_bounds__(448) void k_physics1(Arena A, ApiPtrs T, const DevP
   __syncthreads();
   if (!GATED || cnt[CNT_ANY_RESET] == T.stamp) {
     SubstepCarry K;   // (a single body: nothing carried)
-    substep_body<true>(P->arena, T, P, cnt, N, NR, sh, 1, 0, !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, false, false);
+    substep_body<true, MS>(P->arena, T, P, cnt, N, NR, sh, 1, 0, !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, false, false);
     if (!GATED && (tail & TAIL_POST)) {
       __syncthreads();
       post_block(P->arena, T, P, cnt, sh, 0, 1, N, NR, POST_PRE_MASK);

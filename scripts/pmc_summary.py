@@ -70,7 +70,7 @@ for tag, key, last in (("h", "headline", None), ("c", "contact_settled", 100)):
         if not f:
             continue
         d = pd.read_csv(f[0])
-        d = d[d["Kernel_Name"].str.contains("k_physics4<false>", regex=False) | d["Kernel_Name"].str.contains("k_physics4<(bool)0>", regex=False)]
+        d = d[d["Kernel_Name"].str.contains("k_physics4<false", regex=False) | d["Kernel_Name"].str.contains("k_physics4<(bool)0>", regex=False)]
         for cname, g in d.groupby("Counter_Name"):
             g = g.sort_values("Dispatch_Id")
             vals = g["Counter_Value"].values
