@@ -126,6 +126,7 @@ class DexSimCamera(C.Structure):
 
 IK_MAX_ITERS = 64   # DEXSIM_IK_MAX_ITERS
 NPROX_GROUPS, NPROX_PAIRS = 15, 120   # DEXSIM_NPROX_GROUPS, DEXSIM_NPROX_PAIRS: the pair table of dexsim_query_proximity
+ID_GRAVITY = 1   # DEXSIM_ID_GRAVITY: dexsim_inverse_dynamics includes the gravity force
 
 
 class DexSimIK(C.Structure):
@@ -147,6 +148,7 @@ EXPORTED_SYMBOLS = [
     "dexsim_body_jacobian", "dexsim_mass_matrix",
     "dexsim_ik_struct_size", "dexsim_solve_ik",
     "dexsim_proximity_pair", "dexsim_query_proximity",
+    "dexsim_inverse_dynamics", "dexsim_body_bias_accel",
 ]
 
 
@@ -196,6 +198,8 @@ def declare_prototypes(lib):
     lib.dexsim_solve_ik.argtypes = [vp, vp, i32, vp, vp, P(DexSimIK), vp, vp, vp, vp]
     lib.dexsim_proximity_pair.argtypes = [i32, P(i32), P(i32), P(i32)]
     lib.dexsim_query_proximity.argtypes = [vp, vp, i32, vp, vp, f32, vp, vp, vp, vp]
+    lib.dexsim_inverse_dynamics.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
+    lib.dexsim_body_bias_accel.argtypes = [vp, vp, i32, vp, vp, P(i32), i32, vp, vp]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = i32
     lib.dexsim_error_string.argtypes = [i32]

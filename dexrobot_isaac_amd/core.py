@@ -415,6 +415,49 @@ class DexSimCore:
         gp = None if gravity is None else self._kin_out("mass_matrix", "gravity", gravity, (k, _abi.NJ))
         check(self.lib.dexsim_mass_matrix(self.h, ids, k, qp, mp, gp, self._stream()), "mass_matrix")
 
+    # ------------------------------------------------------------------ inverse dynamics, bias accelerations
+    def _kin_vel(self, what, name, t, k):
+        """Pointer of a (k, 26) velocity or acceleration array that goes with the rows of _kin_rows; checked like q."""
+        if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (k, _abi.NJ):
+            raise DexSimError(f"{what}: {name} must be a contiguous float32 tensor of shape ({k}, {_abi.NJ}) on {self.device}, "
+                              f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return C.c_void_p(t.data_ptr())
+
+    def _kin_rows_qd(self, what, env_ids, q, qd):
+        if (q is None) != (qd is None):
+            raise DexSimError(f"{what}: q and qd must both be None (the envs' state) or both be (k, {_abi.NJ}) overrides")
+        ids, qp, k = self._kin_rows(what, env_ids, q)
+        return ids, qp, (None if qd is None else self._kin_vel(what, "qd", qd, k)), k
+
+    def inverse_dynamics(self, tau, qdd=None, env_ids=None, q=None, qd=None, gravity=True):
+        """tau = M(q) qdd + c(q, qd) (+ g(q) with gravity=True) into `tau` (k, 26) f32, with the M and g of mass_matrix (no
+        armature, no PD terms, no contact).  qdd: (k, 26) aligned with the output rows, None = zero (tau is then the bias force).
+        Rows: env_ids (None = all envs) with the envs' q and qd, or the rows of the (k, 26) overrides `q` and `qd`, which go
+        together (env_ids is then ignored).  dexsim_inverse_dynamics."""
+        ids, qp, vp, k = self._kin_rows_qd("inverse_dynamics", env_ids, q, qd)
+        ap = None if qdd is None else self._kin_vel("inverse_dynamics", "qdd", qdd, k)
+        tp = self._kin_out("inverse_dynamics", "tau", tau, (k, _abi.NJ))
+        self._keep_kin = self._keep_kin + (qd, qdd)
+        check(self.lib.dexsim_inverse_dynamics(self.h, ids, k, qp, vp, ap, _abi.ID_GRAVITY if gravity else 0, tp, self._stream()),
+              "inverse_dynamics")
+
+    def body_bias_accel(self, out, env_ids=None, q=None, qd=None, bodies=None):
+        """Jdot qd of the hand bodies `bodies` (None = all 37) into `out` (k, nb, 6) f32: world linear acceleration of the body
+        origin (0-2) and angular acceleration (3-5) at qdd = 0, without gravity, so that body_jacobian's out[i, b] @ qdd + this
+        is the derivative of rigid_body_states[env, b, 7:13].  Rows as for inverse_dynamics.  dexsim_body_bias_accel."""
+        ids, qp, vp, k = self._kin_rows_qd("body_bias_accel", env_ids, q, qd)
+        if bodies is None:
+            nb, bp = _abi.NUM_HAND_BODIES, None
+        else:
+            bl = [int(b) for b in bodies]
+            nb = len(bl)
+            if not 1 <= nb <= _abi.NUM_HAND_BODIES:
+                raise DexSimError(f"body_bias_accel: between 1 and {_abi.NUM_HAND_BODIES} bodies, got {nb}")
+            bp = (C.c_int * nb)(*bl)
+        op = self._kin_out("body_bias_accel", "out", out, (k, nb, 6))
+        self._keep_kin = self._keep_kin + (qd,)
+        check(self.lib.dexsim_body_bias_accel(self.h, ids, k, qp, vp, bp, nb, op, self._stream()), "body_bias_accel")
+
     # ------------------------------------------------------------------ fingertip inverse kinematics
     def solve_ik(self, targets, controls, env_ids=None, q=None, sites=0, frame=0, free_mask=0x3FFC0, weights=(1, 1, 1, 1, 1),
                  iters=16, damping=1e-3, max_step=0.5, q_out=None, residual=None):

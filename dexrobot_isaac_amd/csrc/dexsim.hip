@@ -990,3 +990,64 @@ extern "C" int dexsim_query_proximity(dexsim_t h, const int64_t* env_ids, int k,
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------- inverse dynamics, bias accelerations
+// Behind every use of the step kernels, like the kernels above.
+// clang-format off
+#include "dexsim_invdyn.hip.inc"
+// clang-format on
+
+// kin_rows plus the rule of the velocity override: q and qd are both NULL (arena) or both (k, 26) overrides
+static int kin_rows_qd(const char* who, dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, KinRows* R) {
+  int rc = kin_rows(who, h, env_ids, k, q, R);
+  if (rc) return rc;
+  if (!q != !qd) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": q and qd must both be NULL (the envs' state) or both be (k, 26) overrides").c_str());
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_inverse_dynamics(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const float* qdd,
+                                       int flags, float* tau, void* stream) {
+  InvDyn K;
+  std::memset(&K, 0, sizeof K);
+  int rc = kin_rows_qd("dexsim_inverse_dynamics", h, env_ids, k, q, qd, &K.rows);
+  if (rc) return rc;
+  if ((flags & ~DEXSIM_ID_GRAVITY) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_inverse_dynamics: unknown flag bits (DEXSIM_ID_GRAVITY is the only flag)");
+  if (!tau || ((uintptr_t)tau & 3) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_inverse_dynamics: tau must be a 4-byte aligned device pointer");
+  NEED_BOUND(h);
+  K.qd = qd; K.qdd = qdd; K.tau = tau; K.gravity = flags & DEXSIM_ID_GRAVITY;
+  k_kin_invdyn<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_body_bias_accel(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const int* bodies, int nb,
+                                      float* acc, void* stream) {
+  BiasAcc K;
+  std::memset(&K, 0, sizeof K);
+  int rc = kin_rows_qd("dexsim_body_bias_accel", h, env_ids, k, q, qd, &K.rows);
+  if (rc) return rc;
+  if (nb < 1 || nb > DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: nb must be in [1, DEXSIM_NUM_HAND_BODIES]");
+  if (!bodies && nb != DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: bodies == NULL needs nb == DEXSIM_NUM_HAND_BODIES");
+  for (int i = 0; i < nb; i++) {
+    const int b = bodies ? bodies[i] : i;
+    if (b < 0 || b >= DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: body index out of range");
+  }
+  int n = 0;   // the request sorted by the frame a body rides on: -1 (the spawn frame), then the joints in order
+  for (int j = -1; j < DEXSIM_NJ; j++) {
+    K.jstart[j + 1] = (unsigned char)n;
+    for (int i = 0; i < nb; i++) {
+      const int b = bodies ? bodies[i] : i;
+      if (kd_body_joint(b) == j) { K.body[n] = (unsigned char)b; K.slot[n] = (unsigned char)i; n++; }
+    }
+  }
+  K.jstart[DEXSIM_NJ + 1] = (unsigned char)n;
+  if (!acc || ((uintptr_t)acc & 3) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: acc must be a 4-byte aligned device pointer");
+  for (int b = 0; b < DEXSIM_NUM_HAND_BODIES; b++)
+    if (h->model.body_parent[b] != kd_body_joint(b))
+      return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: model.body_parent differs from the frames rigid_body_states is published on");
+  NEED_BOUND(h);
+  K.qd = qd; K.acc = acc; K.nb = nb;
+  k_kin_bias_accel<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}

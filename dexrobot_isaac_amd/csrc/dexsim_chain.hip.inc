@@ -1,6 +1,6 @@
-// dexsim_chain.hip.inc -- the frame the query kernels share (k_render_scene, k_kin_jacobian, k_kin_mass, k_ik_solve, k_proximity):
-// pure functions of q, off the step path, writing caller-owned memory only.  Force-inlined functions and macros only: this file
-// emits no code of its own.
+// dexsim_chain.hip.inc -- the frame the query kernels share (k_render_scene, k_kin_jacobian, k_kin_mass, k_ik_solve, k_proximity,
+// k_kin_invdyn, k_kin_bias_accel): pure functions of q (the last two of q and qd: kd_load_qd), off the step path, writing
+// caller-owned memory only.  Force-inlined functions and macros only: this file emits no code of its own.
 //
 //   joint_frame      THE joint-frame rule: parent frame -> a joint's offset, world axis and frame.  Every walk of the family is
 //                    written through it; publish_body (dexsim_physics.hip.inc) spells the same rule out for the step kernels.
@@ -66,6 +66,27 @@ DI bool kd_load_q(const Arena& A, const KinRows& R, int N, int NR, int f, float*
     for (int j = 0; j < 4; j++) qf[j] = FLD(q, 6 + 4 * f + j);
   }
   return valid;
+}
+
+// the row's qd, for the queries that are functions of (q, qd): `qd` is the (k, 26) override that goes with R.q (both NULL or both
+// given), else the arena's qd of the env kd_load_q read q from.  Like kd_load_q, every lane reads a legal address.
+DI void kd_load_qd(const Arena& A, const KinRows& R, const float* qd, int N, int NR, int f, float* vb, float* vf) {
+  const int l = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (qd) {
+    const size_t row = (size_t)min(l, R.k - 1) * DEXSIM_NJ;
+#pragma unroll
+    for (int j = 0; j < 6; j++) vb[j] = GPTR(qd)[row + j];
+#pragma unroll
+    for (int j = 0; j < 4; j++) vf[j] = GPTR(qd)[row + 6 + 4 * f + j];
+  } else {
+    long long id = l;
+    if (R.env_ids) id = GPTR(R.env_ids)[min(l, R.k - 1)];
+    const int e = (l < R.k && id >= 0 && id < NR) ? (int)id : 0;
+#pragma unroll
+    for (int j = 0; j < 6; j++) vb[j] = FLD(qd, j);
+#pragma unroll
+    for (int j = 0; j < 4; j++) vf[j] = FLD(qd, 6 + 4 * f + j);
+  }
 }
 
 DI void kd_base_walk(const DevParams* __restrict__ P, const float* qb, KinBase& B) {

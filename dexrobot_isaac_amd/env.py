@@ -866,6 +866,27 @@ class DexHandEnv:
             raise ValueError(f"{what}: out must be a contiguous float32 tensor of shape {shape} on {device}")
         return out
 
+    def _kindyn_bodies(self, what, bodies):
+        """(indices or None = all, nb) of a `bodies` argument: indices into the rows of rigid_body_states or names from
+        hand_model.BODY_NAMES."""
+        if bodies is None:
+            return None, _abi.NUM_HAND_BODIES
+        if isinstance(bodies, (str, int)):
+            bodies = [bodies]
+        idx = []
+        for b in bodies:
+            if isinstance(b, str):
+                if b not in self.model.body_names:
+                    raise ValueError(f"{what}: unknown body '{b}' (bodies: {self.model.body_names})")
+                b = self.model.body_names.index(b)
+            b = int(b)
+            if not 0 <= b < _abi.NUM_HAND_BODIES:
+                raise ValueError(f"{what}: body index must be in [0, {_abi.NUM_HAND_BODIES}), got {b}")
+            idx.append(b)
+        if not 1 <= len(idx) <= _abi.NUM_HAND_BODIES:
+            raise ValueError(f"{what}: between 1 and {_abi.NUM_HAND_BODIES} bodies, got {len(idx)}")
+        return idx, len(idx)
+
     def get_jacobian(self, bodies=None, env_ids=None, q=None, out=None):
         """gym.acquire_jacobian_tensor / refresh_jacobian_tensors for the hand: (k, nb, 6, 26) geometric Jacobians of the hand
         bodies `bodies` -- indices into the rows of rigid_body_states or names from hand_model.BODY_NAMES such as
@@ -873,25 +894,7 @@ class DexHandEnv:
         velocity; column j: DOF j of dof_state, so jac[i, b] @ dof_vel[env] == rigid_body_states[env, b, 7:13].  Rows: the
         envs `env_ids` (None = all), or the rows of a (k, 26) joint-position override `q` (env_ids is then ignored)."""
         core, ids, q, k = self._kindyn_rows("get_jacobian", "body_jacobian", env_ids, q)
-        if bodies is None:
-            idx = None
-            nb = _abi.NUM_HAND_BODIES
-        else:
-            if isinstance(bodies, (str, int)):
-                bodies = [bodies]
-            idx = []
-            for b in bodies:
-                if isinstance(b, str):
-                    if b not in self.model.body_names:
-                        raise ValueError(f"get_jacobian: unknown body '{b}' (bodies: {self.model.body_names})")
-                    b = self.model.body_names.index(b)
-                b = int(b)
-                if not 0 <= b < _abi.NUM_HAND_BODIES:
-                    raise ValueError(f"get_jacobian: body index must be in [0, {_abi.NUM_HAND_BODIES}), got {b}")
-                idx.append(b)
-            nb = len(idx)
-            if not 1 <= nb <= _abi.NUM_HAND_BODIES:
-                raise ValueError(f"get_jacobian: between 1 and {_abi.NUM_HAND_BODIES} bodies, got {nb}")
+        idx, nb = self._kindyn_bodies("get_jacobian", bodies)
         out = self._kindyn_out("get_jacobian", out, (k, nb, 6, _abi.NJ), core.device)
         core.body_jacobian(out, env_ids=ids, q=q, bodies=idx)
         return out
@@ -912,6 +915,48 @@ class DexHandEnv:
         M = self._kindyn_out("get_mass_matrix", out, (k, _abi.NJ, _abi.NJ), core.device)
         core.mass_matrix(mass=M, env_ids=ids, q=q)
         return M
+
+    # ------------------------------------------------------------------ inverse dynamics, bias accelerations
+    def _kindyn_rows_qd(self, what, method, env_ids, q, qd):
+        """_kindyn_rows for the queries that are functions of (q, qd): the overrides go together."""
+        core, ids, qt, k = self._kindyn_rows(what, method, env_ids, q)
+        if (q is None) != (qd is None):
+            raise ValueError(f"{what}: q and qd go together: both None (the envs' state) or both (k, {_abi.NJ}) overrides")
+        return core, ids, qt, self._kindyn_vel(what, "qd", qd, k, core.device), k
+
+    def _kindyn_vel(self, what, name, t, k, device):
+        if t is None:
+            return None
+        t = torch.as_tensor(t, dtype=torch.float32, device=device)
+        if tuple(t.shape) != (k, _abi.NJ):
+            raise ValueError(f"{what}: {name} must have shape ({k}, {_abi.NJ}), got {tuple(t.shape)}")
+        return t.contiguous()
+
+    def get_inverse_dynamics(self, qdd=None, env_ids=None, q=None, qd=None, gravity=True, out=None):
+        """(k, 26) generalized forces tau = M(q) qdd + c(q, qd) (+ g(q) with gravity=True) that produce the joint accelerations
+        `qdd` (k, 26; None = zero), with the M and g of get_mass_matrix: no armature, no PD terms, no contact.  Rows: the envs
+        `env_ids` (None = all) at their dof_pos / dof_vel, or the rows of the (k, 26) overrides `q` and `qd`, which go together
+        (env_ids is then ignored).  Row i of qdd belongs to row i of the result on either path."""
+        core, ids, q, qd, k = self._kindyn_rows_qd("get_inverse_dynamics", "inverse_dynamics", env_ids, q, qd)
+        qdd = self._kindyn_vel("get_inverse_dynamics", "qdd", qdd, k, core.device)
+        out = self._kindyn_out("get_inverse_dynamics", out, (k, _abi.NJ), core.device)
+        core.inverse_dynamics(out, qdd=qdd, env_ids=ids, q=q, qd=qd, gravity=gravity)
+        return out
+
+    def get_bias_forces(self, env_ids=None, q=None, qd=None, gravity=True, out=None):
+        """get_inverse_dynamics at qdd = 0: the (k, 26) velocity-product force c(q, qd), plus g(q) with gravity=True -- what a
+        computed-torque controller adds to M(q) qdd."""
+        return self.get_inverse_dynamics(None, env_ids, q, qd, gravity, out)
+
+    def get_body_bias_acceleration(self, bodies=None, env_ids=None, q=None, qd=None, out=None):
+        """(k, nb, 6) Jdot qd of the hand bodies `bodies` (as for get_jacobian): world linear acceleration of the body origin
+        (0-2) and angular acceleration (3-5) at zero joint acceleration, without gravity, so that get_jacobian(...)[i, b] @ qdd +
+        this is the derivative of rigid_body_states[env, b, 7:13].  Rows as for get_inverse_dynamics."""
+        core, ids, q, qd, k = self._kindyn_rows_qd("get_body_bias_acceleration", "body_bias_accel", env_ids, q, qd)
+        idx, nb = self._kindyn_bodies("get_body_bias_acceleration", bodies)
+        out = self._kindyn_out("get_body_bias_acceleration", out, (k, nb, 6), core.device)
+        core.body_bias_accel(out, env_ids=ids, q=q, qd=qd, bodies=idx)
+        return out
 
     # ------------------------------------------------------------------ fingertip inverse kinematics
     @property

@@ -727,6 +727,48 @@ int dexsim_proximity_pair(int i, int* cap_a, int* cap_b, int* group);
 int dexsim_query_proximity(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* box_pose, float box_size,
                            float* cap_env, float* self_min, float* pair_dist, void* stream);
 
+/* ------------------------------------------------------------------ inverse dynamics and bias accelerations
+ * The velocity-dependent members of the family that dexsim_body_jacobian / dexsim_mass_matrix begin: what a joint-space computed-torque
+ * or impedance controller (tau = M qdd + c + g) and an operational-space or fingertip-force controller (xdd = J qdd + Jdot qd)
+ * need beyond J(q), M(q) and g(q).  Functions of (q, qd).  Both calls are stream-ordered, never synchronise and allocate nothing,
+ * and neither writes any arena word, API tensor, statistics word, counter or the step stamp.
+ *
+ * ROWS are those of dexsim_body_jacobian.  q and qd are BOTH NULL or BOTH device (k, 26) row-major overrides in dof_state order.
+ * Both NULL: row i is env env_ids[i] (NULL: env i, and k must be num_envs) with its current q and qd (arena); a row whose id is
+ * outside [0, num_envs) leaves its output row untouched.  Both given: they take the place of the state, env_ids is ignored and k
+ * may be any positive number; a row of (q, qd) equal to an env's current state gives that env's output bit for bit.  Exactly one
+ * of q and qd NULL is an error.
+ *
+ * INVERSE DYNAMICS  tau (k, 26) f32, 4-byte aligned:
+ *     tau = M(q) qdd + c(q, qd)                       flags == 0
+ *     tau = M(q) qdd + c(q, qd) + g(q)                flags == DEXSIM_ID_GRAVITY
+ * the generalized force (N on the slides, N m on the hinges) that produces the joint acceleration qdd at the state (q, qd) --
+ * by one recursive Newton-Euler pass, M is never formed.  M and g are those of dexsim_mass_matrix: general symmetric link
+ * inertias, cfg.gravity, NO armature, NO PD terms, no contact and no joint-limit forces (the integrator's M^ adds
+ * diag(armature + h (kd + h kp)); a controller that wants the armature adds armature[j] * qdd[j] itself).  c(q, qd) is the
+ * velocity-product (Coriolis and centrifugal) force: c_i = sum_jk (dM_ij/dq_k - 1/2 dM_jk/dq_i) qd_j qd_k.
+ * qdd: an optional device (k, 26) array aligned with the OUTPUT rows on either row path (row i of qdd belongs to row i of tau,
+ * whichever env that is); NULL means zero, and tau is then the bias force c [+ g].  At qd = 0 and qdd = NULL with the gravity
+ * flag the result is the gravity output of dexsim_mass_matrix to roundoff.
+ *
+ * BIAS ACCELERATIONS  acc (k, nb, 6) f32, 4-byte aligned; bodies as for dexsim_body_jacobian (HOST array of nb hand-body indices,
+ * NULL = all DEXSIM_NUM_HAND_BODIES in order, nb must then be DEXSIM_NUM_HAND_BODIES).  Words 0-2: world linear acceleration of
+ * the body-frame origin, words 3-5: world angular acceleration, both at qdd = 0 and without gravity: Jdot(q, qd) qd.  Contract:
+ * with jac of dexsim_body_jacobian for the same body, jac[i, b] @ qdd + acc[i, b] is the time derivative of
+ * rigid_body_states[env, b, 7:13] for the joint acceleration qdd.  Body 0 (hand_mount, welded to the fixed spawn frame) is all
+ * zeros; with only slides moving, or qd = 0, everything is zero.  The bodies ride on the joint frames rigid_body_states places
+ * them on; a model whose body_parent says otherwise is refused.
+ *
+ * DEXSIM_ERR_ARG (with a dexsim_last_error text; no device needed, nothing is launched): NULL handle, k <= 0, env_ids == NULL
+ * without overrides and k != num_envs, exactly one of q and qd NULL, flag bits other than DEXSIM_ID_GRAVITY, nb outside
+ * [1, DEXSIM_NUM_HAND_BODIES], a body index out of range, bodies == NULL with nb != DEXSIM_NUM_HAND_BODIES, a NULL or misaligned
+ * output.  DEXSIM_ERR_NOT_BOUND before dexsim_bind. */
+#define DEXSIM_ID_GRAVITY 1   /* include the gravity force g(q) */
+int dexsim_inverse_dynamics(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const float* qdd,
+                            int flags, float* tau, void* stream);
+int dexsim_body_bias_accel(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const int* bodies, int nb,
+                           float* acc, void* stream);
+
 const char* dexsim_error_string(int code);
 const char* dexsim_last_error(void);
 
