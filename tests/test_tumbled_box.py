@@ -73,15 +73,13 @@ def _snap(b, fields=FIELDS):
 
 
 # ------------------------------------------------------------------------------------------------- references, computed once
-@functools.lru_cache(maxsize=None)
-def _teacher_ref(kind, n):
+def teacher_ref(sc, ms, start):
     """Three teacher-forced sub-steps on the fp64 and the fp32 oracle (fresh instances): after each, q, qd and the box state of both
     are put to the fp64 oracle's values rounded to float32, so that every sub-step starts from one state.  Per sub-step: the
     float32 state it started from, both snapshots and (first sub-step) both contact lists."""
     from oracle.oracle import Oracle
-    sc, _, ms = _setup(n)
+    n = int(sc.num_envs)
     o64, o32 = Oracle(sc, ms, f64=True), Oracle(sc, ms)
-    start = _state(kind, n)
     _load(o64, start), _load(o32, start)
     out = []
     for sub in range(3):
@@ -94,6 +92,12 @@ def _teacher_ref(kind, n):
         start = {k: ts._f32(o64.get(k)) for k in SYNC}
         _load(o64, start), _load(o32, start)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def _teacher_ref(kind, n):
+    sc, _, ms = _setup(n)
+    return teacher_ref(sc, ms, _state(kind, n))
 
 
 @functools.lru_cache(maxsize=None)
@@ -318,9 +322,9 @@ def _assert_c_rule(report, label):
         assert r[3] <= C_RULE * r[2] + 1e-6, (f, r)
 
 
-def _check_teacher_forced(make, kind, n):
-    """3.2 for the backend that make() returns."""
-    recs = _teacher_ref(kind, n)
+def _check_teacher_forced(make, kind, n, recs=None, label=""):
+    """3.2 for the backend that make() returns; recs: the references, those of the default configuration if None."""
+    recs = _teacher_ref(kind, n) if recs is None else recs
     b = make()
     same, report = np.ones(n, bool), {}
     for rec in recs:
@@ -332,8 +336,9 @@ def _check_teacher_forced(make, kind, n):
         same = _agree(same, rec["s64"]["ncontact"], rec["s32"]["ncontact"], sh["ncontact"])   # (an env left out stays out: its cache differs)
         assert (sh["corner"][:, same] == rec["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
         _accumulate_snap(report, rec["s64"], rec["s32"], sh, same, FIELDS)
-    _assert_c_rule(report, f"teacher-forced, {kind}, n = {n}")
+    _assert_c_rule(report, f"teacher-forced, {label}{kind}, n = {n}")
     assert "wlam 80-83" in report
+    return report
 
 
 # Measured on one MI355X, ratios |HIP - fp64| / |fp32 oracle - fp64| at the 99.9th percentile / at the maximum (the fp32 oracle's own

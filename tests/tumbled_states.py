@@ -101,10 +101,11 @@ def hand_clear_state(rng, model, n, box_size=0.05):
     return {k: _f32(v) for k, v in st.items()}
 
 
-def hand_on_box_state(rng, model, sc, ms, n):
+def hand_on_box_state(rng, model, sc, ms, n, near=False):
     """The hand on a tumbled box (lowest corner at U(-0.3, 0.8) mm).  The hand's height is found per env on a SEPARATE fp64 oracle
     instance (an instance that placed the hand keeps its warm-start cache): the slide q[2] goes down from +0.05 to -0.44 in 2 mm
-    rungs, the env takes the first rung at which its list has an entry that is not box / ground, minus U(0, 2) mm."""
+    rungs, the env takes the first rung at which its list has an entry that is not box / ground, minus U(0, 2) mm.
+    near = True ("hand_near_box"): the rung above that one, plus U(0, 2) mm -- the hand is 2-4 mm short of its first touch."""
     from oracle.oracle import Oracle
     st = _base_state(rng, model, n, True)
     st["q"][:2] = rng.uniform(-0.04, 0.04, (2, n))
@@ -132,11 +133,20 @@ def hand_on_box_state(rng, model, sc, ms, n):
         if (first >= 0).all():
             break
     assert (first >= 0).all(), "a hand never reached box or ground"
-    st["q"][2] = _f32(rungs[first] - 1e-3 * rng.uniform(0.0, 2.0, n))
+    past = 1e-3 * rng.uniform(0.0, 2.0, n)
+    st["q"][2] = _f32(rungs[first - 1] + past) if near else _f32(rungs[first] - past)
     tg = st["q"] + rng.normal(0, 0.03, (26, n))
     tg[2] = st["q"][2] - 0.01
     st["targets"] = _f32(tg)
     return st
+
+
+def _draw(kind, n, seed, sc, model):
+    rng = np.random.default_rng(seed)
+    if kind == "box_alone":
+        return hand_clear_state(rng, model, n, float(sc.box_size))
+    assert kind in ("hand_on_box", "hand_near_box")
+    return hand_on_box_state(rng, model, sc, model.to_struct(), n, near=kind == "hand_near_box")
 
 
 @functools.lru_cache(maxsize=None)
@@ -144,14 +154,23 @@ def _cached(kind, n, seed):
     from dexrobot_isaac_amd.config import build_sim_config, default_cfg
     cfg = default_cfg("BlindGrasping")
     cfg["env"]["numEnvs"] = n
-    sc, model = build_sim_config(cfg)
-    rng = np.random.default_rng(seed)
-    if kind == "box_alone":
-        return hand_clear_state(rng, model, n, float(sc.box_size))
-    assert kind == "hand_on_box"
-    return hand_on_box_state(rng, model, sc, model.to_struct(), n)
+    return _draw(kind, n, seed, *build_sim_config(cfg))
 
 
-def sample(kind, n=256, seed=11):
-    """The "box_alone" / "hand_on_box" state of n envs (default BlindGrasping configuration), built once per process; a fresh copy."""
-    return {k: v.copy() for k, v in _cached(kind, n, seed).items()}
+_BY_CONFIG = {}
+
+
+def sample(kind, n=256, seed=11, config=None):
+    """The "box_alone" / "hand_on_box" / "hand_near_box" state of n envs, built once per process; a fresh copy.  `config`: None for
+    the default BlindGrasping configuration, or (sc, model) -- a DexSimConfig of n envs and the hand model it goes with; the sample is
+    kept per value of the two structs."""
+    if config is None:
+        st = _cached(kind, n, seed)
+    else:
+        sc, model = config
+        assert int(sc.num_envs) == n
+        key = (kind, n, seed, bytes(sc), bytes(model.to_struct()))
+        if key not in _BY_CONFIG:
+            _BY_CONFIG[key] = _draw(kind, n, seed, sc, model)
+        st = _BY_CONFIG[key]
+    return {k: v.copy() for k, v in st.items()}
