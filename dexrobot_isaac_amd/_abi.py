@@ -127,6 +127,8 @@ class DexSimCamera(C.Structure):
 IK_MAX_ITERS = 64   # DEXSIM_IK_MAX_ITERS
 NPROX_GROUPS, NPROX_PAIRS = 15, 120   # DEXSIM_NPROX_GROUPS, DEXSIM_NPROX_PAIRS: the pair table of dexsim_query_proximity
 ID_GRAVITY = 1   # DEXSIM_ID_GRAVITY: dexsim_inverse_dynamics includes the gravity force
+FD_GRAVITY, FD_ARMATURE = 1, 2   # DEXSIM_FD_GRAVITY, DEXSIM_FD_ARMATURE: flags of dexsim_forward_dynamics / dexsim_mass_solve
+MSOLVE_MAX_RHS = 32   # DEXSIM_MSOLVE_MAX_RHS
 
 
 class DexSimIK(C.Structure):
@@ -149,6 +151,7 @@ EXPORTED_SYMBOLS = [
     "dexsim_ik_struct_size", "dexsim_solve_ik",
     "dexsim_proximity_pair", "dexsim_query_proximity",
     "dexsim_inverse_dynamics", "dexsim_body_bias_accel",
+    "dexsim_forward_dynamics", "dexsim_mass_solve",
 ]
 
 
@@ -200,6 +203,8 @@ def declare_prototypes(lib):
     lib.dexsim_query_proximity.argtypes = [vp, vp, i32, vp, vp, f32, vp, vp, vp, vp]
     lib.dexsim_inverse_dynamics.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
     lib.dexsim_body_bias_accel.argtypes = [vp, vp, i32, vp, vp, P(i32), i32, vp, vp]
+    lib.dexsim_forward_dynamics.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
+    lib.dexsim_mass_solve.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = i32
     lib.dexsim_error_string.argtypes = [i32]

@@ -458,6 +458,32 @@ class DexSimCore:
         self._keep_kin = self._keep_kin + (qd,)
         check(self.lib.dexsim_body_bias_accel(self.h, ids, k, qp, vp, bp, nb, op, self._stream()), "body_bias_accel")
 
+    # ------------------------------------------------------------------ forward dynamics, mass-matrix solves
+    def forward_dynamics(self, out, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False):
+        """qdd = (M(q) [+ A])^-1 (tau - c(q, qd) [- g(q)]) into `out` (k, 26) f32, with the M, c and g of mass_matrix and
+        inverse_dynamics; armature=True solves with M + diag(model.armature).  tau: (k, 26) aligned with the output rows,
+        None = zero (out is then the free acceleration).  Rows as for inverse_dynamics.  dexsim_forward_dynamics."""
+        ids, qp, vp, k = self._kin_rows_qd("forward_dynamics", env_ids, q, qd)
+        tp = None if tau is None else self._kin_vel("forward_dynamics", "tau", tau, k)
+        op = self._kin_out("forward_dynamics", "out", out, (k, _abi.NJ))
+        self._keep_kin = self._keep_kin + (qd, tau)
+        flags = (_abi.FD_GRAVITY if gravity else 0) | (_abi.FD_ARMATURE if armature else 0)
+        check(self.lib.dexsim_forward_dynamics(self.h, ids, k, qp, vp, tp, flags, op, self._stream()), "forward_dynamics")
+
+    def mass_solve(self, out, rhs, env_ids=None, q=None, armature=False):
+        """out[i, r] = (M(q_i) [+ A])^-1 rhs[i, r] for `rhs` and `out` (k, nrhs, 26) f32, nrhs in [1, 32]; a row is factored once.
+        `out` may be `rhs` itself (in place).  Rows as for mass_matrix.  dexsim_mass_solve."""
+        ids, qp, k = self._kin_rows("mass_solve", env_ids, q)
+        if rhs.dim() != 3 or not 1 <= rhs.shape[1] <= _abi.MSOLVE_MAX_RHS:
+            raise DexSimError(f"mass_solve: rhs must have shape ({k}, nrhs, {_abi.NJ}) with nrhs in [1, {_abi.MSOLVE_MAX_RHS}], "
+                              f"got {tuple(rhs.shape)}")
+        nrhs = int(rhs.shape[1])
+        rp = self._kin_out("mass_solve", "rhs", rhs, (k, nrhs, _abi.NJ))
+        op = self._kin_out("mass_solve", "out", out, (k, nrhs, _abi.NJ))
+        self._keep_kin = self._keep_kin + (rhs,)
+        check(self.lib.dexsim_mass_solve(self.h, ids, k, qp, rp, nrhs, _abi.FD_ARMATURE if armature else 0, op, self._stream()),
+              "mass_solve")
+
     # ------------------------------------------------------------------ fingertip inverse kinematics
     def solve_ik(self, targets, controls, env_ids=None, q=None, sites=0, frame=0, free_mask=0x3FFC0, weights=(1, 1, 1, 1, 1),
                  iters=16, damping=1e-3, max_step=0.5, q_out=None, residual=None):

@@ -1051,3 +1051,42 @@ extern "C" int dexsim_body_bias_accel(dexsim_t h, const int64_t* env_ids, int k,
   LAUNCH_CHECK();
   return DEXSIM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------- forward dynamics, mass-matrix solves
+// Behind the inverse dynamics: the kernel uses its Newton-Euler helpers.
+// clang-format off
+#include "dexsim_fwddyn.hip.inc"
+// clang-format on
+
+extern "C" int dexsim_forward_dynamics(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const float* tau,
+                                       int flags, float* qdd, void* stream) {
+  FwdDyn K;
+  std::memset(&K, 0, sizeof K);
+  int rc = kin_rows_qd("dexsim_forward_dynamics", h, env_ids, k, q, qd, &K.rows);
+  if (rc) return rc;
+  if ((flags & ~(DEXSIM_FD_GRAVITY | DEXSIM_FD_ARMATURE)) != 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_forward_dynamics: unknown flag bits (DEXSIM_FD_GRAVITY and DEXSIM_FD_ARMATURE are the flags)");
+  if (!qdd || ((uintptr_t)qdd & 3) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_forward_dynamics: qdd must be a 4-byte aligned device pointer");
+  NEED_BOUND(h);
+  K.qd = qd; K.rhs = tau; K.out = qdd; K.nrhs = 1; K.gravity = flags & DEXSIM_FD_GRAVITY; K.armature = flags & DEXSIM_FD_ARMATURE;
+  k_kin_fwddyn<true><<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_mass_solve(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* rhs, int nrhs, int flags,
+                                 float* out, void* stream) {
+  FwdDyn K;
+  std::memset(&K, 0, sizeof K);
+  int rc = kin_rows("dexsim_mass_solve", h, env_ids, k, q, &K.rows);
+  if (rc) return rc;
+  if ((flags & ~DEXSIM_FD_ARMATURE) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: unknown flag bits (DEXSIM_FD_ARMATURE is the only flag)");
+  if (nrhs < 1 || nrhs > DEXSIM_MSOLVE_MAX_RHS) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: nrhs must be in [1, DEXSIM_MSOLVE_MAX_RHS]");
+  if (!rhs) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: rhs must not be NULL");
+  if (!out || ((uintptr_t)out & 3) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: out must be a 4-byte aligned device pointer");
+  NEED_BOUND(h);
+  K.rhs = rhs; K.out = out; K.nrhs = nrhs; K.armature = flags & DEXSIM_FD_ARMATURE;
+  k_kin_fwddyn<false><<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
+  LAUNCH_CHECK();
+  return DEXSIM_OK;
+}

@@ -958,6 +958,33 @@ class DexHandEnv:
         core.body_bias_accel(out, env_ids=ids, q=q, qd=qd, bodies=idx)
         return out
 
+    # ------------------------------------------------------------------ forward dynamics, mass-matrix solves
+    def get_forward_dynamics(self, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False, out=None):
+        """(k, 26) joint accelerations qdd = (M(q) [+ A])^-1 (tau - c(q, qd) [- g(q)]) that the generalized forces `tau` (k, 26;
+        None = zero: the free acceleration) produce -- the inverse of get_inverse_dynamics, with the same M, c and g: no PD terms,
+        no contact, no joint-limit forces (fold them into tau).  armature=True solves with M + diag(model.armature).  Rows as for
+        get_inverse_dynamics; row i of tau belongs to row i of the result on either path."""
+        core, ids, q, qd, k = self._kindyn_rows_qd("get_forward_dynamics", "forward_dynamics", env_ids, q, qd)
+        tau = self._kindyn_vel("get_forward_dynamics", "tau", tau, k, core.device)
+        out = self._kindyn_out("get_forward_dynamics", out, (k, _abi.NJ), core.device)
+        core.forward_dynamics(out, tau=tau, env_ids=ids, q=q, qd=qd, gravity=gravity, armature=armature)
+        return out
+
+    def solve_mass_matrix(self, rhs, env_ids=None, q=None, armature=False, out=None):
+        """(M(q) [+ A])^-1 applied to `rhs` (k, 26) or (k, nrhs, 26), nrhs <= 32, without forming M; the result has rhs's shape.
+        Each row is factored once for all its right-hand sides.  With rows of get_jacobian as right-hand sides this is
+        M^-1 J^T (Lambda^-1 = J M^-1 J^T), with 26 unit columns M^-1 itself.  Rows as for get_mass_matrix; `out` may be `rhs`."""
+        core, ids, q, k = self._kindyn_rows("solve_mass_matrix", "mass_solve", env_ids, q)
+        rhs = torch.as_tensor(rhs, dtype=torch.float32, device=core.device)
+        if rhs.dim() not in (2, 3) or rhs.shape[0] != k or rhs.shape[-1] != _abi.NJ or \
+                (rhs.dim() == 3 and not 1 <= rhs.shape[1] <= _abi.MSOLVE_MAX_RHS):
+            raise ValueError(f"solve_mass_matrix: rhs must have shape ({k}, {_abi.NJ}) or ({k}, nrhs, {_abi.NJ}) with nrhs in "
+                             f"[1, {_abi.MSOLVE_MAX_RHS}], got {tuple(rhs.shape)}")
+        shape = tuple(rhs.shape)
+        out = self._kindyn_out("solve_mass_matrix", out, shape, core.device)
+        core.mass_solve(out.view(k, -1, _abi.NJ), rhs.contiguous().view(k, -1, _abi.NJ), env_ids=ids, q=q, armature=armature)
+        return out
+
     # ------------------------------------------------------------------ fingertip inverse kinematics
     @property
     def control_names(self):

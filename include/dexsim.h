@@ -769,6 +769,43 @@ int dexsim_inverse_dynamics(dexsim_t h, const int64_t* env_ids, int k, const flo
 int dexsim_body_bias_accel(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const int* bodies, int nb,
                            float* acc, void* stream);
 
+/* ------------------------------------------------------------------ forward dynamics and mass-matrix solves
+ * The inverse direction of the family: which joint acceleration a generalized force produces at (q, qd), and M(q)^-1 applied to
+ * caller vectors without forming M -- what a planner that rolls candidate torques forward, an operational-space controller
+ * (Lambda^-1 = J M^-1 J^T), an effective-mass or impulse-response query and a check of a computed-torque controller need.  M is
+ * block-arrow (base block, five finger blocks, no finger-finger coupling): the fingers are eliminated, the 6 x 6 Schur complement
+ * is factored by Cholesky and the result back-substituted, one launch, 26 words written per row and right-hand side.  Both calls
+ * are stream-ordered, never synchronise and allocate nothing, and neither writes any arena word, API tensor, statistics word,
+ * counter or the step stamp.  A row's result depends on that row alone and is reproducible bit for bit.
+ *
+ * FORWARD DYNAMICS  qdd (k, 26) f32, 4-byte aligned:
+ *     qdd = (M(q) [+ A])^-1 (tau - c(q, qd) [- g(q)])
+ * M, c and g are exactly those of dexsim_mass_matrix and dexsim_inverse_dynamics: general symmetric link inertias, cfg.gravity, no
+ * PD terms, no contact and no joint-limit forces (a caller folds such forces into tau).  g is included with DEXSIM_FD_GRAVITY; the
+ * call is then the inverse of dexsim_inverse_dynamics with DEXSIM_ID_GRAVITY.  DEXSIM_FD_ARMATURE solves with M + A,
+ * A = diag(DexHandModel::armature): for the inverse a caller cannot add the armature afterwards, so the flag exists here.
+ * ROWS and the (q, qd) overrides are those of dexsim_inverse_dynamics, word for word.  tau: an optional device (k, 26) array
+ * aligned with the OUTPUT rows on either row path; NULL means zero, and qdd is then the free acceleration.
+ *
+ * MASS SOLVE  out (k, nrhs, 26) f32, 4-byte aligned:
+ *     out[i, r, :] = (M(q_i) [+ A])^-1 rhs[i, r, :]          nrhs in [1, DEXSIM_MSOLVE_MAX_RHS]
+ * A function of q only; DEXSIM_FD_ARMATURE is the only flag.  ROWS and the q override are those of dexsim_mass_matrix; rhs is a
+ * device (k, nrhs, 26) array aligned with the output rows.  A row is factored once and solved for all nrhs right-hand sides; a
+ * column does not depend on nrhs or on its position among the columns.  out == rhs (in place) is allowed, any other overlap is
+ * undefined.  With rows of dexsim_body_jacobian as right-hand sides this gives M^-1 J^T, with 26 unit columns M^-1 itself.  With
+ * qd = 0, flags 0 and tau = r, dexsim_forward_dynamics returns the bits of the mass solve of r with nrhs = 1.
+ *
+ * DEXSIM_ERR_ARG (with a dexsim_last_error text; no device needed, nothing is launched): NULL handle, k <= 0, env_ids == NULL
+ * without overrides and k != num_envs, exactly one of q and qd NULL, unknown flag bits (DEXSIM_FD_GRAVITY on the mass solve is
+ * one), nrhs outside its range, NULL rhs, a NULL or misaligned output.  DEXSIM_ERR_NOT_BOUND before dexsim_bind. */
+#define DEXSIM_FD_GRAVITY 1    /* gravity acts on the hand (same value as DEXSIM_ID_GRAVITY) */
+#define DEXSIM_FD_ARMATURE 2   /* solve with M + diag(DexHandModel::armature) */
+#define DEXSIM_MSOLVE_MAX_RHS 32
+int dexsim_forward_dynamics(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const float* tau,
+                            int flags, float* qdd, void* stream);
+int dexsim_mass_solve(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* rhs, int nrhs, int flags,
+                      float* out, void* stream);
+
 const char* dexsim_error_string(int code);
 const char* dexsim_last_error(void);
 
