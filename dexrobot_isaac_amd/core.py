@@ -387,20 +387,23 @@ class DexSimCore:
                               f"got {t.dtype} {tuple(t.shape)} on {t.device}")
         return C.c_void_p(t.data_ptr())
 
+    def _kin_bodies(self, what, bodies):
+        """(nb, c_int array or None = all 37) of a body list."""
+        if bodies is None:
+            return _abi.NUM_HAND_BODIES, None
+        bl = [int(b) for b in bodies]
+        nb = len(bl)
+        if not 1 <= nb <= _abi.NUM_HAND_BODIES:
+            raise DexSimError(f"{what}: between 1 and {_abi.NUM_HAND_BODIES} bodies, got {nb}")
+        return nb, (C.c_int * nb)(*bl)
+
     def body_jacobian(self, out, env_ids=None, q=None, bodies=None):
         """Geometric Jacobians of the hand bodies `bodies` (indices into the rows of rigid_body_states; None = all 37) into
         `out` (k, nb, 6, 26) f32: rows 0-2 linear velocity of the body origin, 3-5 angular velocity, world frame, so that
         out[i, b] @ qd == rigid_body_states[env, b, 7:13].  Rows: env_ids (None = all envs), or the rows of a (k, 26) `q`
         override (env_ids is then ignored).  dexsim_body_jacobian."""
         ids, qp, k = self._kin_rows("body_jacobian", env_ids, q)
-        if bodies is None:
-            nb, bp = _abi.NUM_HAND_BODIES, None
-        else:
-            bl = [int(b) for b in bodies]
-            nb = len(bl)
-            if not 1 <= nb <= _abi.NUM_HAND_BODIES:
-                raise DexSimError(f"body_jacobian: between 1 and {_abi.NUM_HAND_BODIES} bodies, got {nb}")
-            bp = (C.c_int * nb)(*bl)
+        nb, bp = self._kin_bodies("body_jacobian", bodies)
         op = self._kin_out("body_jacobian", "out", out, (k, nb, 6, _abi.NJ))
         check(self.lib.dexsim_body_jacobian(self.h, ids, k, qp, bp, nb, op, self._stream()), "body_jacobian")
 
@@ -446,14 +449,7 @@ class DexSimCore:
         origin (0-2) and angular acceleration (3-5) at qdd = 0, without gravity, so that body_jacobian's out[i, b] @ qdd + this
         is the derivative of rigid_body_states[env, b, 7:13].  Rows as for inverse_dynamics.  dexsim_body_bias_accel."""
         ids, qp, vp, k = self._kin_rows_qd("body_bias_accel", env_ids, q, qd)
-        if bodies is None:
-            nb, bp = _abi.NUM_HAND_BODIES, None
-        else:
-            bl = [int(b) for b in bodies]
-            nb = len(bl)
-            if not 1 <= nb <= _abi.NUM_HAND_BODIES:
-                raise DexSimError(f"body_bias_accel: between 1 and {_abi.NUM_HAND_BODIES} bodies, got {nb}")
-            bp = (C.c_int * nb)(*bl)
+        nb, bp = self._kin_bodies("body_bias_accel", bodies)
         op = self._kin_out("body_bias_accel", "out", out, (k, nb, 6))
         self._keep_kin = self._keep_kin + (qd,)
         check(self.lib.dexsim_body_bias_accel(self.h, ids, k, qp, vp, bp, nb, op, self._stream()), "body_bias_accel")

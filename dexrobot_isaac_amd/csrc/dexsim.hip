@@ -853,28 +853,47 @@ static int kin_rows(const char* who, dexsim_t h, const int64_t* env_ids, int k, 
   return DEXSIM_OK;
 }
 
+// a required output: non-NULL and `align`-byte aligned
+static int kin_out(const char* who, const char* name, const void* p, int align) {
+  if (p && ((uintptr_t)p & (uintptr_t)(align - 1)) == 0) return DEXSIM_OK;
+  return fail(DEXSIM_ERR_ARG, (std::string(who) + ": " + name + " must be a " + std::to_string(align) + "-byte aligned device pointer").c_str());
+}
+
+// A request of nb hand bodies (NULL = all of them, in order): the checks of the list, then of the output `name`, then that the
+// model's bodies ride on the frames kd_body_joint says.  body[i], where given, receives the i-th requested body.
+static int kin_bodies(const char* who, dexsim_t h, const int* bodies, int nb, unsigned char* body, const char* name, const void* out, int align) {
+  const std::string w(who);
+  if (nb < 1 || nb > DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, (w + ": nb must be in [1, DEXSIM_NUM_HAND_BODIES]").c_str());
+  if (!bodies && nb != DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, (w + ": bodies == NULL needs nb == DEXSIM_NUM_HAND_BODIES").c_str());
+  for (int i = 0; i < nb; i++) {
+    const int b = bodies ? bodies[i] : i;
+    if (b < 0 || b >= DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, (w + ": body index out of range").c_str());
+    if (body) body[i] = (unsigned char)b;
+  }
+  int rc = kin_out(who, name, out, align);
+  if (rc) return rc;
+  for (int b = 0; b < DEXSIM_NUM_HAND_BODIES; b++)
+    if (h->model.body_parent[b] != kd_body_joint(b))
+      return fail(DEXSIM_ERR_ARG, (w + ": model.body_parent differs from the frames rigid_body_states is published on").c_str());
+  return DEXSIM_OK;
+}
+
+// the family's grid: 64 rows per workgroup of KD_THREADS, `gy` workgroups along y
+#define KIN_LAUNCH(kernel, gy, args)                                                                                              \
+  kernel<<<dim3((unsigned)((k + 63) / 64), (unsigned)(gy)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, args, h->NS, h->N); \
+  LAUNCH_CHECK()
+
 extern "C" int dexsim_body_jacobian(dexsim_t h, const int64_t* env_ids, int k, const float* q, const int* bodies, int nb, float* jac,
                                     void* stream) {
   KinJac J;
   std::memset(&J, 0, sizeof J);
   int rc = kin_rows("dexsim_body_jacobian", h, env_ids, k, q, &J.rows);
   if (rc) return rc;
-  if (nb < 1 || nb > DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: nb must be in [1, DEXSIM_NUM_HAND_BODIES]");
-  if (!bodies && nb != DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: bodies == NULL needs nb == DEXSIM_NUM_HAND_BODIES");
-  for (int i = 0; i < nb; i++) {
-    const int b = bodies ? bodies[i] : i;
-    if (b < 0 || b >= DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: body index out of range");
-    J.body[i] = (unsigned char)b;
-  }
-  if (!jac || ((uintptr_t)jac & 15) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: jac must be a 16-byte aligned device pointer");
-  for (int b = 0; b < DEXSIM_NUM_HAND_BODIES; b++)
-    if (h->model.body_parent[b] != kd_body_joint(b))
-      return fail(DEXSIM_ERR_ARG, "dexsim_body_jacobian: model.body_parent differs from the frames rigid_body_states is published on");
+  rc = kin_bodies("dexsim_body_jacobian", h, bodies, nb, J.body, "jac", jac, 16);
+  if (rc) return rc;
   NEED_BOUND(h);
   J.jac = jac; J.nb = nb;
-  const dim3 grid((unsigned)((k + 63) / 64), (unsigned)((nb + KJ_CHUNK - 1) / KJ_CHUNK));
-  k_kin_jacobian<<<grid, dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, J, h->NS, h->N);
-  LAUNCH_CHECK();
+  KIN_LAUNCH(k_kin_jacobian, (nb + KJ_CHUNK - 1) / KJ_CHUNK, J);
   return DEXSIM_OK;
 }
 
@@ -888,8 +907,7 @@ extern "C" int dexsim_mass_matrix(dexsim_t h, const int64_t* env_ids, int k, con
     return fail(DEXSIM_ERR_ARG, "dexsim_mass_matrix: mass must be 16-byte aligned, gravity 4-byte aligned");
   NEED_BOUND(h);
   K.mass = mass; K.gravity = gravity;
-  k_kin_mass<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
-  LAUNCH_CHECK();
+  KIN_LAUNCH(k_kin_mass, 1, K);
   return DEXSIM_OK;
 }
 
@@ -932,8 +950,7 @@ extern "C" int dexsim_solve_ik(dexsim_t h, const int64_t* env_ids, int k, const 
   NEED_BOUND(h);
   K.targets = targets; K.controls = controls; K.q_out = q_out; K.residual = residual;
   K.prm = *prm; K.lam2 = prm->damping * prm->damping;
-  k_ik_solve<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
-  LAUNCH_CHECK();
+  KIN_LAUNCH(k_ik_solve, 1, K);
   return DEXSIM_OK;
 }
 
@@ -986,8 +1003,7 @@ extern "C" int dexsim_query_proximity(dexsim_t h, const int64_t* env_ids, int k,
   NEED_BOUND(h);
   K.hb = 0.5f * size;
   K.cap_env = cap_env; K.self_min = self_min; K.pair_dist = pair_dist;
-  k_proximity<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
-  LAUNCH_CHECK();
+  KIN_LAUNCH(k_proximity, 1, K);
   return DEXSIM_OK;
 }
 
@@ -1012,11 +1028,10 @@ extern "C" int dexsim_inverse_dynamics(dexsim_t h, const int64_t* env_ids, int k
   int rc = kin_rows_qd("dexsim_inverse_dynamics", h, env_ids, k, q, qd, &K.rows);
   if (rc) return rc;
   if ((flags & ~DEXSIM_ID_GRAVITY) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_inverse_dynamics: unknown flag bits (DEXSIM_ID_GRAVITY is the only flag)");
-  if (!tau || ((uintptr_t)tau & 3) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_inverse_dynamics: tau must be a 4-byte aligned device pointer");
+  if ((rc = kin_out("dexsim_inverse_dynamics", "tau", tau, 4))) return rc;
   NEED_BOUND(h);
   K.qd = qd; K.qdd = qdd; K.tau = tau; K.gravity = flags & DEXSIM_ID_GRAVITY;
-  k_kin_invdyn<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
-  LAUNCH_CHECK();
+  KIN_LAUNCH(k_kin_invdyn, 1, K);
   return DEXSIM_OK;
 }
 
@@ -1026,12 +1041,8 @@ extern "C" int dexsim_body_bias_accel(dexsim_t h, const int64_t* env_ids, int k,
   std::memset(&K, 0, sizeof K);
   int rc = kin_rows_qd("dexsim_body_bias_accel", h, env_ids, k, q, qd, &K.rows);
   if (rc) return rc;
-  if (nb < 1 || nb > DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: nb must be in [1, DEXSIM_NUM_HAND_BODIES]");
-  if (!bodies && nb != DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: bodies == NULL needs nb == DEXSIM_NUM_HAND_BODIES");
-  for (int i = 0; i < nb; i++) {
-    const int b = bodies ? bodies[i] : i;
-    if (b < 0 || b >= DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: body index out of range");
-  }
+  rc = kin_bodies("dexsim_body_bias_accel", h, bodies, nb, nullptr, "acc", acc, 4);
+  if (rc) return rc;
   int n = 0;   // the request sorted by the frame a body rides on: -1 (the spawn frame), then the joints in order
   for (int j = -1; j < DEXSIM_NJ; j++) {
     K.jstart[j + 1] = (unsigned char)n;
@@ -1041,14 +1052,9 @@ extern "C" int dexsim_body_bias_accel(dexsim_t h, const int64_t* env_ids, int k,
     }
   }
   K.jstart[DEXSIM_NJ + 1] = (unsigned char)n;
-  if (!acc || ((uintptr_t)acc & 3) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: acc must be a 4-byte aligned device pointer");
-  for (int b = 0; b < DEXSIM_NUM_HAND_BODIES; b++)
-    if (h->model.body_parent[b] != kd_body_joint(b))
-      return fail(DEXSIM_ERR_ARG, "dexsim_body_bias_accel: model.body_parent differs from the frames rigid_body_states is published on");
   NEED_BOUND(h);
   K.qd = qd; K.acc = acc; K.nb = nb;
-  k_kin_bias_accel<<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
-  LAUNCH_CHECK();
+  KIN_LAUNCH(k_kin_bias_accel, 1, K);
   return DEXSIM_OK;
 }
 
@@ -1066,11 +1072,10 @@ extern "C" int dexsim_forward_dynamics(dexsim_t h, const int64_t* env_ids, int k
   if (rc) return rc;
   if ((flags & ~(DEXSIM_FD_GRAVITY | DEXSIM_FD_ARMATURE)) != 0)
     return fail(DEXSIM_ERR_ARG, "dexsim_forward_dynamics: unknown flag bits (DEXSIM_FD_GRAVITY and DEXSIM_FD_ARMATURE are the flags)");
-  if (!qdd || ((uintptr_t)qdd & 3) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_forward_dynamics: qdd must be a 4-byte aligned device pointer");
+  if ((rc = kin_out("dexsim_forward_dynamics", "qdd", qdd, 4))) return rc;
   NEED_BOUND(h);
   K.qd = qd; K.rhs = tau; K.out = qdd; K.nrhs = 1; K.gravity = flags & DEXSIM_FD_GRAVITY; K.armature = flags & DEXSIM_FD_ARMATURE;
-  k_kin_fwddyn<true><<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
-  LAUNCH_CHECK();
+  KIN_LAUNCH(k_kin_fwddyn<true>, 1, K);
   return DEXSIM_OK;
 }
 
@@ -1083,10 +1088,9 @@ extern "C" int dexsim_mass_solve(dexsim_t h, const int64_t* env_ids, int k, cons
   if ((flags & ~DEXSIM_FD_ARMATURE) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: unknown flag bits (DEXSIM_FD_ARMATURE is the only flag)");
   if (nrhs < 1 || nrhs > DEXSIM_MSOLVE_MAX_RHS) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: nrhs must be in [1, DEXSIM_MSOLVE_MAX_RHS]");
   if (!rhs) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: rhs must not be NULL");
-  if (!out || ((uintptr_t)out & 3) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: out must be a 4-byte aligned device pointer");
+  if ((rc = kin_out("dexsim_mass_solve", "out", out, 4))) return rc;
   NEED_BOUND(h);
   K.rhs = rhs; K.out = out; K.nrhs = nrhs; K.armature = flags & DEXSIM_FD_ARMATURE;
-  k_kin_fwddyn<false><<<dim3((unsigned)((k + 63) / 64)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, K, h->NS, h->N);
-  LAUNCH_CHECK();
+  KIN_LAUNCH(k_kin_fwddyn<false>, 1, K);
   return DEXSIM_OK;
 }

@@ -1,13 +1,17 @@
 // dexsim_chain.hip.inc -- the frame the query kernels share (k_render_scene, k_kin_jacobian, k_kin_mass, k_ik_solve, k_proximity,
-// k_kin_invdyn, k_kin_bias_accel): pure functions of q (the last two of q and qd: kd_load_qd), off the step path, writing
+// k_kin_invdyn, k_kin_bias_accel, k_kin_fwddyn): pure functions of q (the last three of q and qd), off the step path, writing
 // caller-owned memory only.  Force-inlined functions and macros only: this file emits no code of its own.
 //
 //   joint_frame      THE joint-frame rule: parent frame -> a joint's offset, world axis and frame.  Every walk of the family is
 //                    written through it; publish_body (dexsim_physics.hip.inc) spells the same rule out for the step kernels.
 //   kd_*             the workgroup shape of the tensor queries: 64 rows x 5 waves, lanes along the rows, wave f walks finger f
-//                    (kd_load_q, kd_base_walk, kd_finger_joint; sincos_joint, never jframe), positions RELATIVE TO THE PALM
-//                    JOINT'S ORIGIN o5, per-row data staged in LDS as [word][row] with row stride KD_LD, a `valid` flag per row
-//                    that only gates stores (every lane reads legal addresses), kd_flush for rows that leave as they were staged.
+//                    (kd_base_walk, kd_finger_joint, kd_finger_link; sincos_joint, never jframe), positions RELATIVE TO THE PALM
+//                    JOINT'S ORIGIN o5, per-row data staged in LDS as [word][row] with row stride KD_LD.
+//   the row rule     kd_row / kd_env say which row and env a lane describes, kd_load_words reads its 6 + 4 words, kd_load puts the
+//                    two together for an override or an arena field (kd_load_q, kd_load_qd).  A `valid` flag per row only gates
+//                    stores: every lane reads legal addresses.  kd_flush writes rows that leave as they were staged, whole or as
+//                    a range of columns of longer rows.
+//   KD_TRI           the packed lower triangle every symmetric block of the family is kept in.
 
 #define KD_LD 65          /* LDS row stride in words: [word][row], padded by one */
 #define KD_THREADS 320    /* 5 waves: wave f walks finger f */
@@ -45,49 +49,40 @@ __host__ DI int kd_body_joint(int b) {
 
 struct KinBase { V3 a[6], orel[6]; Q4 q[6]; };   // world axes, origins relative to o5, frame orientations of the base joints
 
-// the row's q: 6 base joints + the 4 joints of finger f.  `valid` rows only decide about stores: every lane reads a legal address
-DI bool kd_load_q(const Arena& A, const KinRows& R, int N, int NR, int f, float* qb, float* qf) {
-  const int l = blockIdx.x * 64 + (threadIdx.x & 63);
-  bool valid = l < R.k;
-  if (R.q) {
-    const size_t row = (size_t)min(l, R.k - 1) * DEXSIM_NJ;
+// ---- the row rule: lane l = 64 blockIdx.x + lane describes row l of the call.  `valid` rows only decide about stores: every lane
+// reads a legal address -- row min(l, k - 1) of a (k, ...) array, env 0 of the arena where the row has no env.
+DI int kd_lane_row() { return blockIdx.x * 64 + (threadIdx.x & 63); }
+DI int kd_row(const KinRows& R) { return min(kd_lane_row(), R.k - 1); }
+
+// state path: the row's env (0 where it has none); `valid` also asks for an id inside [0, NR)
+DI int kd_env(const KinRows& R, int NR, bool& valid) {
+  long long id = kd_lane_row();
+  if (R.env_ids) id = GPTR(R.env_ids)[kd_row(R)];
+  valid = valid && id >= 0 && id < NR;
+  return valid ? (int)id : 0;
+}
+
+// 6 base words + the 4 words of finger f out of 26, word j at p[at + j step]: row r of a (k, 26) array (at = 26 r, step = 1) or an
+// arena field of env e (at = e, step = N)
+DI void kd_load_words(const float* p, size_t at, size_t step, int f, float* b, float* w) {
 #pragma unroll
-    for (int j = 0; j < 6; j++) qb[j] = GPTR(R.q)[row + j];
+  for (int j = 0; j < 6; j++) b[j] = GPTR(p)[at + j * step];
 #pragma unroll
-    for (int j = 0; j < 4; j++) qf[j] = GPTR(R.q)[row + 6 + 4 * f + j];
-  } else {
-    long long id = l;
-    if (R.env_ids) id = GPTR(R.env_ids)[min(l, R.k - 1)];
-    valid = valid && id >= 0 && id < NR;
-    const int e = valid ? (int)id : 0;
-#pragma unroll
-    for (int j = 0; j < 6; j++) qb[j] = FLD(q, j);
-#pragma unroll
-    for (int j = 0; j < 4; j++) qf[j] = FLD(q, 6 + 4 * f + j);
-  }
+  for (int j = 0; j < 4; j++) w[j] = GPTR(p)[at + (6 + 4 * f + j) * step];
+}
+
+// the row's words of the (k, 26) override `ov`, else of the arena field `fld` of the row's env; returns `valid`
+DI bool kd_load(const KinRows& R, const float* ov, const float* fld, int N, int NR, int f, float* b, float* w) {
+  bool valid = kd_lane_row() < R.k;
+  if (ov) kd_load_words(ov, (size_t)kd_row(R) * DEXSIM_NJ, 1, f, b, w);
+  else kd_load_words(fld, kd_env(R, NR, valid), N, f, b, w);
   return valid;
 }
 
-// the row's qd, for the queries that are functions of (q, qd): `qd` is the (k, 26) override that goes with R.q (both NULL or both
-// given), else the arena's qd of the env kd_load_q read q from.  Like kd_load_q, every lane reads a legal address.
-DI void kd_load_qd(const Arena& A, const KinRows& R, const float* qd, int N, int NR, int f, float* vb, float* vf) {
-  const int l = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (qd) {
-    const size_t row = (size_t)min(l, R.k - 1) * DEXSIM_NJ;
-#pragma unroll
-    for (int j = 0; j < 6; j++) vb[j] = GPTR(qd)[row + j];
-#pragma unroll
-    for (int j = 0; j < 4; j++) vf[j] = GPTR(qd)[row + 6 + 4 * f + j];
-  } else {
-    long long id = l;
-    if (R.env_ids) id = GPTR(R.env_ids)[min(l, R.k - 1)];
-    const int e = (l < R.k && id >= 0 && id < NR) ? (int)id : 0;
-#pragma unroll
-    for (int j = 0; j < 6; j++) vb[j] = FLD(qd, j);
-#pragma unroll
-    for (int j = 0; j < 4; j++) vf[j] = FLD(qd, 6 + 4 * f + j);
-  }
-}
+// the row's q (6 base joints + the 4 joints of finger f) and, for the queries that are functions of (q, qd), its qd: `qd` is the
+// (k, 26) override that goes with R.q (both NULL or both given), else the arena's qd of the env kd_load_q read q from
+DI bool kd_load_q(const Arena& A, const KinRows& R, int N, int NR, int f, float* qb, float* qf) { return kd_load(R, R.q, A.q, N, NR, f, qb, qf); }
+DI void kd_load_qd(const Arena& A, const KinRows& R, const float* qd, int N, int NR, int f, float* vb, float* vf) { kd_load(R, qd, A.qd, N, NR, f, vb, vf); }
 
 DI void kd_base_walk(const DevParams* __restrict__ P, const float* qb, KinBase& B) {
   Q4 qc = q4p(P->model.spawn_quat);
@@ -110,22 +105,36 @@ DI void kd_finger_joint(const JC& c, float qj, V3& of, Q4& qf, V3& aw) {
   of = of + F.d; aw = F.aw; qf = F.qn;
 }
 
+// one link of a finger chain: kd_finger_joint, then the link's centre (from the joint's origin) and inertia in world axes
+DI void kd_finger_link(const JC& c, float qj, V3& of, Q4& qf, V3& aw, V3& rc, S6& I) {
+  kd_finger_joint(c, qj, of, qf, aw);
+  const M3 Rj = q2mat(qf);
+  rc = mul(Rj, v3p(c.com));
+  I = rotate_inertia(Rj, c.inertia);
+}
+
+#define KD_TRI(i, j) ((i) * ((i) + 1) / 2 + (j))   /* packed lower triangle */
 #define KD_PUT3(w, v) { s_w[((w) + 0) * KD_LD + lane] = (v).x; s_w[((w) + 1) * KD_LD + lane] = (v).y; s_w[((w) + 2) * KD_LD + lane] = (v).z; }
 
-// Words [w0, w0 + n) of the workgroup's 64 staged rows -> dst[(row0 + r) * n + c], all five waves along the contiguous output
-// index; a row leaves only if s_valid[r].  QUAD: 16 bytes per lane (n a multiple of 4, dst 16-byte aligned), else one word.
-template <bool QUAD>
-DI void kd_flush(const float* s_w, const int* s_valid, int w0, int n, float* dst) {
+// Words [w0, w0 + n) of the workgroup's 64 staged rows -> dst[(row0 + r) * rowlen + col0 + c], all five waves along the contiguous
+// output index; a row leaves only if s_valid[r].  QUAD: 16 bytes per lane (n a multiple of 4, dst 16-byte aligned), else one word.
+// PER > 0: the index runs over PER >= n words per row, a compile-time constant, and the words past n are skipped.
+template <bool QUAD, int PER = 0>
+DI void kd_flush(const float* s_w, const int* s_valid, int w0, int n, float* dst, size_t rowlen, size_t col0) {
   const size_t row0 = (size_t)blockIdx.x * 64;
-  const int per_row = QUAD ? n / 4 : n;
+  const int per_row = PER ? PER : QUAD ? n / 4 : n;
   for (int idx = threadIdx.x; idx < 64 * per_row; idx += KD_THREADS) {
     const int r = idx / per_row, c = idx - r * per_row;
-    if (!s_valid[r]) continue;
+    if ((PER && c >= n) || !s_valid[r]) continue;
     if (QUAD) {
       const float* const w = s_w + (w0 + 4 * c) * KD_LD + r;
-      st4_global(dst + (row0 + r) * n + 4 * (size_t)c, w[0], w[KD_LD], w[2 * KD_LD], w[3 * KD_LD]);
+      st4_global(dst + (row0 + r) * rowlen + col0 + 4 * (size_t)c, w[0], w[KD_LD], w[2 * KD_LD], w[3 * KD_LD]);
     } else {
-      GPTR(dst)[(row0 + r) * n + c] = s_w[(w0 + c) * KD_LD + r];
+      GPTR(dst)[(row0 + r) * rowlen + col0 + c] = s_w[(w0 + c) * KD_LD + r];
     }
   }
 }
+
+// rows of n words that leave whole
+template <bool QUAD>
+DI void kd_flush(const float* s_w, const int* s_valid, int w0, int n, float* dst) { kd_flush<QUAD>(s_w, s_valid, w0, n, dst, n, 0); }

@@ -8,10 +8,11 @@
 // eliminate the fingers, Cholesky of the 6 x 6 Schur complement on wave 0, back-substitute.  NOT the articulated-body recursion:
 // projecting a 6 x 6 articulated inertia five times through the massless base joints cancels in fp32.
 //
-//   setup   every wave repeats the base chain and walks finger f.  FD: the Newton-Euler pass of k_kin_invdyn at qdd = 0 gives the
-//           bias force (kd_link_wrench's arithmetic on the rotated centre and inertia the composites share; the finger's joints
-//           stay in registers, its wrench about o5 goes to LDS for the palm pass).
-//           Both: the composite-body words F_f, C_f as k_kin_mass forms them, F_f (+ A) inverted (spd_inverse<4>), G_f = F_f^-1 C_f^T.
+//   setup   every wave repeats the base chain and walks finger f.  FD: the Newton-Euler pass of k_kin_invdyn at
+//           qdd = 0 gives the bias force (kd_joint_motion, kd_link_wrench on the rotated centre and inertia the composites share,
+//           kd_finger_backward: the finger's joints stay in registers, its wrench about o5 goes to LDS for kd_palm_project).
+//           Both: the composite-body words F_f, C_f (k_kin_mass's loop, spelled out again: see there), F_f (+ A) inverted
+//           (spd_inverse<4>), G_f = F_f^-1 C_f^T.
 //           B is a sum over bodies, so the finger's own composite gives its part B_f of B on its own wave, and what goes to LDS is
 //           the finger's 21 words of the Schur complement, B_f - C_f F_f^-1 C_f^T: wave 0 is left with the palm link alone.
 //   factor  wave 0, after the first barrier: S = B_palm (+ A) + the five finger parts, fd_chol6 -- once per row
@@ -24,14 +25,16 @@
 // arithmetic does not depend on the batch it sits in.  In place (out == rhs) is safe: a batch is read before it is written and
 // no other batch or workgroup touches its words.
 //
+// From dexsim_chain.hip.inc: the row rule (kd_load_q, kd_load_qd), kd_base_walk, kd_finger_joint, KD_TRI, kd_flush (whole
+// rows for FD, a batch of columns inside rows of nrhs x 26 words for the mass solve).  From dexsim_invdyn.hip.inc: the Newton-Euler
+// set.  From dexsim_kindyn.hip.inc: kd_base_block.
+//
 // Plain __syncthreads() only: no atomics, no spins.  A row >= k or with an id outside [0, num_envs) never writes caller memory.
 
 #ifndef FD_COLS
 #define FD_COLS 4        /* right-hand sides per barrier round of the mass solve (1 .. 4; profiles/forward_dynamics/README.md) */
 #endif
 static_assert(FD_COLS >= 1 && FD_COLS <= 4, "FD_COLS: the batch has to fit the 64 KiB of static LDS");
-
-#define FD_TRI(i, j) ((i) * ((i) + 1) / 2 + (j))   /* packed lower triangle */
 
 // LDS words.  SCH is dead once wave 0 has its factor, so the mass solve (one barrier more per launch) puts CFR over it.
 template <bool FD>
@@ -58,29 +61,11 @@ struct FwdDyn {
   int armature;        // DEXSIM_FD_ARMATURE
 };
 
-// The 21 words a rigid body (mass, centre relative to o5, inertia about the centre) adds to the base block: every base joint
-// carries it.  k_kin_mass's base pass, for one body instead of the whole hand.
-DI void fd_base_block(const KinBase& B, const Comp& H, float* out) {
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    const V3 Pm = H.m * (i < 3 ? B.a[i] : cross(B.a[i], H.c - B.orel[i]));
-    const V3 L = i < 3 ? v3(0, 0, 0) : mul(H.I, B.a[i]);
-#pragma unroll
-    for (int k = 0; k <= i; k++) out[FD_TRI(i, k)] = k < 3 ? dot(B.a[k], Pm) : dot(B.a[k], L + cross(H.c - B.orel[k], Pm));
-  }
-}
-
 // Where a value of the code both instances share is also read by the Newton-Euler pass of FD, it goes through opaque() in BOTH:
 // the compiler contracts a product into a following add only if the product has no other reader, so a second reader in one
 // instance would change the rounding of the shared arithmetic, and forward dynamics at qd = 0 would lose the bits of the mass solve.
 DI V3 fd_opaque(V3 v) { return {opaque(v.x), opaque(v.y), opaque(v.z)}; }
 DI S6 fd_opaque(S6 s) { return {opaque(s.xx), opaque(s.yy), opaque(s.zz), opaque(s.xy), opaque(s.xz), opaque(s.yz)}; }
-
-// kd_link_wrench for a link whose rotated centre rc and inertia I are at hand (the composites need the same two)
-DI void fd_link_wrench(float mass, V3 rc, const S6& I, const KdMotion& m, V3& f, V3& n) {
-  f = mass * kd_point_accel(m, rc);
-  n = mul(I, m.al) + cross(m.w, mul(I, m.w)) + cross(rc, f);
-}
 
 // Cholesky factor of a packed SPD 6 x 6 (spd_solve<6>'s arithmetic, the factor kept): L below the diagonal, rd = 1 / L_ii
 DI void fd_chol6(const float* S, float* L, float* rd) {
@@ -88,11 +73,11 @@ DI void fd_chol6(const float* S, float* L, float* rd) {
   for (int i = 0; i < 6; i++)
 #pragma unroll
     for (int j = 0; j <= i; j++) {
-      float s = S[FD_TRI(i, j)];
+      float s = S[KD_TRI(i, j)];
 #pragma unroll
-      for (int k = 0; k < j; k++) s -= L[FD_TRI(i, k)] * L[FD_TRI(j, k)];
-      if (i == j) { const float d = sqrtf(fmaxf(s, 1e-20f)); L[FD_TRI(i, i)] = d; rd[i] = 1.f / d; }
-      else L[FD_TRI(i, j)] = s * rd[j];
+      for (int k = 0; k < j; k++) s -= L[KD_TRI(i, k)] * L[KD_TRI(j, k)];
+      if (i == j) { const float d = sqrtf(fmaxf(s, 1e-20f)); L[KD_TRI(i, i)] = d; rd[i] = 1.f / d; }
+      else L[KD_TRI(i, j)] = s * rd[j];
     }
 }
 
@@ -102,14 +87,14 @@ DI void fd_chol6_solve(const float* L, const float* rd, const float* b, float* x
   for (int i = 0; i < 6; i++) {
     float s = b[i];
 #pragma unroll
-    for (int k = 0; k < i; k++) s -= L[FD_TRI(i, k)] * y[k];
+    for (int k = 0; k < i; k++) s -= L[KD_TRI(i, k)] * y[k];
     y[i] = s * rd[i];
   }
 #pragma unroll
   for (int i = 5; i >= 0; i--) {
     float s = y[i];
 #pragma unroll
-    for (int k = i + 1; k < 6; k++) s -= L[FD_TRI(k, i)] * x[k];
+    for (int k = i + 1; k < 6; k++) s -= L[KD_TRI(k, i)] * x[k];
     x[i] = s * rd[i];
   }
 }
@@ -136,18 +121,6 @@ DI void fd_cols_stage(float* s_w, int w0, const float* tin) {
   for (int i = 0; i < TIN; i++) {
     const int idx = threadIdx.x + i * KD_THREADS, r = idx / CW, c = idx - r * CW;
     if (idx < 64 * CW) s_w[(w0 + c) * KD_LD + r] = tin[i];
-  }
-}
-
-// the way back: kd_flush<false> for a batch of columns inside rows of nrhs x 26 words
-template <int CW>
-DI void fd_cols_flush(const float* s_w, const int* s_valid, int w0, const FwdDyn& K, int c0) {
-  const int n = min(CW, (K.nrhs - c0) * DEXSIM_NJ);
-  const size_t rowlen = (size_t)K.nrhs * DEXSIM_NJ, row0 = (size_t)blockIdx.x * 64;
-  for (int idx = threadIdx.x; idx < 64 * CW; idx += KD_THREADS) {
-    const int r = idx / CW, c = idx - r * CW;
-    if (c >= n || !s_valid[r]) continue;
-    GPTR(K.out)[(row0 + r) * rowlen + (size_t)c0 * DEXSIM_NJ + c] = s_w[(w0 + c) * KD_LD + r];
   }
 }
 
@@ -192,7 +165,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_fwddyn(const DevParams* __re
 #pragma unroll
     for (int l = 0; l < DEXSIM_NFJ; l++) {
       const JC& c = P->jc[6 + 4 * f + l];
-      kd_finger_joint(c, qf[l], of, qc, a[l]);
+      kd_finger_joint(c, qf[l], of, qc, a[l]);   // kd_finger_link spelled out: through it the mass solve was 2 to 7 % slower
       o[l] = of;
       const M3 Rj = q2mat(qc);
       const V3 rc = fd_opaque(mul(Rj, v3p(c.com)));
@@ -201,23 +174,11 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_fwddyn(const DevParams* __re
       if (FD) {
         m = kd_joint_motion(m, of - op, a[l], vf[l], 0.f, false);
         op = of;
-        fd_link_wrench(c.mass, rc, I, m, fl[l], nl[l]);
+        kd_link_wrench(c.mass, rc, I, m, fl[l], nl[l]);
         __builtin_amdgcn_sched_barrier(0);   // link by link: interleaved for ILP, four links' inertias and wrenches do not fit the registers
       }
     }
-    if (FD) {   // backward pass over the finger, as k_kin_invdyn: F, Nm = the wrench of links l .. 3 about o[l]
-      V3 F = fl[3], Nm = nl[3];
-      cf[3] = dot(a[3], Nm);
-#pragma unroll
-      for (int l = DEXSIM_NFJ - 2; l >= 0; l--) {
-        Nm = nl[l] + Nm + cross(o[l + 1] - o[l], F);
-        F = fl[l] + F;
-        cf[l] = dot(a[l], Nm);
-      }
-      Nm = Nm + cross(o[0], F);   // about o5
-      KD_PUT3(Map::WR + 6 * f, F);
-      KD_PUT3(Map::WR + 6 * f + 3, Nm);
-    }
+    if (FD) kd_finger_backward(a, o, fl, nl, cf, 1, s_w, Map::WR + 6 * f, lane);
   }
   // the scheduler interleaves for ILP and would start the composites inside the walk: the two together do not fit the registers
   __builtin_amdgcn_sched_barrier(0);
@@ -250,7 +211,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_fwddyn(const DevParams* __re
     }
   {
     float Bf[21];
-    fd_base_block(B, comp[0], Bf);
+    kd_base_block(B, comp[0], Bf);
 #pragma unroll
     for (int i = 0; i < 6; i++)
 #pragma unroll
@@ -258,7 +219,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_fwddyn(const DevParams* __re
         float s = 0.f;
 #pragma unroll
         for (int l = 0; l < DEXSIM_NFJ; l++) s += Cm[6 * l + i] * G[6 * l + k];
-        s_w[(Map::SCH + 21 * f + FD_TRI(i, k)) * KD_LD + lane] = Bf[FD_TRI(i, k)] - s;
+        s_w[(Map::SCH + 21 * f + KD_TRI(i, k)) * KD_LD + lane] = Bf[KD_TRI(i, k)] - s;
       }
   }
   if (FD) fd_cols_stage<CW, TIN>(s_w, Map::STAGE, tin);
@@ -273,14 +234,14 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_fwddyn(const DevParams* __re
     Comp H;
     H.m = c5.mass; H.c = fd_opaque(mul(R5, v3p(c5.com))); H.I = fd_opaque(rotate_inertia(R5, c5.inertia));
     float S[21];
-    fd_base_block(B, H, S);
+    kd_base_block(B, H, S);
 #pragma unroll
     for (int ff = 0; ff < DEXSIM_NFINGER; ff++)
 #pragma unroll
       for (int i = 0; i < 21; i++) S[i] += s_w[(Map::SCH + 21 * ff + i) * KD_LD + lane];
     if (K.armature) {
 #pragma unroll
-      for (int i = 0; i < 6; i++) S[FD_TRI(i, i)] += P->jc[i].armature;
+      for (int i = 0; i < 6; i++) S[KD_TRI(i, i)] += P->jc[i].armature;
     }
     fd_chol6(S, L6, rd);
     if (FD) {
@@ -288,15 +249,8 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_fwddyn(const DevParams* __re
       const float* const w5 = s_w + Map::M5 * KD_LD + lane;
       const KdMotion m5 = {v3(w5[0], w5[KD_LD], w5[2 * KD_LD]), v3(w5[3 * KD_LD], w5[4 * KD_LD], w5[5 * KD_LD]),
                            v3(w5[6 * KD_LD], w5[7 * KD_LD], w5[8 * KD_LD])};
-      fd_link_wrench(c5.mass, H.c, H.I, m5, F, Nm);
-#pragma unroll
-      for (int ff = 0; ff < DEXSIM_NFINGER; ff++) {
-        const float* const w = s_w + (Map::WR + 6 * ff) * KD_LD + lane;
-        F += v3(w[0], w[KD_LD], w[2 * KD_LD]);
-        Nm += v3(w[3 * KD_LD], w[4 * KD_LD], w[5 * KD_LD]);
-      }
-#pragma unroll
-      for (int j = 0; j < 6; j++) cB[j] = j < 3 ? dot(B.a[j], F) : dot(B.a[j], Nm - cross(B.orel[j], F));
+      kd_link_wrench(c5.mass, H.c, H.I, m5, F, Nm);
+      kd_palm_project(B, F, Nm, s_w, Map::WR, lane, cB, 1);
     }
   }
   if (!FD) {
@@ -365,7 +319,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_fwddyn(const DevParams* __re
     }
     __syncthreads();
     if (FD) { kd_flush<false>(s_w, s_valid, Map::STAGE, DEXSIM_NJ, K.out); break; }
-    fd_cols_flush<CW>(s_w, s_valid, Map::STAGE, K, c0);
+    kd_flush<false, CW>(s_w, s_valid, Map::STAGE, min(CW, (K.nrhs - c0) * DEXSIM_NJ), K.out, (size_t)K.nrhs * DEXSIM_NJ, (size_t)c0 * DEXSIM_NJ);
     c0 += CB;
     if (c0 >= K.nrhs) break;
     fd_cols_load<CW, TIN>(K, c0, tin);   // (issued at the head of the batch before, these loads made the call slower: README of the profile)

@@ -16,6 +16,11 @@
 //   k_kin_bias_accel  the forward pass alone at qdd = 0 and without gravity, then a_b = ao + al x r + w x (w x r) and al for the
 //                     requested bodies welded to each joint frame (kd_body_joint; the host sorts the request by frame): 6 words per body
 //
+// From dexsim_chain.hip.inc: the row rule (kd_load_q, kd_load_qd, kd_load_words for qdd), kd_base_walk, the link walk kd_finger_link
+// (k_kin_bias_accel needs no centre or inertia and walks kd_finger_joint), kd_flush.  The Newton-Euler set defined here --
+// kd_joint_motion, kd_link_wrench, kd_finger_backward, kd_palm_project -- is also k_kin_fwddyn<true>'s (dexsim_fwddyn.hip.inc);
+// k_kin_invdyn spells the last two out (see there).
+//
 // Plain __syncthreads() only: no atomics, no spins.  A row >= k or with an id outside [0, num_envs) never writes caller memory.
 // Numerics: only differences of o5-relative origins enter (levers of hand size); the spawn position never does -- joint 0 hangs
 // on a frame that neither turns nor accelerates, so its lever drops out.
@@ -76,12 +81,41 @@ DI void kd_base_motion(const KinBase& B, const float* vb, const float* ab, V3 a0
   }
 }
 
-// the wrench link c needs, about its frame's origin: f = m a_c, n = I al + w x (I w) + rc x f
-DI void kd_link_wrench(const JC& c, const M3& R, const KdMotion& m, V3& f, V3& n) {
-  const V3 rc = mul(R, v3p(c.com));
-  const S6 I = rotate_inertia(R, c.inertia);
-  f = c.mass * kd_point_accel(m, rc);
+// the wrench a link (mass, centre rc from its frame's origin, inertia I in world axes) needs, about that origin: f = m a_c,
+// n = I al + w x (I w) + rc x f
+DI void kd_link_wrench(float mass, V3 rc, const S6& I, const KdMotion& m, V3& f, V3& n) {
+  f = mass * kd_point_accel(m, rc);
   n = mul(I, m.al) + cross(m.w, mul(I, m.w)) + cross(rc, f);
+}
+
+// Backward pass over a finger: with F, Nm = the wrench of links l .. 3 about o[l], joint l's torque -> t[l * ts] (registers, ts = 1,
+// or the lane's LDS column, ts = KD_LD); the finger's wrench about o5 -> LDS words [WR, WR + 6): force, moment.
+DI void kd_finger_backward(const V3* a, const V3* o, const V3* fl, const V3* nl, float* t, int ts, float* s_w, int WR, int lane) {
+  V3 F = fl[3], Nm = nl[3];
+  t[3 * ts] = dot(a[3], Nm);
+#pragma unroll
+  for (int l = DEXSIM_NFJ - 2; l >= 0; l--) {
+    Nm = nl[l] + Nm + cross(o[l + 1] - o[l], F);
+    F = fl[l] + F;
+    t[l * ts] = dot(a[l], Nm);
+  }
+  Nm = Nm + cross(o[0], F);   // about o5
+  KD_PUT3(WR, F);
+  KD_PUT3(WR + 3, Nm);
+}
+
+// Palm pass: F, Nm = the palm link's wrench about o5; the five finger wrenches at LDS words [WR, WR + 30) are added and the sum is
+// projected on the six base joints -> t[j * ts].  Links 0-4 are massless (validate_model): every base joint carries the whole hand.
+DI void kd_palm_project(const KinBase& B, V3 F, V3 Nm, const float* s_w, int WR, int lane, float* t, int ts) {
+#pragma unroll
+  for (int ff = 0; ff < DEXSIM_NFINGER; ff++) {
+    const float* const w = s_w + (WR + 6 * ff) * KD_LD + lane;
+    F += v3(w[0], w[KD_LD], w[2 * KD_LD]);
+    Nm += v3(w[3 * KD_LD], w[4 * KD_LD], w[5 * KD_LD]);
+  }
+#pragma unroll
+  for (int j = 0; j < 6; j++)   // the moment about o_j: o5 - o_j = -orel[j]
+    t[j * ts] = j < 3 ? dot(B.a[j], F) : dot(B.a[j], Nm - cross(B.orel[j], F));
 }
 
 // -------------------------------------------------------------------------------------------------- inverse dynamics
@@ -98,14 +132,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_invdyn(const DevParams* __re
   for (int j = 0; j < 6; j++) ab[j] = 0.f;
 #pragma unroll
   for (int j = 0; j < 4; j++) af[j] = 0.f;
-  if (K.qdd) {
-    const int l = blockIdx.x * 64 + lane;
-    const size_t row = (size_t)min(l, K.rows.k - 1) * DEXSIM_NJ;
-#pragma unroll
-    for (int j = 0; j < 6; j++) ab[j] = GPTR(K.qdd)[row + j];
-#pragma unroll
-    for (int j = 0; j < 4; j++) af[j] = GPTR(K.qdd)[row + 6 + 4 * f + j];
-  }
+  if (K.qdd) kd_load_words(K.qdd, (size_t)kd_row(K.rows) * DEXSIM_NJ, 1, f, ab, af);
   KinBase B;
   kd_base_walk(P, qb, B);
   if (f == 0) s_valid[lane] = valid;
@@ -122,15 +149,16 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_invdyn(const DevParams* __re
 #pragma unroll
     for (int l = 0; l < DEXSIM_NFJ; l++) {
       const JC& c = P->jc[6 + 4 * f + l];
-      kd_finger_joint(c, qf[l], of, qc, a[l]);
+      V3 rc;
+      S6 I;
+      kd_finger_link(c, qf[l], of, qc, a[l], rc, I);
       o[l] = of;
       m = kd_joint_motion(m, of - op, a[l], vf[l], af[l], false);
       op = of;
-      kd_link_wrench(c, q2mat(qc), m, fl[l], nl[l]);
+      kd_link_wrench(c.mass, rc, I, m, fl[l], nl[l]);
     }
   }
-
-  // ---- backward pass over the finger: F, Nm = the wrench of links l .. 3 about o[l]
+  // ---- backward and palm pass, spelled out: through kd_finger_backward and kd_palm_project tau on 65536 override rows was 4 % slower
   {
     V3 F = fl[3], Nm = nl[3];
     s_w[(ID_TAU + 6 + 4 * f + 3) * KD_LD + lane] = dot(a[3], Nm);
@@ -148,7 +176,9 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_invdyn(const DevParams* __re
 
   if (f == 0) {   // ---- palm pass: the palm link and the five fingers, projected on the six base joints
     V3 F, Nm;
-    kd_link_wrench(P->jc[5], q2mat(B.q[5]), mb[5], F, Nm);
+    const JC& c5 = P->jc[5];
+    const M3 R5 = q2mat(B.q[5]);
+    kd_link_wrench(c5.mass, mul(R5, v3p(c5.com)), rotate_inertia(R5, c5.inertia), mb[5], F, Nm);
 #pragma unroll
     for (int ff = 0; ff < DEXSIM_NFINGER; ff++) {
       const float* const w = s_w + (ID_WR + 6 * ff) * KD_LD + lane;

@@ -12,6 +12,9 @@
 //   phase B  all 5 waves along the CONTIGUOUS output index: expand to the dense layout -- cross product a_c x (p_b - o_c) or
 //            a_c, ancestor mask, symmetric mirror, exact zeros -- and store 16 bytes per lane, fully coalesced.
 //
+// From dexsim_chain.hip.inc: the row rule (kd_load_q), kd_base_walk, kd_finger_joint (Jacobians) and the link walk kd_finger_link
+// (mass matrix), KD_TRI, kd_flush.  kd_base_block, defined here, is also k_kin_fwddyn's (dexsim_fwddyn.hip.inc).
+//
 // Plain __syncthreads() only: no atomics, no spins.  A row >= k or with an id outside [0, num_envs) never writes caller memory.
 //
 // Numerics: with positions relative to o5 (the finger walk starts at 0, the base origins are suffix sums of the walk's own
@@ -130,14 +133,29 @@ DI float kd_mass_entry(const float* s_w, int r, int i, int j) {
   const int hi = max(i, j), lo = min(i, j);
   int w;
   bool zero = false;
-  if (hi < 6) w = KM_BASE + hi * (hi + 1) / 2 + lo;
+  if (hi < 6) w = KM_BASE + KD_TRI(hi, lo);
   else {
     const int f = (hi - 6) >> 2, l = (hi - 6) & 3;
     if (lo < 6) w = KM_FINGER(f) + 10 + 6 * l + lo;
-    else { const int l2 = (lo - 6) & 3; zero = ((lo - 6) >> 2) != f; w = KM_FINGER(f) + l * (l + 1) / 2 + l2; }
+    else { const int l2 = (lo - 6) & 3; zero = ((lo - 6) >> 2) != f; w = KM_FINGER(f) + KD_TRI(l, l2); }
   }
   const float v = s_w[w * KD_LD + r];
   return zero ? 0.f : v;
+}
+
+// The composite-body words (CRBA).  For the subtree of joint i with composite H (mass, centre relative to o5, inertia about the
+// centre) and axis a_i: Pm = m dc/dq_i is its momentum for unit velocity, L = I a_i its angular momentum about the centre, and
+// M[i][k], k an ancestor of i (or i), is a_k . Pm (k prismatic) or a_k . (L + (c - o_k) x Pm) (k revolute); dV/dq_i = -g . Pm.
+
+// the 21 words a rigid body H adds to the base block: every base joint carries it -> out[KD_TRI(i, k)]
+DI void kd_base_block(const KinBase& B, const Comp& H, float* out) {
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const V3 Pm = H.m * (i < 3 ? B.a[i] : cross(B.a[i], H.c - B.orel[i]));
+    const V3 L = i < 3 ? v3(0, 0, 0) : mul(H.I, B.a[i]);
+#pragma unroll
+    for (int k = 0; k <= i; k++) out[KD_TRI(i, k)] = k < 3 ? dot(B.a[k], Pm) : dot(B.a[k], L + cross(H.c - B.orel[k], Pm));
+  }
 }
 
 __global__ __launch_bounds__(KD_THREADS) void k_kin_mass(const DevParams* __restrict__ P, KinMass K, int N, int NR) {
@@ -146,8 +164,6 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_mass(const DevParams* __rest
   const int lane = threadIdx.x & 63, f = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const Arena& A = P->arena;
   const V3 g = v3p(P->cfg.gravity);
-  // generalized force of joint i for unit velocity momentum Pm = m dc/dq_i of its subtree: dV/dq_i = -g . Pm
-  // M[i][k], k an ancestor of i (or i): a_k . Pm (k prismatic), a_k . (L + (c - o_k) x Pm) (k revolute), L = I_c a_i about c
 
   {   // ---- phase A, finger pass: every wave its finger
     float qb[6], qf[4];
@@ -163,21 +179,21 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_mass(const DevParams* __rest
 #pragma unroll
       for (int l = 0; l < DEXSIM_NFJ; l++) {
         const JC& c = P->jc[6 + 4 * f + l];
-        kd_finger_joint(c, qf[l], of, qc, a[l]);
+        V3 rc;
+        kd_finger_link(c, qf[l], of, qc, a[l], rc, comp[l].I);
         o[l] = of;
-        const M3 Rj = q2mat(qc);
-        comp[l].m = c.mass; comp[l].c = of + mul(Rj, v3p(c.com)); comp[l].I = rotate_inertia(Rj, c.inertia);
+        comp[l].m = c.mass; comp[l].c = of + rc;
       }
     }
 #pragma unroll
     for (int l = DEXSIM_NFJ - 2; l >= 0; l--) comp_add(comp[l], comp[l + 1]);   // subtree of joint l = links l .. 3
     const int F = KM_FINGER(f);
 #pragma unroll
-    for (int i = 0; i < DEXSIM_NFJ; i++) {
+    for (int i = 0; i < DEXSIM_NFJ; i++) {   // spelled out here and in k_kin_fwddyn: through one kd_finger_blocks the mass solve rounded differently
       const V3 Pm = comp[i].m * cross(a[i], comp[i].c - o[i]);
       const V3 L = mul(comp[i].I, a[i]);
 #pragma unroll
-      for (int k = 0; k <= i; k++) s_w[(F + i * (i + 1) / 2 + k) * KD_LD + lane] = dot(a[k], L + cross(comp[i].c - o[k], Pm));
+      for (int k = 0; k <= i; k++) s_w[(F + KD_TRI(i, k)) * KD_LD + lane] = dot(a[k], L + cross(comp[i].c - o[k], Pm));
 #pragma unroll
       for (int k = 0; k < 6; k++)
         s_w[(F + 10 + 6 * i + k) * KD_LD + lane] = k < 3 ? dot(B.a[k], Pm) : dot(B.a[k], L + cross(comp[i].c - B.orel[k], Pm));
@@ -206,13 +222,13 @@ __global__ __launch_bounds__(KD_THREADS) void k_kin_mass(const DevParams* __rest
         c.I = S6{w[4 * KD_LD], w[5 * KD_LD], w[6 * KD_LD], w[7 * KD_LD], w[8 * KD_LD], w[9 * KD_LD]};
         comp_add(H, c);
       }
-      float out[21], grav[6];
+      float out[21], grav[6];   // spelled out: through kd_base_block, M[5][4] and M[5][5] rounded differently
 #pragma unroll
       for (int i = 0; i < 6; i++) {
         const V3 Pm = H.m * (i < 3 ? B.a[i] : cross(B.a[i], H.c - B.orel[i]));
         const V3 L = i < 3 ? v3(0, 0, 0) : mul(H.I, B.a[i]);
 #pragma unroll
-        for (int k = 0; k <= i; k++) out[i * (i + 1) / 2 + k] = k < 3 ? dot(B.a[k], Pm) : dot(B.a[k], L + cross(H.c - B.orel[k], Pm));
+        for (int k = 0; k <= i; k++) out[KD_TRI(i, k)] = k < 3 ? dot(B.a[k], Pm) : dot(B.a[k], L + cross(H.c - B.orel[k], Pm));
         grav[i] = -dot(g, Pm);
       }
 #pragma unroll

@@ -1,11 +1,37 @@
-"""What the tests of the query kernels share (test_render, test_kindyn, test_ik, test_proximity): the queries are pure functions of
-q that write caller-owned memory only, so every suite poses cores the same way, puts its outputs between guard rows and checks that
-nothing of the instance changed.  A plain module: no fixtures."""
+"""What the tests of the query kernels share (test_render, test_kindyn, test_ik, test_proximity, test_inverse_dynamics,
+test_forward_dynamics): the queries are pure functions of q (and qd) that write caller-owned memory only, so every suite loads the
+library, poses cores, stubs the core under DexHandEnv, puts its outputs between guard rows and checks that nothing of the instance
+changed in the same way.  A plain module: no fixtures."""
 import numpy as np
 
 from dexrobot_isaac_amd.config import build_sim_config, default_cfg
 
 GUARD = -7.0
+
+
+def load_lib():
+    from dexrobot_isaac_amd import _lib
+    from dexrobot_isaac_amd.build import build_lib
+    build_lib()
+    return _lib.load()
+
+
+def dev(a):
+    """None and tensors as they are, arrays as contiguous tensors on the GPU."""
+    import torch
+    if a is None or torch.is_tensor(a):
+        return a
+    return torch.as_tensor(np.ascontiguousarray(a), device="cuda:0")
+
+
+def stub_core(record, **methods):
+    """A core factory with just enough of a core for DexHandEnv's own argument checks: method `name` appends record[name](its
+    arguments) to `calls` and computes nothing; `methods` are defined as given.  Every core made has a class and a list of its own."""
+    def factory(sim_cfg, model_struct, device="cpu"):
+        from oracle.py_backend import OracleCore
+        rec = {name: (lambda self, *a, _what=what, **kw: self.calls.append(_what(*a, **kw))) for name, what in record.items()}
+        return type("Stub", (OracleCore,), dict(calls=[], **rec, **methods))(sim_cfg, model_struct, device)
+    return factory
 
 
 def setup(n, task="BlindGrasping"):

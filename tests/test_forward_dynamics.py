@@ -31,13 +31,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from dexrobot_isaac_amd import _abi, _lib
-from dexrobot_isaac_amd.build import build_lib
+from dexrobot_isaac_amd import _abi
 from oracle.oracle import Oracle
 from tests import fwddyn_ref as fr
 from tests import invdyn_ref as ir
 from tests import kindyn_ref as kr
-from tests.query_rig import bits, guarded as _guarded, guards_ok as _guards_ok, pose_core, same as _same, setup as _setup, snapshot as _snapshot
+from tests.query_rig import (bits, dev as _dev, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, same as _same, setup as _setup,
+                             snapshot as _snapshot, stub_core)
 
 N = 70
 NJ = _abi.NJ
@@ -47,8 +47,7 @@ CASES = ("full", "free", "nograv", "msolve")
 
 @pytest.fixture(scope="module")
 def lib():
-    build_lib()
-    return _lib.load()
+    return load_lib()
 
 
 # ------------------------------------------------------------------------------------------------- references
@@ -185,19 +184,10 @@ def test_missing_terms_are_discriminated():
         assert miss >= 100 * FACTOR * off[name]["e_qdd"]
 
 
-def _stub_core(sim_cfg, model_struct, device="cpu"):
-    """Just enough of a core for DexHandEnv's own argument checks: records the calls, computes nothing."""
-    from oracle.py_backend import OracleCore
-
-    class Stub(OracleCore):
-        calls = []
-
-        def forward_dynamics(self, out, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False):
-            self.calls.append(("fd", tuple(out.shape), tau is not None, q is not None, qd is not None, gravity, armature))
-
-        def mass_solve(self, out, rhs, env_ids=None, q=None, armature=False):
-            self.calls.append(("ms", tuple(out.shape), tuple(rhs.shape), q is not None, armature))
-    return Stub(sim_cfg, model_struct, device)
+_stub_core = stub_core(dict(
+    forward_dynamics=lambda out, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False:
+        ("fd", tuple(out.shape), tau is not None, q is not None, qd is not None, gravity, armature),
+    mass_solve=lambda out, rhs, env_ids=None, q=None, armature=False: ("ms", tuple(out.shape), tuple(rhs.shape), q is not None, armature)))
 
 
 def test_env_argument_validation():
@@ -261,13 +251,6 @@ def test_env_argument_validation():
 
 
 # ------------------------------------------------------------------------------------------------- GPU helpers
-def _dev(a):
-    import torch
-    if a is None or torch.is_tensor(a):
-        return a
-    return torch.as_tensor(np.ascontiguousarray(a), device="cuda:0")
-
-
 def gpu_fd(core, k, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False):
     full, out = _guarded(k, NJ)
     core.forward_dynamics(out, tau=_dev(tau), env_ids=env_ids, q=_dev(q), qd=_dev(qd), gravity=gravity, armature=armature)

@@ -24,10 +24,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from dexrobot_isaac_amd import _abi, _lib
-from dexrobot_isaac_amd.build import build_lib
+from dexrobot_isaac_amd import _abi
 from tests import ik_ref as ir
-from tests.query_rig import bits, guarded as _guarded, guards_ok as _guards_ok, pose_core, same as _same, setup as _setup, snapshot as _snapshot
+from tests.query_rig import (bits, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, same as _same, setup as _setup,
+                             snapshot as _snapshot, stub_core)
 
 N = 70
 NJ, NACT, NF = _abi.NJ, _abi.NACT, _abi.NFINGER
@@ -49,8 +49,7 @@ def _prm(**kw):
 # ------------------------------------------------------------------------------------------------- CPU
 @pytest.fixture(scope="module")
 def lib():
-    build_lib()
-    return _lib.load()
+    return load_lib()
 
 
 def test_abi_exports_and_argument_errors(lib):
@@ -90,16 +89,7 @@ def test_abi_exports_and_argument_errors(lib):
     assert _abi.IK_MAX_ITERS == 64
 
 
-def _stub_core(sim_cfg, model_struct, device="cpu"):
-    """Just enough of a core for DexHandEnv's own argument checks: records the calls, computes nothing."""
-    from oracle.py_backend import OracleCore
-
-    class Stub(OracleCore):
-        calls = []
-
-        def solve_ik(self, targets, controls, **kw):
-            self.calls.append((tuple(targets.shape), tuple(controls.shape), kw))
-    return Stub(sim_cfg, model_struct, device)
+_stub_core = stub_core(dict(solve_ik=lambda targets, controls, **kw: (tuple(targets.shape), tuple(controls.shape), kw)))
 
 
 def test_env_argument_validation():

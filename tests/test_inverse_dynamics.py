@@ -25,12 +25,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from dexrobot_isaac_amd import _abi, _lib
-from dexrobot_isaac_amd.build import build_lib
+from dexrobot_isaac_amd import _abi
 from oracle.oracle import Oracle
 from tests import invdyn_ref as ir
 from tests import kindyn_ref as kr
-from tests.query_rig import bits, guarded as _guarded, guards_ok as _guards_ok, pose_core, same as _same, setup as _setup, snapshot as _snapshot
+from tests.query_rig import (bits, dev as _dev, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, same as _same, setup as _setup,
+                             snapshot as _snapshot, stub_core)
 
 N = 70
 NB, NJ = _abi.NUM_HAND_BODIES, _abi.NJ
@@ -40,8 +40,7 @@ FACTOR = 4
 # ------------------------------------------------------------------------------------------------- CPU
 @pytest.fixture(scope="module")
 def lib():
-    build_lib()
-    return _lib.load()
+    return load_lib()
 
 
 def test_abi_exports_and_null_handle(lib):
@@ -129,22 +128,11 @@ def test_velocity_terms_are_discriminated():
     assert miss >= 100 * FACTOR * r["e_bias"]
 
 
-def _stub_core(sim_cfg, model_struct, device="cpu"):
-    """Just enough of a core for DexHandEnv's own argument checks: records the calls, computes nothing."""
-    from oracle.py_backend import OracleCore
-
-    class Stub(OracleCore):
-        calls = []
-
-        def inverse_dynamics(self, tau, qdd=None, env_ids=None, q=None, qd=None, gravity=True):
-            self.calls.append(("tau", tuple(tau.shape), qdd is not None, q is not None, qd is not None, gravity))
-
-        def body_bias_accel(self, out, env_ids=None, q=None, qd=None, bodies=None):
-            self.calls.append(("acc", tuple(out.shape), bodies))
-
-        def body_jacobian(self, out, env_ids=None, q=None, bodies=None):
-            self.calls.append(("jac", tuple(out.shape), bodies))
-    return Stub(sim_cfg, model_struct, device)
+_stub_core = stub_core(dict(
+    inverse_dynamics=lambda tau, qdd=None, env_ids=None, q=None, qd=None, gravity=True:
+        ("tau", tuple(tau.shape), qdd is not None, q is not None, qd is not None, gravity),
+    body_bias_accel=lambda out, env_ids=None, q=None, qd=None, bodies=None: ("acc", tuple(out.shape), bodies),
+    body_jacobian=lambda out, env_ids=None, q=None, bodies=None: ("jac", tuple(out.shape), bodies)))
 
 
 def test_env_argument_validation():
@@ -188,13 +176,6 @@ def test_env_argument_validation():
 
 
 # ------------------------------------------------------------------------------------------------- GPU helpers
-def _dev(a):
-    import torch
-    if a is None or torch.is_tensor(a):
-        return a
-    return torch.as_tensor(np.ascontiguousarray(a), device="cuda:0")
-
-
 def gpu_tau(core, k, qdd=None, env_ids=None, q=None, qd=None, gravity=True):
     full, out = _guarded(k, NJ)
     core.inverse_dynamics(out, qdd=_dev(qdd), env_ids=env_ids, q=_dev(q), qd=_dev(qd), gravity=gravity)

@@ -16,10 +16,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from dexrobot_isaac_amd import _abi, _lib
-from dexrobot_isaac_amd.build import build_lib
+from dexrobot_isaac_amd import _abi
 from tests import kindyn_ref as kr
-from tests.query_rig import bits, guarded as _guarded, guards_ok as _guards_ok, pose_core, same as _same, setup as _setup, snapshot as _snapshot
+from tests.query_rig import (bits, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, same as _same, setup as _setup,
+                             snapshot as _snapshot, stub_core)
 
 N = 70
 NB, NJ = _abi.NUM_HAND_BODIES, _abi.NJ
@@ -28,8 +28,7 @@ NB, NJ = _abi.NUM_HAND_BODIES, _abi.NJ
 # ------------------------------------------------------------------------------------------------- CPU
 @pytest.fixture(scope="module")
 def lib():
-    build_lib()
-    return _lib.load()
+    return load_lib()
 
 
 def test_abi_exports_and_null_handle(lib):
@@ -81,19 +80,10 @@ def test_reference_roundoff():
     assert abs(g64[:, 2] - 5.17).max() < 0.01                                  # the z slide carries the hand's weight
 
 
-def _stub_core(sim_cfg, model_struct, device="cpu"):
-    """Just enough of a core for DexHandEnv's own argument checks: records the calls, computes nothing."""
-    from oracle.py_backend import OracleCore
-
-    class Stub(OracleCore):
-        calls = []
-
-        def body_jacobian(self, out, env_ids=None, q=None, bodies=None):
-            self.calls.append(("jac", tuple(out.shape), bodies))
-
-        def mass_matrix(self, mass=None, gravity=None, env_ids=None, q=None):
-            self.calls.append(("mass", None if mass is None else tuple(mass.shape), None if gravity is None else tuple(gravity.shape)))
-    return Stub(sim_cfg, model_struct, device)
+_stub_core = stub_core(dict(
+    body_jacobian=lambda out, env_ids=None, q=None, bodies=None: ("jac", tuple(out.shape), bodies),
+    mass_matrix=lambda mass=None, gravity=None, env_ids=None, q=None:
+        ("mass", None if mass is None else tuple(mass.shape), None if gravity is None else tuple(gravity.shape))))
 
 
 def test_env_argument_validation():

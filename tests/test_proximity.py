@@ -28,10 +28,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from dexrobot_isaac_amd import _abi, _lib
-from dexrobot_isaac_amd.build import build_lib
+from dexrobot_isaac_amd import _abi
 from tests import proximity_ref as pr
-from tests.query_rig import bits, guarded as _guarded, guards_ok as _guards_ok, pose_core, same as _same, setup as _setup, snapshot as _snapshot
+from tests.query_rig import (bits, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, same as _same, setup as _setup,
+                             snapshot as _snapshot, stub_core)
 
 N = 70
 NJ, NCAP, NG, NP = _abi.NJ, _abi.NCAP, _abi.NPROX_GROUPS, _abi.NPROX_PAIRS
@@ -43,8 +43,7 @@ ALL = ("cap_env", "self_min", "pair_dist")
 # ------------------------------------------------------------------------------------------------- CPU
 @pytest.fixture(scope="module")
 def lib():
-    build_lib()
-    return _lib.load()
+    return load_lib()
 
 
 def test_abi_exports_pair_table_and_argument_errors(lib):
@@ -166,19 +165,7 @@ def test_reference_against_brute_force():
         assert (ln[sl] <= brute + 1e-15).all() and (ln[sl] >= brute - lip - 1e-15).all()
 
 
-def _stub_core(sim_cfg, model_struct, device="cpu"):
-    """Just enough of a core for DexHandEnv's own argument checks: records the calls, computes nothing."""
-    from oracle.py_backend import OracleCore
-
-    class Stub(OracleCore):
-        calls = []
-
-        def proximity_pairs(self):
-            return pr.pair_table()
-
-        def proximity(self, **kw):
-            self.calls.append(kw)
-    return Stub(sim_cfg, model_struct, device)
+_stub_core = stub_core(dict(proximity=lambda **kw: kw), proximity_pairs=lambda self: pr.pair_table())
 
 
 def test_env_argument_validation():
