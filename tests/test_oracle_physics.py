@@ -58,10 +58,25 @@ def _numeric_mass_and_gravity(model, q, eps=1e-6):
     return M, g
 
 
+def _derivation_poses():
+    """The original pose, and rows of tests/wide_states.py: the whole joint range at speed, base rotations and the first thumb joint
+    outside quadrant 0 of the half-angle -- where tests/test_wide_poses.py uses M and b."""
+    from tests import wide_states
+    rng = np.random.default_rng(0)
+    poses = [(rng.uniform(-0.3, 0.6, 26), rng.uniform(-1, 1, 26))]
+    st = wide_states.sample("free")
+    thumb_far = int(np.argmax(st["q"][6]))
+    assert st["q"][6, thumb_far] > np.pi / 2 and (np.abs(st["q"][3:6, :4]) > np.pi / 2).any()
+    return poses + [(st["q"][:, e].copy(), st["qd"][:, e].copy()) for e in (0, 1, 2, 3, thumb_far)]
+
+
 def test_mass_matrix_gravity_coriolis_match_numerical_derivation():
     o, model, _ = _mk(f64=True)
-    rng = np.random.default_rng(0)
-    q, qd = rng.uniform(-0.3, 0.6, 26), rng.uniform(-1, 1, 26)
+    for q, qd in _derivation_poses():
+        _check_derivation(o, model, q, qd)
+
+
+def _check_derivation(o, model, q, qd):
     M, b0 = o.mass_matrix(q, np.zeros(26))
     Mn, gn = _numeric_mass_and_gravity(model, q)
     assert np.abs(M - Mn).max() < 1e-7 and np.abs(M - M.T).max() == 0 and np.linalg.eigvalsh(M).min() > 0
