@@ -152,6 +152,7 @@ EXPORTED_SYMBOLS = [
     "dexsim_proximity_pair", "dexsim_query_proximity",
     "dexsim_inverse_dynamics", "dexsim_body_bias_accel",
     "dexsim_forward_dynamics", "dexsim_mass_solve",
+    "dexsim_inverse_dynamics_derivatives", "dexsim_forward_dynamics_derivatives",
 ]
 
 
@@ -205,6 +206,8 @@ def declare_prototypes(lib):
     lib.dexsim_body_bias_accel.argtypes = [vp, vp, i32, vp, vp, P(i32), i32, vp, vp]
     lib.dexsim_forward_dynamics.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
     lib.dexsim_mass_solve.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
+    lib.dexsim_inverse_dynamics_derivatives.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
+    lib.dexsim_forward_dynamics_derivatives.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         getattr(lib, name).restype = i32
     lib.dexsim_error_string.argtypes = [i32]

@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdexsim.so")
 SOURCES = ["dexsim.hip", "dexsim_device.h", "dexsim_physics.hip.inc", "dexsim_l2.hip.inc", "dexsim_state.hip.inc",
            "dexsim_chain.hip.inc", "dexsim_render.hip.inc", "dexsim_kindyn.hip.inc", "dexsim_ik.hip.inc", "dexsim_proximity.hip.inc",
-           "dexsim_invdyn.hip.inc", "dexsim_fwddyn.hip.inc"]
+           "dexsim_invdyn.hip.inc", "dexsim_fwddyn.hip.inc", "dexsim_dynderiv.hip.inc"]
 
 
 DEBUG_SPIN_LIB = os.path.join(HERE, "libdexsim_dbgspin.so")

@@ -480,6 +480,38 @@ class DexSimCore:
         check(self.lib.dexsim_mass_solve(self.h, ids, k, qp, rp, nrhs, _abi.FD_ARMATURE if armature else 0, op, self._stream()),
               "mass_solve")
 
+    # ------------------------------------------------------------------ derivatives of the inverse and the forward dynamics
+    def _kin_deriv_outs(self, what, names, outs, k):
+        if all(o is None for o in outs):
+            raise DexSimError(f"{what}: at least one of {names[0]} and {names[1]} is required")
+        return [None if o is None else self._kin_out(what, n, o, (k, _abi.NJ, _abi.NJ)) for n, o in zip(names, outs)]
+
+    def inverse_dynamics_derivatives(self, dtau_dq=None, dtau_dqd=None, qdd=None, env_ids=None, q=None, qd=None, gravity=True):
+        """The derivatives of inverse_dynamics at fixed qdd into `dtau_dq` and / or `dtau_dqd`, each (k, 26, 26) f32 and
+        derivative-major: out[i, c, r] = d tau_r / d (q or qd)_c (the transpose of the Jacobian).  Either may be None, not both.
+        qdd and rows as for inverse_dynamics.  dexsim_inverse_dynamics_derivatives."""
+        what = "inverse_dynamics_derivatives"
+        ids, qp, vp, k = self._kin_rows_qd(what, env_ids, q, qd)
+        ap = None if qdd is None else self._kin_vel(what, "qdd", qdd, k)
+        dp, dvp = self._kin_deriv_outs(what, ("dtau_dq", "dtau_dqd"), (dtau_dq, dtau_dqd), k)
+        self._keep_kin = self._keep_kin + (qd, qdd)
+        check(self.lib.dexsim_inverse_dynamics_derivatives(self.h, ids, k, qp, vp, ap, _abi.ID_GRAVITY if gravity else 0, dp, dvp,
+                                                           self._stream()), what)
+
+    def forward_dynamics_derivatives(self, qdd, dqdd_dq=None, dqdd_dqd=None, tau=None, env_ids=None, q=None, qd=None, gravity=True,
+                                     armature=False):
+        """forward_dynamics into `qdd` (k, 26) f32 (required) and its derivatives at fixed tau into `dqdd_dq` and / or `dqdd_dqd`,
+        (k, 26, 26) f32, derivative-major: out[i, c, r] = d qdd_r / d (q or qd)_c.  tau, flags and rows as for forward_dynamics.
+        dexsim_forward_dynamics_derivatives."""
+        what = "forward_dynamics_derivatives"
+        ids, qp, vp, k = self._kin_rows_qd(what, env_ids, q, qd)
+        tp = None if tau is None else self._kin_vel(what, "tau", tau, k)
+        op = self._kin_out(what, "qdd", qdd, (k, _abi.NJ))
+        dp, dvp = self._kin_deriv_outs(what, ("dqdd_dq", "dqdd_dqd"), (dqdd_dq, dqdd_dqd), k)
+        self._keep_kin = self._keep_kin + (qd, tau)
+        flags = (_abi.FD_GRAVITY if gravity else 0) | (_abi.FD_ARMATURE if armature else 0)
+        check(self.lib.dexsim_forward_dynamics_derivatives(self.h, ids, k, qp, vp, tp, flags, op, dp, dvp, self._stream()), what)
+
     # ------------------------------------------------------------------ fingertip inverse kinematics
     def solve_ik(self, targets, controls, env_ids=None, q=None, sites=0, frame=0, free_mask=0x3FFC0, weights=(1, 1, 1, 1, 1),
                  iters=16, damping=1e-3, max_step=0.5, q_out=None, residual=None):

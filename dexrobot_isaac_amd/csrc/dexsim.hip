@@ -1094,3 +1094,63 @@ extern "C" int dexsim_mass_solve(dexsim_t h, const int64_t* env_ids, int k, cons
   KIN_LAUNCH(k_kin_fwddyn<false>, 1, K);
   return DEXSIM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------- dynamics derivatives
+// Behind the forward dynamics: the forward route launches k_kin_fwddyn on either side of the derivative kernel.
+// clang-format off
+#include "dexsim_dynderiv.hip.inc"
+// clang-format on
+
+// the checks of the derivative outputs: at least one, each 4-byte aligned
+static int kin_deriv_outs(const char* who, const char* na, const float* a, const char* nb, const float* b) {
+  if (!a && !b) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": at least one of " + na + " and " + nb + " is required").c_str());
+  int rc;
+  if (a && (rc = kin_out(who, na, a, 4))) return rc;
+  if (b && (rc = kin_out(who, nb, b, 4))) return rc;
+  return DEXSIM_OK;
+}
+
+extern "C" int dexsim_inverse_dynamics_derivatives(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd,
+                                                   const float* qdd, int flags, float* dtau_dq, float* dtau_dqd, void* stream) {
+  IdDeriv K;
+  std::memset(&K, 0, sizeof K);
+  int rc = kin_rows_qd("dexsim_inverse_dynamics_derivatives", h, env_ids, k, q, qd, &K.rows);
+  if (rc) return rc;
+  if ((flags & ~DEXSIM_ID_GRAVITY) != 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_inverse_dynamics_derivatives: unknown flag bits (DEXSIM_ID_GRAVITY is the only flag)");
+  if ((rc = kin_deriv_outs("dexsim_inverse_dynamics_derivatives", "dtau_dq", dtau_dq, "dtau_dqd", dtau_dqd))) return rc;
+  NEED_BOUND(h);
+  K.qd = qd; K.qdd = qdd; K.dq = dtau_dq; K.dqd = dtau_dqd; K.gravity = flags & DEXSIM_ID_GRAVITY;
+  KIN_LAUNCH(k_kin_id_deriv<false>, 1, K);
+  return DEXSIM_OK;
+}
+
+// Three launches on the caller's stream: qdd, then -d tau / d (q, qd) at that qdd, then the mass solve of the 26 rows of each
+// derivative, in place.
+extern "C" int dexsim_forward_dynamics_derivatives(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd,
+                                                   const float* tau, int flags, float* qdd, float* dqdd_dq, float* dqdd_dqd, void* stream) {
+  FwdDyn F;
+  std::memset(&F, 0, sizeof F);
+  int rc = kin_rows_qd("dexsim_forward_dynamics_derivatives", h, env_ids, k, q, qd, &F.rows);
+  if (rc) return rc;
+  if ((flags & ~(DEXSIM_FD_GRAVITY | DEXSIM_FD_ARMATURE)) != 0)
+    return fail(DEXSIM_ERR_ARG,
+                "dexsim_forward_dynamics_derivatives: unknown flag bits (DEXSIM_FD_GRAVITY and DEXSIM_FD_ARMATURE are the flags)");
+  if ((rc = kin_out("dexsim_forward_dynamics_derivatives", "qdd", qdd, 4))) return rc;
+  if ((rc = kin_deriv_outs("dexsim_forward_dynamics_derivatives", "dqdd_dq", dqdd_dq, "dqdd_dqd", dqdd_dqd))) return rc;
+  NEED_BOUND(h);
+  F.qd = qd; F.rhs = tau; F.out = qdd; F.nrhs = 1; F.gravity = flags & DEXSIM_FD_GRAVITY; F.armature = flags & DEXSIM_FD_ARMATURE;
+  KIN_LAUNCH(k_kin_fwddyn<true>, 1, F);
+  IdDeriv K;
+  std::memset(&K, 0, sizeof K);
+  K.rows = F.rows; K.qd = qd; K.qdd = qdd; K.dq = dqdd_dq; K.dqd = dqdd_dqd; K.gravity = flags & DEXSIM_FD_GRAVITY;
+  KIN_LAUNCH(k_kin_id_deriv<true>, 1, K);
+  static_assert(DEXSIM_NJ <= DEXSIM_MSOLVE_MAX_RHS, "the mass solve takes a derivative's 26 rows in one call");
+  F.qd = nullptr; F.nrhs = DEXSIM_NJ; F.gravity = 0;
+  for (float* d : {dqdd_dq, dqdd_dqd}) {
+    if (!d) continue;
+    F.rhs = d; F.out = d;
+    KIN_LAUNCH(k_kin_fwddyn<false>, 1, F);
+  }
+  return DEXSIM_OK;
+}

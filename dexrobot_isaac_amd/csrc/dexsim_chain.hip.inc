@@ -1,5 +1,5 @@
 // dexsim_chain.hip.inc -- the frame the query kernels share (k_render_scene, k_kin_jacobian, k_kin_mass, k_ik_solve, k_proximity,
-// k_kin_invdyn, k_kin_bias_accel, k_kin_fwddyn): pure functions of q (the last three of q and qd), off the step path, writing
+// k_kin_invdyn, k_kin_bias_accel, k_kin_fwddyn, k_kin_id_deriv): pure functions of q (the last four of q and qd), off the step path, writing
 // caller-owned memory only.  Force-inlined functions and macros only: this file emits no code of its own.
 //
 //   joint_frame      THE joint-frame rule: parent frame -> a joint's offset, world axis and frame.  Every walk of the family is

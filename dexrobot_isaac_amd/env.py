@@ -985,6 +985,39 @@ class DexHandEnv:
         core.mass_solve(out.view(k, -1, _abi.NJ), rhs.contiguous().view(k, -1, _abi.NJ), env_ids=ids, q=q, armature=armature)
         return out
 
+    # ------------------------------------------------------------------ derivatives of the inverse and the forward dynamics
+    def _kindyn_outs(self, what, out, shapes, device):
+        """_kindyn_out for a call with several outputs: `out` is None or a tuple / list with one tensor per shape."""
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != len(shapes)):
+            raise ValueError(f"{what}: out must be a tuple of {len(shapes)} tensors")
+        return [self._kindyn_out(what, o, s, device) for o, s in zip(out or [None] * len(shapes), shapes)]
+
+    def get_inverse_dynamics_derivatives(self, qdd=None, env_ids=None, q=None, qd=None, gravity=True, out=None):
+        """(dtau_dq, dtau_dqd), each (k, 26, 26): the derivatives of get_inverse_dynamics(qdd, ...) with respect to the joint
+        positions and velocities at fixed qdd, analytic.  D[i, r, c] = d tau_r / d q_c, so D[i] @ dq is the first-order change of
+        tau.  The two are TRANSPOSED VIEWS of the device's derivative-major arrays (dexsim.h): call .contiguous() for a dense
+        matrix, or .transpose(1, 2) for the (k, c, r) array as it was written.  Arguments and rows as for get_inverse_dynamics.
+        out: a pair of contiguous (k, 26, 26) tensors that receive the derivative-major arrays; the views returned are of them."""
+        what = "get_inverse_dynamics_derivatives"
+        core, ids, q, qd, k = self._kindyn_rows_qd(what, "inverse_dynamics_derivatives", env_ids, q, qd)
+        qdd = self._kindyn_vel(what, "qdd", qdd, k, core.device)
+        dq, dqd = self._kindyn_outs(what, out, [(k, _abi.NJ, _abi.NJ)] * 2, core.device)
+        core.inverse_dynamics_derivatives(dq, dqd, qdd=qdd, env_ids=ids, q=q, qd=qd, gravity=gravity)
+        return dq.transpose(1, 2), dqd.transpose(1, 2)
+
+    def get_forward_dynamics_derivatives(self, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False, out=None):
+        """(qdd, dqdd_dq, dqdd_dqd): the (k, 26) result of get_forward_dynamics(tau, ...) and its (k, 26, 26) derivatives with
+        respect to the joint positions and velocities at fixed tau, D[i, r, c] = d qdd_r / d q_c, as transposed views like
+        get_inverse_dynamics_derivatives.  d qdd / d tau is (M [+ A])^-1: solve_mass_matrix of 26 unit columns.  Unbounded at
+        the base's gimbal lock, where M is singular.  Arguments and rows as for get_forward_dynamics.  out: a triple of contiguous
+        tensors (k, 26), (k, 26, 26), (k, 26, 26) that receive qdd and the derivative-major arrays."""
+        what = "get_forward_dynamics_derivatives"
+        core, ids, q, qd, k = self._kindyn_rows_qd(what, "forward_dynamics_derivatives", env_ids, q, qd)
+        tau = self._kindyn_vel(what, "tau", tau, k, core.device)
+        qdd, dq, dqd = self._kindyn_outs(what, out, [(k, _abi.NJ)] + [(k, _abi.NJ, _abi.NJ)] * 2, core.device)
+        core.forward_dynamics_derivatives(qdd, dq, dqd, tau=tau, env_ids=ids, q=q, qd=qd, gravity=gravity, armature=armature)
+        return qdd, dq.transpose(1, 2), dqd.transpose(1, 2)
+
     # ------------------------------------------------------------------ fingertip inverse kinematics
     @property
     def control_names(self):

@@ -806,6 +806,46 @@ int dexsim_forward_dynamics(dexsim_t h, const int64_t* env_ids, int k, const flo
 int dexsim_mass_solve(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* rhs, int nrhs, int flags,
                       float* out, void* stream);
 
+/* ------------------------------------------------------------------ derivatives of the inverse and the forward dynamics
+ * The linearisation of the two calls above about a state: what a trajectory optimiser (iLQR / DDP), an LQR design about a pose,
+ * a stability check of an impedance law and a model-based learner consume.  Analytic (the tangent of the Newton-Euler pass), not
+ * finite differences: in fp32 differences of dexsim_inverse_dynamics have no step at which roundoff and truncation are both small.
+ * Both calls are stream-ordered, never synchronise and allocate nothing, and neither writes any arena word, API tensor, statistics
+ * word, counter or the step stamp.  A row's result depends on that row alone and is reproducible bit for bit.
+ *
+ * INVERSE-DYNAMICS DERIVATIVES  of tau(q, qd, qdd) = M(q) qdd + c(q, qd) [+ g(q)], exactly the function dexsim_inverse_dynamics
+ * computes (no armature, no PD, no contact, no joint-limit terms), at fixed qdd:
+ *     dtau_dq[i, c, r] = d tau_r / d q_c          dtau_dqd[i, c, r] = d tau_r / d qd_c
+ * LAYOUT: every derivative output of this section is (k, 26, 26) f32, 4-byte aligned, DERIVATIVE-MAJOR: the 26 contiguous words
+ * out[i, c, :] are the derivative of the WHOLE vector with respect to coordinate c.  As a matrix out[i] is the TRANSPOSE of the
+ * Jacobian d tau / d q; the first-order change is sum_c out[i, c, :] dq_c.  This is the row layout of dexsim_mass_solve
+ * (out[i, r, :] = one right-hand side), so the forward route below solves its 26 rows in place.
+ * ROWS, the (q, qd) overrides, ids outside [0, num_envs) (their output rows are left untouched) and qdd (optional, aligned with
+ * the OUTPUT rows, NULL = zero) are those of dexsim_inverse_dynamics, word for word; DEXSIM_ID_GRAVITY is the only flag.  Either
+ * output may be NULL (it is then not computed; the other has the bits it has when both are given), not both.
+ * STRUCTURAL ZEROS: the torque of a joint of finger f does not depend on (q, qd) of finger g != f; those 4 x 4 blocks are written
+ * as +0.0, not left untouched.
+ *
+ * FORWARD-DYNAMICS DERIVATIVES  of qdd(q, qd, tau) = (M(q) [+ A])^-1 (tau - c(q, qd) [- g(q)]), the function
+ * dexsim_forward_dynamics computes, at fixed tau; flags DEXSIM_FD_GRAVITY | DEXSIM_FD_ARMATURE with the same meaning:
+ *     dqdd_dq = -(M [+ A])^-1 dtau_dq      dqdd_dqd = -(M [+ A])^-1 dtau_dqd      (dtau_* at the returned qdd; A is constant)
+ * in the layout above: dqdd_dq[i, c, r] = d qdd_r / d q_c.  qdd (k, 26) is REQUIRED: it receives the forward-dynamics result (the
+ * bits of dexsim_forward_dynamics) and is where the intermediate lives, since nothing is allocated.  Either derivative output may
+ * be NULL, not both.  Three launches on the stream: forward dynamics into qdd, the negated inverse-dynamics derivatives at that
+ * qdd, the mass solve of each output's 26 rows in place.  Contract: as numbers (-0 == +0) the result equals the negated
+ * dexsim_mass_solve (nrhs = 26, same DEXSIM_FD_ARMATURE) of dexsim_inverse_dynamics_derivatives at the returned qdd with the same
+ * gravity flag.  There is no third output: d qdd / d tau is (M [+ A])^-1, which dexsim_mass_solve with 26 unit columns gives.
+ * ROWS, overrides and tau (optional, aligned with the output rows, NULL = zero) are those of dexsim_forward_dynamics.  The base's
+ * gimbal lock (q4 = +-pi/2), where M is singular, makes these derivatives unbounded.
+ *
+ * DEXSIM_ERR_ARG (with a dexsim_last_error text; no device needed, nothing is launched): the lists of dexsim_inverse_dynamics and
+ * dexsim_forward_dynamics, plus both derivative outputs NULL, a misaligned derivative output, and a NULL or misaligned qdd of the
+ * forward call.  DEXSIM_ERR_NOT_BOUND before dexsim_bind. */
+int dexsim_inverse_dynamics_derivatives(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd,
+                                        const float* qdd, int flags, float* dtau_dq, float* dtau_dqd, void* stream);
+int dexsim_forward_dynamics_derivatives(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd,
+                                        const float* tau, int flags, float* qdd, float* dqdd_dq, float* dqdd_dqd, void* stream);
+
 const char* dexsim_error_string(int code);
 const char* dexsim_last_error(void);
 
