@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdexsim.so")
-SOURCES = ["dexsim.hip", "dexsim_device.h", "dexsim_physics.hip.inc", "dexsim_l2.hip.inc", "dexsim_state.hip.inc",
+SOURCES = ["dexsim.hip", "dexsim_device.h", "dexsim_stamps.h", "dexsim_physics.hip.inc", "dexsim_l2.hip.inc", "dexsim_state.hip.inc",
            "dexsim_chain.hip.inc", "dexsim_render.hip.inc", "dexsim_kindyn.hip.inc", "dexsim_ik.hip.inc", "dexsim_proximity.hip.inc",
            "dexsim_invdyn.hip.inc", "dexsim_fwddyn.hip.inc", "dexsim_dynderiv.hip.inc"]
 
@@ -31,6 +31,21 @@ def build_debug_spin(force=False, bound=2000000):
     dexsim_physics.hip.inc): a sequencing bug shows up as a recorded word in the counters block instead of a hung GPU.
     Loaded only by tests/ (DEXSIM_LIB_PATH); the product never uses it."""
     return build_lib(force=force, defs=(f"-DDEXSIM_DEBUG_SPIN={int(bound)}",), out=DEBUG_SPIN_LIB)
+
+
+PROFILE_LIB = os.path.join(HERE, "..", "build_variants", "libdexsim_prof.so")
+
+
+def build_profile(detail=None, extra_defs=(), out=PROFILE_LIB, force=True):
+    """Profiling twin of the library (-DDEXSIM_PROFILE_PHASES: per-wave cycle stamps, csrc/dexsim_stamps.h), for
+    scripts/phase_profile.py.  detail: the detail groups of the header's list to compile in, a name or several ("SCHUR",
+    ("SCHUR", "SWEEP05"), "NONE"); None = the header's default.  extra_defs: further -D experiment switches.  Same code-generation
+    flags as the product, so that the stamps time the kernel that ships; never built next to the package."""
+    defs = ["-DDEXSIM_PROFILE_PHASES"]
+    if detail:
+        defs.append("-DDEXSIM_PROFILE_DETAIL=" + "|".join([detail] if isinstance(detail, str) else detail))
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    return build_lib(force=force, defs=(*defs, *extra_defs), out=out)
 
 
 def build_lib(force=False, verbose=False, defs=(), out=None):
@@ -59,5 +74,11 @@ def build_lib(force=False, verbose=False, defs=(), out=None):
     return lib
 
 
-if __name__ == "__main__":
-    print(build_lib(force=True, verbose=True))
+if __name__ == "__main__":   # python -m dexrobot_isaac_amd.build [--out PATH] [-D...]: the library, or a variant of it with defines
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    args, defs = ap.parse_known_args()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    print(build_lib(force=True, verbose=True, defs=tuple(defs), out=args.out))

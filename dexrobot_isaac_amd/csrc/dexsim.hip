@@ -5,6 +5,7 @@
 #include <cmath>
 #include <algorithm>
 #include "dexsim_device.h"
+#include "dexsim_stamps.h"
 
 #include <cstdio>
 #include <cstdlib>

@@ -132,11 +132,6 @@ DI Q4 site_quat(const Arena& A, int N, int e, int s) {
 //   phase B  wave 0: task observations + FSM, termination, rewards -- reading the helper results back from the LDS
 //            tile, writing the reward table into LDS
 //   phase C  all waves: coalesced flush of obs_all, obs_buf and the reward table
-#ifdef DEXSIM_PROFILE_PHASES
-#define PB_STAMP(k) do { if (threadIdx.x == 0) A.crow[(size_t)(32 + (k)) * N + blockIdx.x * 64] = __int_as_float((int)(__builtin_amdgcn_s_memtime() - pb_t0)); } while (0)
-#else
-#define PB_STAMP(k) do {} while (0)
-#endif
 // LDS staging behind the observation tile (word index x 64 lanes)
 #define ST_PEN 0      /* joint-limit penalty sum (task 0)                 */
 #define ST_FV2 1      /* sum of squared finger velocities (task 2)        */
@@ -341,9 +336,7 @@ DI void post_logic_a(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   const DexSimConfig& C = P->cfg;
   const float cdt = C.control_dt;
   const bool blind = C.task == DEXSIM_TASK_BLIND_GRASPING;
-#ifdef DEXSIM_PROFILE_PHASES
-  const unsigned long long pb_t0 = __builtin_amdgcn_s_memtime();
-#endif
+  const Stamps st = Stamps::begin(0);
   // own copies of the few inputs the helper waves also turn into observation rows (same arithmetic, same values)
   const V3 hp = in.hp;
   V3 pad[5];
@@ -429,7 +422,7 @@ DI void post_logic_a(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     OB(O_stage_progress) = prog;
   }
 
-  PB_STAMP(2);
+  st.mark<SG_POST_LOGIC>(A, N, 0, blockIdx.x * 64, PL_TASK_OBS);
   if (obs_only) return;
 
   // ---- episode progress, termination (step_processor.py:80-181)
@@ -484,9 +477,7 @@ DI void post_logic_b(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   const bool real = e < NR;
   const DexSimConfig& C = P->cfg;
   const bool blind = C.task == DEXSIM_TASK_BLIND_GRASPING;
-#ifdef DEXSIM_PROFILE_PHASES
-  const unsigned long long pb_t0 = __builtin_amdgcn_s_memtime();
-#endif
+  const Stamps st = Stamps::begin(0);
   const int estep = m.estep, stage = m.stage, just2 = m.just2, just3 = m.just3, grasp = m.grasp, thumb = m.thumb, others = m.others;
   const int t_succ = m.t_succ, t_fail = m.t_fail, t_tout = m.t_tout, should_reset = m.should_reset, sreason = m.sreason, crit_s = m.crit_s;
   int freason[DEXSIM_NUM_FAIL], crit_f[DEXSIM_NUM_FAIL];
@@ -502,7 +493,7 @@ DI void post_logic_b(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     cmag[f] = m.cmag[f];
     tip[f] = {OB(O_fingertip_poses_world + 7 * f), OB(O_fingertip_poses_world + 7 * f + 1), OB(O_fingertip_poses_world + 7 * f + 2)};
   }
-  PB_STAMP(3);
+  st.mark<SG_POST_LOGIC>(A, N, 0, blockIdx.x * 64, PL_TERMINATION);
   // ---- rewards
   float r[DEXSIM_NUM_REWARD_TERMS];
 #pragma unroll
@@ -560,7 +551,7 @@ DI void post_logic_b(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     r[DEXSIM_REW_s2_completion] = (just3 && !crit_f[3]) ? 1.f : 0.f;
     r[DEXSIM_REW_penetration_penalty] = fmaxf(half * C.geometric_penetration_factor - mind, 0.f) * C.penetration_depth_scale;
   }
-  PB_STAMP(4);
+  st.mark<SG_POST_LOGIC>(A, N, 0, blockIdx.x * 64, PL_REWARD_TERMS);
   float total = 0.f;
 #pragma unroll
   for (int i = 0; i < DEXSIM_NUM_REWARD_TERMS; i++) {
@@ -595,7 +586,7 @@ DI void post_logic_b(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     }
   }
 
-  PB_STAMP(5);
+  st.mark<SG_POST_LOGIC>(A, N, 0, blockIdx.x * 64, PL_REWARD_TABLE);
   // ---- cross-env statistics: wavefront ballot -> one atomic per wave and counter
   const int rs = real ? should_reset : 0;
   auto wave_count = [&](int pred, int slot) {
@@ -610,7 +601,7 @@ DI void post_logic_b(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   wave_count(real && t_succ, CNT_TERM_SUCCESS);
   wave_count(real && t_fail, CNT_TERM_FAILURE);
   wave_count(real && t_tout, CNT_TERM_TIMEOUT);
-  PB_STAMP(6);
+  st.mark<SG_POST_LOGIC>(A, N, 0, blockIdx.x * 64, PL_STATS);
 }
 
 DI void reset_phase0(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, int N, int NR, int e);   // below
@@ -641,13 +632,7 @@ DI void post_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict
   int* s_tab = (int*)(s_st + 64 * ST_WORDS);     // obs_buf column -> obs_all row, staged for the flush
   const int e = blockIdx.x * 64 + lane;
   const DexSimConfig& C = P->cfg;
-#ifdef DEXSIM_PROFILE_PHASES
-  const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-  int stamp_i = 0;
-#define POST_STAMP() do { if (lane == 0) A.crow[(size_t)(wv * 8 + stamp_i) * N + blockIdx.x * 64] = __int_as_float((int)(__builtin_amdgcn_s_memtime() - t_start)); stamp_i++; } while (0)
-#else
-#define POST_STAMP() do {} while (0)
-#endif
+  const Stamps st = Stamps::begin(0);
   // ---- phase A
   PostIn in;
   PostMid mid;
@@ -666,7 +651,7 @@ DI void post_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict
       if (!((done_mask >> t) & 1) && (nw == 7 ? c_post_task_wave7[t] : c_post_task_wave[t] % nh) == wv - 1)
         post_task(t, A, P, cnt, s_ob, s_st, obs_only, N);
   }
-  POST_STAMP();   // 0: phase A done
+  st.mark<SG_POST>(A, N, wv, blockIdx.x * 64, POST_A);
   __syncthreads();
   // ---- phase B: wave 0 runs the reward / bookkeeping logic (it reads the tile, it does not write it); the observation
   // tile has been complete since the barrier above, so the helper waves flush it meanwhile, with 16-byte accesses.  A
@@ -722,7 +707,7 @@ DI void post_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict
       }
     }
   }
-  POST_STAMP();   // 1: phase B done (helpers: observation flush issued)
+  st.mark<SG_POST>(A, N, wv, blockIdx.x * 64, POST_B);   // (helpers: observation flush issued)
   __syncthreads();
   // ---- phase C: the reward table wave 0 has just written (rows + the total reward row), all waves
   if (!obs_only) {
@@ -736,9 +721,8 @@ DI void post_block(const Arena& A, const ApiPtrs& T, const DevParams* __restrict
       }
     }
   }
-  POST_STAMP();   // 2: reward rows issued
-  POST_STAMP();   // 3: obs_buf flush issued
-#undef POST_STAMP
+  st.mark<SG_POST>(A, N, wv, blockIdx.x * 64, POST_ROWS);
+  st.mark<SG_POST>(A, N, wv, blockIdx.x * 64, POST_OBS);
 }
 
 #define POST_LDS_BYTES ((64 * OB_STRIDE + 64 * ST_WORDS + DEXSIM_OBS_ALL_DIM) * sizeof(float))

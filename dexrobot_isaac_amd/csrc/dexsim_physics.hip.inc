@@ -863,14 +863,9 @@ DI void schur_helper(float* sh, const int dlb, int job, int lane) {
 // composite part of S meanwhile and picks the sums up behind their tokens.
 DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseChain& B, float* sh, const int dlb, float* uB_out,
                    int lane, int N, int e, int tgt_lds = -1, bool solve_only = false, int split_seq = 0,
-                   unsigned long long dbg_t0 = 0, int dbg_row = 0, int* dbg_cnt = nullptr) {
-#if defined(DEXSIM_PROFILE_PHASES) && defined(DBG_SCHUR)
-#define SCHUR_STAMP(i) do { if (lane == 0) A.crow[(size_t)(dbg_row + (i)) * N + e] = __int_as_float((int)(__builtin_amdgcn_s_memtime() - dbg_t0)); } while (0)
-#else
-#define SCHUR_STAMP(i) do {} while (0)
-#endif
+                   const Stamps st = {}, int* dbg_cnt = nullptr) {
   const float h = P->h;
-  SCHUR_STAMP(0);
+  st.mark<SG_SCHUR>(A, N, 0, e, SCHUR_START);
   Comp comp5;
   V3 f5 = sh_get3(sh, lane, DL_PALM_WRENCH), n5 = sh_get3(sh, lane, DL_PALM_WRENCH + 3);
   float Ssub[21], gsum[6] = {0, 0, 0, 0, 0, 0};
@@ -889,7 +884,7 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
       for (int i = 0; i < 6; i++) gsum[i] += SH(DL_GSUM(dlb, f) + i);
     }
   }
-  SCHUR_STAMP(1);   // composite sum done
+  st.mark<SG_SCHUR>(A, N, 0, e, SCHUR_COMPOSITE);   // composite sum done
   float S[36];
   if (split_seq > 0) schur_row<5, 0, 3>(sh, dlb, lane);   // (the other rows come from the helpers)
   else {
@@ -907,7 +902,7 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
       }
     }
   }
-  SCHUR_STAMP(2);   // own rows done
+  st.mark<SG_SCHUR>(A, N, 0, e, SCHUR_OWN_ROWS);   // own rows done
   float tauB[6];
   float bias[6];
   if (split_seq > 0) {
@@ -920,7 +915,7 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
       while (__float_as_int(*(volatile float*)(sh + (FS_FLAG + w) * 64)) != want) { __builtin_amdgcn_s_sleep(1); SPIN_GUARD(dbg_cnt, 1, split_seq); }
     }
     asm volatile("" ::: "memory");
-    SCHUR_STAMP(3);   // tokens seen
+    st.mark<SG_SCHUR>(A, N, 0, e, SCHUR_TOKENS);   // tokens seen
     {
       int idx = 0;
 #pragma unroll
@@ -953,13 +948,13 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
       tauB[i] = kp * (tgt - B.qb[i]) - kdh * B.qdb[i] - bias[i] - gsum[i];
     }
   }
-  SCHUR_STAMP(4);   // S, tau_B complete
+  st.mark<SG_SCHUR>(A, N, 0, e, SCHUR_S_TAUB);   // S, tau_B complete
   if (solve_only) {
     float x[6];
     spd_solve<6>(S, tauB, x);
 #pragma unroll
     for (int i = 0; i < 6; i++) uB_out[i] = B.qdb[i] + h * x[i];
-    SCHUR_STAMP(5);   // solved
+    st.mark<SG_SCHUR>(A, N, 0, e, SCHUR_SOLVED);   // solved
     return;
   }
   spd_inverse<6>(S);
@@ -2076,27 +2071,7 @@ DI void build_rows_item(const DevParams* __restrict__ P, int N, int ol, int k, i
 // words per lane, the row builder's matrices) sits next to the few values substep_body keeps alive across them, not next to the
 // finger dynamics' or the publication's.  (Inlined: the allocation is the whole kernel's, and it is close to the 256-register
 // budget -- a change here is checked with -Rpass-analysis=kernel-resource-usage for 0 bytes of scratch.)
-#ifdef DEXSIM_PROFILE_PHASES
-#define GP_STAMP(i) do { if (lane == 0) A.crow[(size_t)(stamp_base + wv * 8 + (i)) * N + e] = __int_as_float((int)(__builtin_amdgcn_s_memtime() - t_start)); } while (0)
-#endif
-#if defined(DEXSIM_PROFILE_PHASES) && !defined(DBG_PH2) && !defined(DBG_ROWS)   /* (the phase-2 / row-build stamps use the same rows) */
-#define SWEEP_STAMP(i) do { if (it == 2 && lane == 0 && (wv == 0 || wv == 5) && stamp_base + 64 <= DEXSIM_KMAX * 3 * 28) A.crow[(size_t)(stamp_base + 56 + (i) + (wv == 5 ? 5 : 0)) * N + e] = __int_as_float((int)(__builtin_amdgcn_s_memtime() - t_start)); } while (0)
-#else
-#define SWEEP_STAMP(i) do {} while (0)
-#endif
-#ifndef DEXSIM_PROFILE_PHASES
-#define GP_STAMP(i) do {} while (0)
-#endif
-// per-wave stamps inside pass 2 of the sweeps (single-body launch, stamp_base == 0): rows 400 + 8 wave + i, i = 0 pass start, 1 own
-// work done (item update / box block sweep), 2 first barrier passed, 3 reduction done, 4 second barrier passed
-#if defined(DEXSIM_PROFILE_PHASES) && defined(DBG_SWEEP)
-#define SWEEP_STAMP2X(cond, i) do { if ((cond) && (threadIdx.x & 63) == 0 && stamp_base == 0) A.crow[(size_t)(400 + wv * 8 + (i)) * N + blockIdx.x * 64] = __int_as_float((int)(__builtin_amdgcn_s_memtime() - t_start)); } while (0)
-#else
-#define SWEEP_STAMP2X(cond, i) do {} while (0)
-#endif
-#define SWEEP_STAMP2(i) SWEEP_STAMP2X(it == 2, i)
-DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, int lane, int e,
-                                                                  unsigned long long t_start, int stamp_base, unsigned* probe) {
+DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, int lane, int e, const Stamps st, unsigned* probe) {
   extern __shared__ __attribute__((aligned(16))) float sh[];
   const Arena& A = P->arena;
   const DexSimConfig& C = P->cfg;
@@ -2138,7 +2113,7 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
       }
     }
   }
-  GP_STAMP(3);   // phase 3 done
+  st.mark<SG_BODY>(A, N, wv, e, PH_3_ROWS);   // phase 3 done
   __syncthreads();
   unsigned long long pr_t4 = 0;
   if (probe && wv == 0) pr_t4 = __builtin_amdgcn_s_memtime();
@@ -2172,9 +2147,9 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
       }
 #pragma unroll 1
       for (int it = 0; it <= iters; it++) {
-        SWEEP_STAMP2(1);
+        if (it == 2) st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_WORK);
         __syncthreads();
-        SWEEP_STAMP2(2);
+        if (it == 2) st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_BARRIER1);
         int b = 0;
         if (((nbmax + 3) & ~3) >= 8) {   // (eight blocks per batch, as on the palm wave)
           const f4 y0 = *XQ(0, 2), y1 = *XQ(1, 2), y2 = *XQ(2, 2), y3 = *XQ(3, 2), y4 = *XQ(4, 2), y5 = *XQ(5, 2), y6 = *XQ(6, 2), y7 = *XQ(7, 2);
@@ -2188,11 +2163,11 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
         }
         Tm0 += *XQ(12, 2);
         *TQ(2) = Tm0;
-        SWEEP_STAMP2(3);
+        if (it == 2) st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_REDUCED);
         __syncthreads();
-        SWEEP_STAMP2(4);
+        if (it == 2) st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_BARRIER2);
         if (it == iters) break;
-        SWEEP_STAMP2X(it == 1, 0);   // (the box block's work of pass 2 starts here)
+        if (it == 1) st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_START);   // (the box block's work of pass 2 starts here)
         const f4 q1 = *TQ(1);
         const f2 o01 = q1.zw, o23 = Tm0.xy, o45 = Tm0.zw;
         f2 v01 = o01, v23 = o23, v45 = o45, d01 = {0.f, 0.f}, d23 = {0.f, 0.f}, d45 = {0.f, 0.f};
@@ -2229,12 +2204,11 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
       // phase 3 -- so the sums need no per-lane masks; only the finger reducers, whose block range differs from lane to lane,
       // select)
       int it = 0;   // pass counter (profile stamps)
-      (void)it;
       const int nb4 = (nbmax + 3) & ~3;     // block loops run in batches of four independent loads (unused blocks read as zero)
       auto exchange = [&]() {
-        SWEEP_STAMP2(1);
+        if (it == 2) st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_WORK);
         __syncthreads();
-        SWEEP_STAMP(2); SWEEP_STAMP2(2);
+        if (it == 2) { st.mark<SG_SWEEP05>(A, N, wv, e, SW_BARRIER1); st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_BARRIER1); }
         if (wv < 5) {
           f4 t = *TQ(3 + wv);
 #pragma unroll 1
@@ -2272,9 +2246,9 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
           t1 += *XQ(12, 1);
           *TQ(1) = t1;
         }
-        SWEEP_STAMP(3); SWEEP_STAMP2(3);
+        if (it == 2) { st.mark<SG_SWEEP05>(A, N, wv, e, SW_REDUCED); st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_REDUCED); }
         __syncthreads();
-        SWEEP_STAMP2(4);
+        if (it == 2) st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_BARRIER2);
       };
       const bool fast = jmax <= 12 && n_items <= 6 * 64;   // every block is one contact and every item has a lane of its own
       {
@@ -2315,7 +2289,7 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
         exchange();
 #pragma unroll 1
         for (it = 1; it <= iters; it++) {
-          SWEEP_STAMP(0); SWEEP_STAMP2(0);
+          if (it == 2) { st.mark<SG_SWEEP05>(A, N, wv, blockIdx.x * 64, SW_START); st.mark<SG_SWEEP_ALL>(A, N, wv, blockIdx.x * 64, SW_START); }
           if (have) {
             const f4 t0 = *TQ(0), t1 = *TQ(1), t2 = *TQ(2), tq = *TQ(qi);
             TurnVel vl;
@@ -2329,9 +2303,9 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
             *XQ(blk, 0) = f4{dU01.x, dU01.y, dU23.x, dU23.y}; *XQ(blk, 1) = f4{dU45.x, dU45.y, dV01.x, dV01.y};
             *XQ(blk, 2) = f4{dVW.x, dVW.y, dW12.x, dW12.y}; *XQ(blk, 3) = f4{dG01.x, dG01.y, dG23.x, dG23.y};
           }
-          SWEEP_STAMP(1);
+          if (it == 2) st.mark<SG_SWEEP05>(A, N, wv, blockIdx.x * 64, SW_WORK);
           exchange();
-          SWEEP_STAMP(4);
+          if (it == 2) st.mark<SG_SWEEP05>(A, N, wv, blockIdx.x * 64, SW_BARRIER2);
         }
         if (R.act) {   // impulses: to LDS (contact forces of the last sub-step) and to the warm-start cache
           s_lam[(3 * kk) * 64 + lane] = lam[0]; s_lam[(3 * kk + 1) * 64 + lane] = lam[1]; s_lam[(3 * kk + 2) * 64 + lane] = lam[2];
@@ -2439,13 +2413,11 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
       }
     }
   }
-  GP_STAMP(4);   // phase 4 done
+  st.mark<SG_BODY>(A, N, wv, e, PH_4_SWEEPS);   // phase 4 done
   if (wv == 6) __builtin_amdgcn_s_setprio(2);
   __syncthreads();
   if (probe && wv == 0 && lane == 0) atomicAdd(probe + blockIdx.x * 4 + 3, (unsigned)(__builtin_amdgcn_s_memtime() - pr_t4));
 }
-#undef GP_STAMP
-#undef SWEEP_STAMP
 
 // carry (k_physics4): what a body hands to the next inlined body without going through the arena -- the finger wave's own joint
 // state in registers, base joints and box position (which every wave needs) through LDS words (FS_CARRY_*).  The arena is
@@ -2455,10 +2427,10 @@ DI void general_contact_phases(const DevParams* __restrict__ P, int N, int wv, i
 struct SubstepCarry { float ql[4], qdl[4], tg[4]; };
 template <bool LAST, bool MS>
 // seq: 1-based index of this body within the launch (token of the wave-5 -> wave-6 hand_free hand-off, see FS_FLAG)
-// post_pre (last sub-step of the fused control step only): the box wave, idle during the publication, already runs the
+// (st: the profiling build's cycle stamps of this body, dexsim_stamps.h)  post_pre (last sub-step of the fused control step only): the box wave, idle during the publication, already runs the
 // post-physics tasks that do not depend on it (POST_PRE_MASK) into the observation tile at the bottom of the LDS
 DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restrict__ P, int* __restrict__ cnt, int N, int NR, float* sh,
-                     int seq, int stamp_base, bool post_pre, bool count_contacts, SubstepCarry& carry, bool carry_in, bool carry_out) {
+                     int seq, const Stamps st, bool post_pre, bool count_contacts, SubstepCarry& carry, bool carry_in, bool carry_out) {
   constexpr int dlb = FS_ROW;
   // contact statistics: only a control step's main physics step counts (a gated launch would race with finalize_stats);
   // word = stamp parity, see CNT_CONTACTS
@@ -2468,21 +2440,6 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   // words of finger f -- is scalar arithmetic instead of ~20 VGPRs of hoisted index products)
   const int wv = __builtin_amdgcn_readfirstlane(wave_role(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   const int e = blockIdx.x * 64 + lane;
-#ifdef DEXSIM_PROFILE_PHASES
-  // diagnostic build only (scripts/phase_profile.py): per-wave cycle stamps at the phase boundaries, written to the
-  // otherwise idle `crow` rows of lane 0; never compiled into the product library
-  const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-  int stamp_i = 0;
-#ifdef DBG_PH2
-#define PH2_STAMP(i) do { if (lane == 0 && (wv == 1 || wv == 5)) A.crow[(size_t)(stamp_base + 56 + (i) + (wv == 5 ? 4 : 0)) * N + e] = __int_as_float((int)(__builtin_amdgcn_s_memtime() - t_start)); } while (0)
-#else
-#define PH2_STAMP(i) do {} while (0)
-#endif
-#define PHASE_STAMP() do { if (lane == 0) A.crow[(size_t)(stamp_base + wv * 8 + stamp_i) * N + e] = __int_as_float((int)(__builtin_amdgcn_s_memtime() - t_start)); stamp_i++; } while (0)
-#else
-#define PH2_STAMP(i) do {} while (0)
-#define PHASE_STAMP() do {} while (0)
-#endif
   {
   const DexHandModel& M = P->model;
   const DexSimConfig& C = P->cfg;
@@ -2532,7 +2489,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
       if (lane == 0) sh[(FS_FLAG + 5) * 64] = __int_as_float((seq << 1) | (pclear ? 1 : 0));
     }
   }
-  PHASE_STAMP();   // 0: base chain done
+  st.mark<SG_BODY>(A, N, wv, e, PH_BASE_CHAIN);
 
   // ---- phase 1
   int nc = 0, nbg = 0;
@@ -2675,7 +2632,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     SH(DL_NC) = __int_as_float(nc | (nbg << 8));
     // The box wave's own copy of the phase-1 barrier and of its phase 2 (the speculative block is only defined and used
     // inside this branch).
-    PHASE_STAMP();   // 1: phase 1 done
+    st.mark<SG_BODY>(A, N, wv, e, PH_1);
     __syncthreads();
     if (hand_free) {   // the speculation held: the remaining sweeps, then commit twist, impulses and (last sub-step) forces
       if (has_box) {
@@ -2691,7 +2648,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     }
   }
   if (wv != 6) {
-    PHASE_STAMP();   // 1: phase 1 done
+    st.mark<SG_BODY>(A, N, wv, e, PH_1);
     __syncthreads();
   }
   // Hand clear of box and ground in the whole workgroup and at most 4 box/ground contacts per env: the box and the
@@ -2711,11 +2668,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     if (lane == 0) *(volatile float*)(sh + (FS_FLAG + wv) * 64) = __int_as_float((seq << 1) | 1 | SCHUR_SPLIT_BIT);
   }
   if (wv == 0) {
-    #ifdef DEXSIM_PROFILE_PHASES
-    schur_base(A, P, B, sh, dlb, uB, lane, N, e, FS_TGTB, early, early ? seq : 0, t_start, stamp_base + 56, cnt);
-#else
-    schur_base(A, P, B, sh, dlb, uB, lane, N, e, FS_TGTB, early, early ? seq : 0, 0, 0, cnt);
-#endif
+    schur_base(A, P, B, sh, dlb, uB, lane, N, e, FS_TGTB, early, early ? seq : 0, st, cnt);
     if (early) {
 #pragma unroll
       for (int i = 0; i < 6; i++) SH(FS_UB + i) = uB[i];
@@ -2782,10 +2735,10 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     // counts (+ which contacts touch the box) go into the (now dead) token words, tagged so that they can never look like a
     // token of a later sub-step
     const int nbg0 = __float_as_int(SH(DL_NC)) & 0xff;   // box/ground contacts found by wave 6 (read before wave 0 rewrites the word)
-    PH2_STAMP(0);
+    st.mark<SG_PH2>(A, N, wv, e, PH2_NARROW);
     if (cw >= 0) SH(FS_FLAG + cw) = __int_as_float(NP_TAG | ((clear_mask >> cw) & 1) | (nloc << 1) | (tmask << 8));
     __syncthreads();
-    PH2_STAMP(1);
+    st.mark<SG_PH2>(A, N, wv, e, PH2_BARRIER);
     if (cw >= 0) {
       int off = nbg0;
       int tot = off;
@@ -2816,7 +2769,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
           }
         }
       }
-      PH2_STAMP(2);
+      st.mark<SG_PH2>(A, N, wv, e, PH2_APPENDED);
     }
     if (wv == 0) {
       // list length, split counts and the work-item table: on wave 0, which has no capsules of its own to append (the box wave took
@@ -2860,7 +2813,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
       if (lane == 0) sh[FS_NITEM * 64] = __int_as_float(tot_items);
     }
   }
-  PHASE_STAMP();   // 2: phase 2 done
+  st.mark<SG_BODY>(A, N, wv, e, PH_2);
   __syncthreads();
 
   // ---- phases 3 and 4 (general path): rows of the hand contacts, then the block-parallel sweeps -- general_contact_phases
@@ -2897,7 +2850,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
       FLD(wgen, 0) = DEXSIM_WGEN_NEXT(gen);
       if (last) solve_forces_box(A, P, ccnt, s_lam, nbg, lane, N, e, NR);
     }
-    PHASE_STAMP(); PHASE_STAMP();   // keep the stamp slots aligned
+    st.mark<SG_BODY>(A, N, wv, e, PH_3_ROWS); st.mark<SG_BODY>(A, N, wv, e, PH_4_SWEEPS);   // (phases 3 and 4 are empty on this path)
     __syncthreads();                // u_B and the box twist are read by every wave in phase 5
   }
   if (gp) {
@@ -2922,18 +2875,13 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     for (int i = 0; i < 24; i++) Gkeep[i] = 0.f;   // (not live through phases 3-4: this path reads G_f back from the arena)
     unsigned long long pr_t3 = 0;
     if (T.probe && wv == 0) pr_t3 = __builtin_amdgcn_s_memtime();
-#ifdef DEXSIM_PROFILE_PHASES
-    general_contact_phases(P, N, wv, lane, e, t_start, stamp_base, T.probe);
-    stamp_i += 2;
-#else
-    general_contact_phases(P, N, wv, lane, e, 0ull, 0, T.probe);
-#endif
+    general_contact_phases(P, N, wv, lane, e, st, T.probe);
     if (T.probe && wv == 0 && lane == 0) {
       atomicAdd(T.probe + blockIdx.x * 4, (unsigned)(__builtin_amdgcn_s_memtime() - pr_t3));
       atomicAdd(T.probe + blockIdx.x * 4 + 2, 1u);
     }
   } else if (early) {
-    PHASE_STAMP(); PHASE_STAMP();   // keep the stamp slots aligned
+    st.mark<SG_BODY>(A, N, wv, e, PH_3_ROWS); st.mark<SG_BODY>(A, N, wv, e, PH_4_SWEEPS);   // (phases 3 and 4 are empty on this path)
   }
 
   // ---- phase 5: back-substitution qd = L^-1 u, semi-implicit Euler, joint-limit clamp; forces
@@ -2982,16 +2930,14 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   }
   if (last && wv < 5 && gp) forces_reduce(A, ccnt, s_hdr, sh + FS_FORCE * 64, nc, lane, N, e, NR, wv, 5);
   if (last && wv == 5 && gp) contact_stats(ccnt, s_hdr, nc, lane, e, NR);
-  PHASE_STAMP();   // 5: phase 5 done
+  st.mark<SG_BODY>(A, N, wv, e, PH_5);
   }
   if (LAST) {
     __syncthreads();   // the publication reads the state written above by the other waves of the workgroup
     publish_body(A, T, P, 0, N, NR, 6);
     if (post_pre && wv == 6) post_pre_tasks(A, P, cnt, sh, N);
-    PHASE_STAMP();   // 6: publication done
+    st.mark<SG_BODY>(A, N, wv, e, PH_PUBLISH);
   }
-#undef PHASE_STAMP
-#undef PH2_STAMP
 }
 
 DI void reset_phase1(const Arena& A, int N, int e);                                      // dexsim_l2.hip.inc
@@ -3046,13 +2992,13 @@ __global__ __launch_bounds__(448) void k_physics4(Arena A, ApiPtrs T, const DevP
   __syncthreads();   // targets are read by every wave of the first sub-step
   if (!GATED || cnt[CNT_ANY_RESET] == T.stamp) {
     SubstepCarry K;
-    substep_body<false, MS>(P->arena, T, P, cnt, N, NR, sh, 1, 64, false, true, K, false, true);    // stamp_base: rows of the diagnostic cycle stamps (profile build only)
+    substep_body<false, MS>(P->arena, T, P, cnt, N, NR, sh, 1, Stamps::begin(1), false, true, K, false, true);
     __syncthreads();
-    substep_body<false, MS>(P->arena, T, P, cnt, N, NR, sh, 2, 128, false, true, K, true, true);
+    substep_body<false, MS>(P->arena, T, P, cnt, N, NR, sh, 2, Stamps::begin(2), false, true, K, true, true);
     __syncthreads();
-    substep_body<false, MS>(P->arena, T, P, cnt, N, NR, sh, 3, 192, false, true, K, true, true);
+    substep_body<false, MS>(P->arena, T, P, cnt, N, NR, sh, 3, Stamps::begin(3), false, true, K, true, true);
     __syncthreads();
-    substep_body<true, MS>(P->arena, T, P, cnt, N, NR, sh, 4, 256, !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, true, false);
+    substep_body<true, MS>(P->arena, T, P, cnt, N, NR, sh, 4, Stamps::begin(4), !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, true, false);
     if (!GATED && (tail & TAIL_POST)) {
       __syncthreads();     // publication (site poses, hand twist) -> observations; LDS changes hands
       post_block(P->arena, T, P, cnt, sh, 0, 1, N, NR, POST_PRE_MASK);
@@ -3076,7 +3022,7 @@ __global__ __launch_bounds__(448) void k_physics1(Arena A, ApiPtrs T, const DevP
   __syncthreads();
   if (!GATED || cnt[CNT_ANY_RESET] == T.stamp) {
     SubstepCarry K;   // (a single body: nothing carried)
-    substep_body<true, MS>(P->arena, T, P, cnt, N, NR, sh, 1, 0, !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, false, false);
+    substep_body<true, MS>(P->arena, T, P, cnt, N, NR, sh, 1, Stamps::begin(0), !GATED && (tail & TAIL_POST), !GATED && !(tail & TAIL_NOT_FINAL), K, false, false);
     if (!GATED && (tail & TAIL_POST)) {
       __syncthreads();
       post_block(P->arena, T, P, cnt, sh, 0, 1, N, NR, POST_PRE_MASK);
