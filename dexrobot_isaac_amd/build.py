@@ -3,27 +3,27 @@ so that it travels with the repo snapshot and shows up as loaded native code."""
 import os
 import shutil
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdexsim.so")
-SOURCES = ["dexsim.hip", "dexsim_device.h", "dexsim_stamps.h", "dexsim_physics.hip.inc", "dexsim_l2.hip.inc", "dexsim_state.hip.inc",
-           "dexsim_chain.hip.inc", "dexsim_render.hip.inc", "dexsim_kindyn.hip.inc", "dexsim_ik.hip.inc", "dexsim_proximity.hip.inc",
-           "dexsim_invdyn.hip.inc", "dexsim_fwddyn.hip.inc", "dexsim_dynderiv.hip.inc"]
+ABI_HEADER = os.path.join(HERE, "..", "include", "dexsim.h")
+_SHARED = ["dexsim_device.h", "dexsim_host.h"]
+# The library's two translation units, in link order: name -> (source, the files of csrc/ that its compile reads besides).  Neither
+# includes a .hip.inc of the other: the step kernels' code cannot depend on a query file, and a query edit does not recompile them.
+SOURCES = {
+    "step": ("dexsim.hip", [*_SHARED, "dexsim_stamps.h", "dexsim_physics.hip.inc", "dexsim_l2.hip.inc", "dexsim_state.hip.inc"]),
+    "queries": ("dexsim_queries.hip", [*_SHARED, "dexsim_chain.hip.inc", "dexsim_render.hip.inc", "dexsim_kindyn.hip.inc",
+                                       "dexsim_ik.hip.inc", "dexsim_proximity.hip.inc", "dexsim_invdyn.hip.inc",
+                                       "dexsim_fwddyn.hip.inc", "dexsim_dynderiv.hip.inc"]),
+}
 
 
 DEBUG_SPIN_LIB = os.path.join(HERE, "libdexsim_dbgspin.so")
 # the code-generation flags of the library (reasons: build_lib); tests that compile device code of the library stand-alone use the same
 CODEGEN_FLAGS = ["--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
                  "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-std=c++17"]
-
-
-def _stale(lib=LIB):
-    if not os.path.exists(lib):
-        return True
-    t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(HERE, "..", "include", "dexsim.h")]
-    return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
 def build_debug_spin(force=False, bound=2000000):
@@ -49,9 +49,18 @@ def build_profile(detail=None, extra_defs=(), out=PROFILE_LIB, force=True):
 
 
 def build_lib(force=False, verbose=False, defs=(), out=None):
-    """hipcc --offload-arch=gfx950 (cross-compiles without a GPU).  Returns the path of the library."""
+    """hipcc --offload-arch=gfx950 (cross-compiles without a GPU): each unit of SOURCES to an object next to the library
+    (libdexsim.step.o, libdexsim.queries.o), both at once, then one link.  Without `force` a unit is compiled only if its object is
+    missing or older than one of its files, and a library newer than every file of both units is left alone whether or not the
+    objects are still there.  Objects do not remember their defines: every caller that passes `defs` passes `force`.  Returns
+    the path of the library."""
     lib = out or LIB
-    if not force and not _stale(lib):
+    units = []   # (source, object, newest modification time of what the compile reads)
+    for name, (src, deps) in SOURCES.items():
+        files = [os.path.join(CSRC, f) for f in (src, *deps)] + [ABI_HEADER]
+        newest = max(os.path.getmtime(f) for f in files if os.path.exists(f))
+        units.append((os.path.join(CSRC, src), f"{os.path.splitext(lib)[0]}.{name}.o", newest))
+    if not force and os.path.exists(lib) and all(t <= os.path.getmtime(lib) for _, _, t in units):
         return lib
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
@@ -67,10 +76,17 @@ def build_lib(force=False, verbose=False, defs=(), out=None):
     # -mllvm -amdgpu-sched-strategy=max-ilp: the step kernel is a few long dependency chains on waves that are (almost) alone on
     # their SIMD, so the scheduler should interleave independent chains rather than minimise register pressure: same VGPR
     # counts, still no spills / scratch, 61.3 -> 62.2 M env-steps/s (contact-rich regime 187 -> 189 us: within 1 %).
-    cmd = [hipcc, *CODEGEN_FLAGS, "-fPIC", "-shared", *defs, "-o", lib, os.path.join(CSRC, "dexsim.hip")]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd, cwd=CSRC)
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd, cwd=CSRC)
+
+    compiles = [[hipcc, *CODEGEN_FLAGS, "-fPIC", *defs, "-c", "-o", obj, src]
+                for src, obj, t in units if force or not os.path.exists(obj) or os.path.getmtime(obj) < t]
+    with ThreadPoolExecutor(len(SOURCES)) as pool:
+        list(pool.map(run, compiles))
+    # the library is missing or older than a file of a unit, hence older than that unit's object: always link
+    run([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", lib, *(obj for _, obj, _ in units)])
     return lib
 
 

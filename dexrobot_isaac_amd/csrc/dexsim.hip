@@ -1,10 +1,15 @@
-// dexsim.hip -- libdexsim: C-ABI (include/dexsim.h) over the gfx950 kernels.
+// dexsim.hip -- libdexsim's step unit: the C-ABI (include/dexsim.h) of the simulation itself over the gfx950 step kernels
+// (dexsim_physics, dexsim_l2, dexsim_state), and the library's one error record.
 //
-// Build: hipcc --offload-arch=gfx950 -O3 -fPIC -shared -o libdexsim.so dexsim.hip
+// The library is two translation units, this one and dexsim_queries.hip (the query kernels and their entry points), and neither
+// includes the other's .hip.inc files: the step kernels' code is a function of this unit alone, whatever the query unit gains,
+// and an edit of a query file does not recompile them.  What both need is in dexsim_device.h and dexsim_host.h.
+// Build (build.py): hipcc <CODEGEN_FLAGS> -fPIC -c each unit, then hipcc --offload-arch=gfx950 -fPIC -shared -o libdexsim.so
+// the two objects, this unit's first.
 // No torch types, no CUDA shims, no dual back-end: this file only targets CDNA4 through HIP.
 #include <cmath>
 #include <algorithm>
-#include "dexsim_device.h"
+#include "dexsim_host.h"
 #include "dexsim_stamps.h"
 
 #include <cstdio>
@@ -26,50 +31,19 @@ static_assert(lds_map_conflict({0, (int)((POST_LDS_BYTES + 64 * sizeof(float) - 
 
 static thread_local std::string g_last_error;
 
-static int fail(int code, const char* what) {
+// the error record's two writers (dexsim_host.h), shared with the query unit
+int fail(int code, const char* what) {
   g_last_error = what ? what : "";
   return code;
 }
-#define HIP_TRY(expr)                                                                 \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    if (_e != hipSuccess) {                                                           \
-      g_last_error = std::string(#expr) + ": " + hipGetErrorString(_e);               \
-      return DEXSIM_ERR_HIP;                                                          \
-    }                                                                                 \
-  } while (0)
-
-struct DexSim {
-  DexSimConfig cfg;
-  DexHandModel model;
-  int device;
-  int N;  // real envs
-  int NS; // padded to a multiple of 64: arena stride, every lane of every wavefront owns an env
-  DevParams* d_params;
-  Arena arena;
-  ApiPtrs api;
-  bool bound;
-  bool model_struct;           // the model has the structure of the specialised chain forms: the MS step kernels (dexsim_create)
-  hipEvent_t ev0, ev1;
-  const float* last_actions;   // device pointer of the last dexsim_step (DEXSIM_STAGE_STEP re-launches the same kernel)
-  hipEvent_t tev[128];         // dexsim_step_timing: ring of 64 (start, stop) pairs
-  int timing;                  // 0 = off, else 1 + number of steps recorded since it was switched on
-};
-
-static int padded(int n) { return (n + 63) / 64 * 64; }
+int fail_hip(const char* expr, hipError_t e) {
+  g_last_error = std::string(expr) + ": " + hipGetErrorString(e);
+  return DEXSIM_ERR_HIP;
+}
 
 // A new control step begins: new stamp for the device-side reset gate and the parity of the contact statistics (CNT_ANY_RESET,
 // CNT_CONTACTS in dexsim_device.h).  Never 0 (the counters block is zero-initialised).
 static void next_stamp(DexSim* h) { h->api.stamp = h->api.stamp >= 0x3ffffffe ? 1 : h->api.stamp + 1; }
-
-// Every entry point runs on the handle's device whatever the caller's current device is, and restores the caller's.
-struct DeviceGuard {
-  int prev = -1; bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-};
 
 static const char* const kObsKeyNames[] = {
 #define X(name, dim) #name,
@@ -340,12 +314,7 @@ int dexsim_bind(dexsim_t h, const DexSimBuffers* b) {
   return DEXSIM_OK;
 }
 
-#define NEED_BOUND(h)                                                        \
-  if (!(h)) return fail(DEXSIM_ERR_ARG, "null handle");                      \
-  if (!(h)->bound) return fail(DEXSIM_ERR_NOT_BOUND, "dexsim_bind has not been called"); \
-  DeviceGuard _device_guard((h)->device)
 #define GRID(h) dim3((h)->NS / 64), dim3(64), 0, (hipStream_t)stream
-#define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
 
 static int launch_publish(dexsim_t h, int full, void* stream) {
   k_publish<<<dim3(h->NS / 64), dim3(384), 0, (hipStream_t)stream>>>(h->arena, h->api, h->d_params, h->api.counters, full, h->NS, h->N);
@@ -690,8 +659,7 @@ extern "C" int dexsim_state_layout(const DexSimConfig* cfg, DexSimField* fields,
   return DEXSIM_OK;
 }
 
-// The three kernels of the family.  Named here, behind every use of the step kernels, so that the compiler also emits them behind
-// the step kernels: the code object keeps the step path's kernels where they were.
+// The three kernels of the family.
 static constexpr auto k_state_save = &k_state_xfer<ST_SAVE>;   // instance -> bank
 static constexpr auto k_state_load = &k_state_xfer<ST_LOAD>;   // bank -> instance
 static constexpr auto k_state_copy = &k_state_xfer<ST_COPY>;   // instance -> instance (fork)
@@ -769,389 +737,5 @@ extern "C" int dexsim_set_step_stamp(dexsim_t h, int stamp) {
   if (!h) return fail(DEXSIM_ERR_ARG, "null handle");
   if (stamp < 1 || stamp > 0x3ffffffe) return fail(DEXSIM_ERR_ARG, "dexsim_set_step_stamp: the stamp must be in [1, 0x3ffffffe]");
   h->api.stamp = stamp;
-  return DEXSIM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------- camera sensors
-// Templates instantiated here, behind every use of the step kernels, so that the code object keeps the step path's kernels where
-// they were (like the state kernels above).
-// clang-format off
-#include "dexsim_chain.hip.inc"
-#include "dexsim_render.hip.inc"
-// clang-format on
-
-extern "C" int dexsim_camera_struct_size(size_t* out) {
-  if (!out) return fail(DEXSIM_ERR_ARG, "dexsim_camera_struct_size: null argument");
-  *out = sizeof(DexSimCamera);
-  return DEXSIM_OK;
-}
-
-extern "C" int dexsim_render_layout(DexSimField* fields, int max_fields, int* n_fields, size_t* scene_words) {
-  if (!n_fields || !scene_words) return fail(DEXSIM_ERR_ARG, "dexsim_render_layout: bad argument");
-  int n = 0, end = 0;
-  for (const RenderSection& s : kRenderSections) {
-    if (fields) {
-      if (n >= max_fields) return fail(DEXSIM_ERR_LAYOUT, "field table too small");
-      std::snprintf(fields[n].name, sizeof fields[n].name, "%s", s.name);
-      fields[n].rows = s.words; fields[n].is_int = s.is_int; fields[n].offset = (size_t)s.off;
-    }
-    end = s.off + s.words;
-    n++;
-  }
-  *n_fields = n;
-  *scene_words = (size_t)end;
-  return DEXSIM_OK;
-}
-
-extern "C" int dexsim_render(dexsim_t h, const DexSimCamera* cam, const float* eye, const float* target, const int64_t* env_ids, int k,
-                             float* scene, float* depth, uint8_t* rgba, int32_t* seg, void* stream) {
-  if (!h || !h->bound) return fail(DEXSIM_ERR_ARG, "dexsim_render: null or unbound handle");
-  if (!cam || !scene) return fail(DEXSIM_ERR_ARG, "dexsim_render: camera and scene workspace are required");
-  if (!depth && !rgba && !seg) return fail(DEXSIM_ERR_ARG, "dexsim_render: at least one of depth, rgba and seg is required");
-  if (((uintptr_t)scene & 15) != 0 || ((uintptr_t)rgba & 3) != 0)
-    return fail(DEXSIM_ERR_ARG, "dexsim_render: the scene workspace must be 16-byte aligned, rgba 4-byte aligned");
-  if (cam->width < 1 || cam->width > DEXSIM_RENDER_MAX_DIM || cam->height < 1 || cam->height > DEXSIM_RENDER_MAX_DIM)
-    return fail(DEXSIM_ERR_ARG, "dexsim_render: width and height must be in [1, 4096]");
-  if (!(cam->hfov_deg > 0.f && cam->hfov_deg < 180.f)) return fail(DEXSIM_ERR_ARG, "dexsim_render: hfov_deg must be in (0, 180)");
-  if (!(cam->near_clip < cam->far_clip)) return fail(DEXSIM_ERR_ARG, "dexsim_render: near_clip must be below far_clip");
-  if (cam->parent_joint < -1 || cam->parent_joint >= DEXSIM_NJ) return fail(DEXSIM_ERR_ARG, "dexsim_render: parent_joint out of range");
-  if (!env_ids) k = h->N;
-  if (k < 0) return fail(DEXSIM_ERR_ARG, "dexsim_render: k must not be negative");
-  const long long npix = (long long)cam->width * cam->height;
-  if ((long long)k * npix >= (1ll << 31)) return fail(DEXSIM_ERR_ARG, "dexsim_render: k * width * height must stay below 2^31");
-  if (k == 0) return DEXSIM_OK;
-  DeviceGuard guard(h->device);
-  RenderArgs R;
-  R.cam = *cam; R.eye = eye; R.target = target; R.env_ids = env_ids; R.k = k; R.img0 = 0;
-  const double t = std::tan(0.5 * (double)cam->hfov_deg * 3.14159265358979323846 / 180.0);
-  R.tan_x = (float)t; R.tan_y = (float)(t * (double)cam->height / (double)cam->width);
-  auto* ks = cam->parent_joint >= 0 ? k_render_scene<true> : k_render_scene<false>;
-  auto* kr = h->cfg.has_box ? k_render_rays<true> : k_render_rays<false>;
-  ks<<<dim3((k + 63) / 64), dim3(64), 0, (hipStream_t)stream>>>(h->d_params, R, scene, h->NS, h->N);
-  LAUNCH_CHECK();
-  const RayOut O{depth, (unsigned*)rgba, (int*)seg};
-  const int ymax = 32768;   // images per launch (extent of the grid's y dimension)
-  for (int i0 = 0; i0 < k; i0 += ymax) {
-    R.img0 = i0;
-    kr<<<dim3((unsigned)((npix + 255) / 256), (unsigned)std::min(ymax, k - i0)), dim3(256), 0, (hipStream_t)stream>>>(scene, R, O, h->N);
-    LAUNCH_CHECK();
-  }
-  return DEXSIM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------- Jacobians, mass matrix, gravity force
-// Behind every use of the step kernels, like the state and camera kernels above.
-// clang-format off
-#include "dexsim_kindyn.hip.inc"
-// clang-format on
-
-// The checks both entry points share; none of them needs a device.  k is the number of output rows.
-static int kin_rows(const char* who, dexsim_t h, const int64_t* env_ids, int k, const float* q, KinRows* R) {
-  if (!h) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": null handle").c_str());
-  if (k <= 0) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": k must be positive").c_str());
-  if (!q && !env_ids && k != h->N) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": env_ids == NULL without a q override needs k == num_envs").c_str());
-  R->env_ids = q ? nullptr : env_ids; R->q = q; R->k = k;
-  return DEXSIM_OK;
-}
-
-// a required output: non-NULL and `align`-byte aligned
-static int kin_out(const char* who, const char* name, const void* p, int align) {
-  if (p && ((uintptr_t)p & (uintptr_t)(align - 1)) == 0) return DEXSIM_OK;
-  return fail(DEXSIM_ERR_ARG, (std::string(who) + ": " + name + " must be a " + std::to_string(align) + "-byte aligned device pointer").c_str());
-}
-
-// A request of nb hand bodies (NULL = all of them, in order): the checks of the list, then of the output `name`, then that the
-// model's bodies ride on the frames kd_body_joint says.  body[i], where given, receives the i-th requested body.
-static int kin_bodies(const char* who, dexsim_t h, const int* bodies, int nb, unsigned char* body, const char* name, const void* out, int align) {
-  const std::string w(who);
-  if (nb < 1 || nb > DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, (w + ": nb must be in [1, DEXSIM_NUM_HAND_BODIES]").c_str());
-  if (!bodies && nb != DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, (w + ": bodies == NULL needs nb == DEXSIM_NUM_HAND_BODIES").c_str());
-  for (int i = 0; i < nb; i++) {
-    const int b = bodies ? bodies[i] : i;
-    if (b < 0 || b >= DEXSIM_NUM_HAND_BODIES) return fail(DEXSIM_ERR_ARG, (w + ": body index out of range").c_str());
-    if (body) body[i] = (unsigned char)b;
-  }
-  int rc = kin_out(who, name, out, align);
-  if (rc) return rc;
-  for (int b = 0; b < DEXSIM_NUM_HAND_BODIES; b++)
-    if (h->model.body_parent[b] != kd_body_joint(b))
-      return fail(DEXSIM_ERR_ARG, (w + ": model.body_parent differs from the frames rigid_body_states is published on").c_str());
-  return DEXSIM_OK;
-}
-
-// the family's grid: 64 rows per workgroup of KD_THREADS, `gy` workgroups along y
-#define KIN_LAUNCH(kernel, gy, args)                                                                                              \
-  kernel<<<dim3((unsigned)((k + 63) / 64), (unsigned)(gy)), dim3(KD_THREADS), 0, (hipStream_t)stream>>>(h->d_params, args, h->NS, h->N); \
-  LAUNCH_CHECK()
-
-extern "C" int dexsim_body_jacobian(dexsim_t h, const int64_t* env_ids, int k, const float* q, const int* bodies, int nb, float* jac,
-                                    void* stream) {
-  KinJac J;
-  std::memset(&J, 0, sizeof J);
-  int rc = kin_rows("dexsim_body_jacobian", h, env_ids, k, q, &J.rows);
-  if (rc) return rc;
-  rc = kin_bodies("dexsim_body_jacobian", h, bodies, nb, J.body, "jac", jac, 16);
-  if (rc) return rc;
-  NEED_BOUND(h);
-  J.jac = jac; J.nb = nb;
-  KIN_LAUNCH(k_kin_jacobian, (nb + KJ_CHUNK - 1) / KJ_CHUNK, J);
-  return DEXSIM_OK;
-}
-
-extern "C" int dexsim_mass_matrix(dexsim_t h, const int64_t* env_ids, int k, const float* q, float* mass, float* gravity, void* stream) {
-  KinMass K;
-  std::memset(&K, 0, sizeof K);
-  int rc = kin_rows("dexsim_mass_matrix", h, env_ids, k, q, &K.rows);
-  if (rc) return rc;
-  if (!mass && !gravity) return fail(DEXSIM_ERR_ARG, "dexsim_mass_matrix: at least one of mass and gravity is required");
-  if (((uintptr_t)mass & 15) != 0 || ((uintptr_t)gravity & 3) != 0)
-    return fail(DEXSIM_ERR_ARG, "dexsim_mass_matrix: mass must be 16-byte aligned, gravity 4-byte aligned");
-  NEED_BOUND(h);
-  K.mass = mass; K.gravity = gravity;
-  KIN_LAUNCH(k_kin_mass, 1, K);
-  return DEXSIM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------- fingertip inverse kinematics
-// Behind every use of the step kernels, like the kernels above.
-// clang-format off
-#include "dexsim_ik.hip.inc"
-// clang-format on
-
-extern "C" int dexsim_ik_struct_size(size_t* out) {
-  if (!out) return fail(DEXSIM_ERR_ARG, "dexsim_ik_struct_size: null argument");
-  *out = sizeof(DexSimIK);
-  return DEXSIM_OK;
-}
-
-extern "C" int dexsim_solve_ik(dexsim_t h, const int64_t* env_ids, int k, const float* q0, const float* targets, const DexSimIK* prm,
-                               float* controls, float* q_out, float* residual, void* stream) {
-  // the parameter checks need neither a handle nor a device
-  if (!targets || !controls || !prm) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: targets, controls and prm are required");
-  if (prm->sites < 0 || prm->sites > 1) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: sites must be 0 (fingertips) or 1 (fingerpads)");
-  if (prm->frame < 0 || prm->frame > 1) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: frame must be 0 (world) or 1 (hand)");
-  if (prm->free_mask == 0 || (prm->free_mask >> DEXSIM_NACT) != 0)
-    return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: free_mask must have at least one of its bits 0..17 set and none above");
-  if (prm->frame == 1 && (prm->free_mask & 63u) != 0)
-    return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: hand-frame targets (frame 1) need the base controls 0..5 fixed");
-  if (prm->iters < 1 || prm->iters > DEXSIM_IK_MAX_ITERS) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: iters must be in [1, DEXSIM_IK_MAX_ITERS]");
-  if (!(prm->damping > 0.f) || !std::isfinite(prm->damping)) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: damping must be positive");
-  if (!(prm->max_step > 0.f) || !std::isfinite(prm->max_step)) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: max_step must be positive");
-  float wsum = 0.f;
-  for (int f = 0; f < DEXSIM_NFINGER; f++) {
-    if (!(prm->weight[f] >= 0.f) || !std::isfinite(prm->weight[f])) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: a weight is negative");
-    wsum += prm->weight[f];
-  }
-  if (!(wsum > 0.f)) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: the weights are all zero");
-  if (k <= 0) return fail(DEXSIM_ERR_ARG, "dexsim_solve_ik: k must be positive");
-  IkArgs K;
-  std::memset(&K, 0, sizeof K);
-  int rc = kin_rows("dexsim_solve_ik", h, env_ids, k, q0, &K.rows);
-  if (rc) return rc;
-  NEED_BOUND(h);
-  K.targets = targets; K.controls = controls; K.q_out = q_out; K.residual = residual;
-  K.prm = *prm; K.lam2 = prm->damping * prm->damping;
-  KIN_LAUNCH(k_ik_solve, 1, K);
-  return DEXSIM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------- clearance queries
-// Behind every use of the step kernels, like the kernels above.
-// clang-format off
-#include "dexsim_proximity.hip.inc"
-// clang-format on
-
-// pair i of the pair table (include/dexsim.h), in the capsule order validate_model and dexsim_query_proximity insist on
-static void px_pair(int i, int* cap_a, int* cap_b, int* group) {
-  if (i < 90) {
-    const int g = i / 9, r = i - 9 * g;
-    *cap_a = px_finger_cap(px_group_fa(g), r / 3); *cap_b = px_finger_cap(px_group_fb(g), r % 3); *group = g;
-  } else {
-    const int j = i - 90, f = j / 6, r = j - 6 * f;
-    *cap_a = r / 2; *cap_b = px_finger_cap(f, 1 + r % 2); *group = 10 + f;
-  }
-}
-
-extern "C" int dexsim_proximity_pair(int i, int* cap_a, int* cap_b, int* group) {
-  if (!cap_a || !cap_b || !group) return fail(DEXSIM_ERR_ARG, "dexsim_proximity_pair: null argument");
-  if (i < 0 || i >= DEXSIM_NPROX_PAIRS) return fail(DEXSIM_ERR_ARG, "dexsim_proximity_pair: pair index out of range");
-  px_pair(i, cap_a, cap_b, group);
-  return DEXSIM_OK;
-}
-
-extern "C" int dexsim_query_proximity(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* box_pose, float box_size,
-                                      float* cap_env, float* self_min, float* pair_dist, void* stream) {
-  // the checks of the outputs, of box_size and of k need neither a handle nor a device
-  if (!cap_env && !self_min && !pair_dist)
-    return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: at least one of cap_env, self_min and pair_dist is required");
-  if (((uintptr_t)cap_env & 15) != 0 || ((uintptr_t)self_min & 15) != 0 || ((uintptr_t)pair_dist & 15) != 0)
-    return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: the outputs must be 16-byte aligned");
-  if (!std::isfinite(box_size)) return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: box_size is not finite");
-  if (k <= 0) return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: k must be positive");
-  ProxArgs K;
-  std::memset(&K, 0, sizeof K);
-  int rc = kin_rows("dexsim_query_proximity", h, env_ids, k, q, &K.rows);
-  if (rc) return rc;
-  for (int c = 0; c < DEXSIM_NCAP; c++)
-    if (h->model.cap_fslot[c] != (c < 3 ? DEXSIM_FSLOT_PALM : c - 3))
-      return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: the model must have exactly three palm capsules (0-2) and one capsule per finger "
-                                  "link (capsule 3 + s in force slot s)");
-  const float size = box_size > 0.f ? box_size : h->cfg.box_size;
-  K.box_pose = box_pose;
-  K.box_env = !box_pose && !q && h->cfg.has_box;
-  if ((K.box_pose || K.box_env) && !(size > 0.f))
-    return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: a box needs a positive box_size or cfg.box_size");
-  NEED_BOUND(h);
-  K.hb = 0.5f * size;
-  K.cap_env = cap_env; K.self_min = self_min; K.pair_dist = pair_dist;
-  KIN_LAUNCH(k_proximity, 1, K);
-  return DEXSIM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------- inverse dynamics, bias accelerations
-// Behind every use of the step kernels, like the kernels above.
-// clang-format off
-#include "dexsim_invdyn.hip.inc"
-// clang-format on
-
-// kin_rows plus the rule of the velocity override: q and qd are both NULL (arena) or both (k, 26) overrides
-static int kin_rows_qd(const char* who, dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, KinRows* R) {
-  int rc = kin_rows(who, h, env_ids, k, q, R);
-  if (rc) return rc;
-  if (!q != !qd) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": q and qd must both be NULL (the envs' state) or both be (k, 26) overrides").c_str());
-  return DEXSIM_OK;
-}
-
-extern "C" int dexsim_inverse_dynamics(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const float* qdd,
-                                       int flags, float* tau, void* stream) {
-  InvDyn K;
-  std::memset(&K, 0, sizeof K);
-  int rc = kin_rows_qd("dexsim_inverse_dynamics", h, env_ids, k, q, qd, &K.rows);
-  if (rc) return rc;
-  if ((flags & ~DEXSIM_ID_GRAVITY) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_inverse_dynamics: unknown flag bits (DEXSIM_ID_GRAVITY is the only flag)");
-  if ((rc = kin_out("dexsim_inverse_dynamics", "tau", tau, 4))) return rc;
-  NEED_BOUND(h);
-  K.qd = qd; K.qdd = qdd; K.tau = tau; K.gravity = flags & DEXSIM_ID_GRAVITY;
-  KIN_LAUNCH(k_kin_invdyn, 1, K);
-  return DEXSIM_OK;
-}
-
-extern "C" int dexsim_body_bias_accel(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const int* bodies, int nb,
-                                      float* acc, void* stream) {
-  BiasAcc K;
-  std::memset(&K, 0, sizeof K);
-  int rc = kin_rows_qd("dexsim_body_bias_accel", h, env_ids, k, q, qd, &K.rows);
-  if (rc) return rc;
-  rc = kin_bodies("dexsim_body_bias_accel", h, bodies, nb, nullptr, "acc", acc, 4);
-  if (rc) return rc;
-  int n = 0;   // the request sorted by the frame a body rides on: -1 (the spawn frame), then the joints in order
-  for (int j = -1; j < DEXSIM_NJ; j++) {
-    K.jstart[j + 1] = (unsigned char)n;
-    for (int i = 0; i < nb; i++) {
-      const int b = bodies ? bodies[i] : i;
-      if (kd_body_joint(b) == j) { K.body[n] = (unsigned char)b; K.slot[n] = (unsigned char)i; n++; }
-    }
-  }
-  K.jstart[DEXSIM_NJ + 1] = (unsigned char)n;
-  NEED_BOUND(h);
-  K.qd = qd; K.acc = acc; K.nb = nb;
-  KIN_LAUNCH(k_kin_bias_accel, 1, K);
-  return DEXSIM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------- forward dynamics, mass-matrix solves
-// Behind the inverse dynamics: the kernel uses its Newton-Euler helpers.
-// clang-format off
-#include "dexsim_fwddyn.hip.inc"
-// clang-format on
-
-extern "C" int dexsim_forward_dynamics(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const float* tau,
-                                       int flags, float* qdd, void* stream) {
-  FwdDyn K;
-  std::memset(&K, 0, sizeof K);
-  int rc = kin_rows_qd("dexsim_forward_dynamics", h, env_ids, k, q, qd, &K.rows);
-  if (rc) return rc;
-  if ((flags & ~(DEXSIM_FD_GRAVITY | DEXSIM_FD_ARMATURE)) != 0)
-    return fail(DEXSIM_ERR_ARG, "dexsim_forward_dynamics: unknown flag bits (DEXSIM_FD_GRAVITY and DEXSIM_FD_ARMATURE are the flags)");
-  if ((rc = kin_out("dexsim_forward_dynamics", "qdd", qdd, 4))) return rc;
-  NEED_BOUND(h);
-  K.qd = qd; K.rhs = tau; K.out = qdd; K.nrhs = 1; K.gravity = flags & DEXSIM_FD_GRAVITY; K.armature = flags & DEXSIM_FD_ARMATURE;
-  KIN_LAUNCH(k_kin_fwddyn<true>, 1, K);
-  return DEXSIM_OK;
-}
-
-extern "C" int dexsim_mass_solve(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* rhs, int nrhs, int flags,
-                                 float* out, void* stream) {
-  FwdDyn K;
-  std::memset(&K, 0, sizeof K);
-  int rc = kin_rows("dexsim_mass_solve", h, env_ids, k, q, &K.rows);
-  if (rc) return rc;
-  if ((flags & ~DEXSIM_FD_ARMATURE) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: unknown flag bits (DEXSIM_FD_ARMATURE is the only flag)");
-  if (nrhs < 1 || nrhs > DEXSIM_MSOLVE_MAX_RHS) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: nrhs must be in [1, DEXSIM_MSOLVE_MAX_RHS]");
-  if (!rhs) return fail(DEXSIM_ERR_ARG, "dexsim_mass_solve: rhs must not be NULL");
-  if ((rc = kin_out("dexsim_mass_solve", "out", out, 4))) return rc;
-  NEED_BOUND(h);
-  K.rhs = rhs; K.out = out; K.nrhs = nrhs; K.armature = flags & DEXSIM_FD_ARMATURE;
-  KIN_LAUNCH(k_kin_fwddyn<false>, 1, K);
-  return DEXSIM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------- dynamics derivatives
-// Behind the forward dynamics: the forward route launches k_kin_fwddyn on either side of the derivative kernel.
-// clang-format off
-#include "dexsim_dynderiv.hip.inc"
-// clang-format on
-
-// the checks of the derivative outputs: at least one, each 4-byte aligned
-static int kin_deriv_outs(const char* who, const char* na, const float* a, const char* nb, const float* b) {
-  if (!a && !b) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": at least one of " + na + " and " + nb + " is required").c_str());
-  int rc;
-  if (a && (rc = kin_out(who, na, a, 4))) return rc;
-  if (b && (rc = kin_out(who, nb, b, 4))) return rc;
-  return DEXSIM_OK;
-}
-
-extern "C" int dexsim_inverse_dynamics_derivatives(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd,
-                                                   const float* qdd, int flags, float* dtau_dq, float* dtau_dqd, void* stream) {
-  IdDeriv K;
-  std::memset(&K, 0, sizeof K);
-  int rc = kin_rows_qd("dexsim_inverse_dynamics_derivatives", h, env_ids, k, q, qd, &K.rows);
-  if (rc) return rc;
-  if ((flags & ~DEXSIM_ID_GRAVITY) != 0)
-    return fail(DEXSIM_ERR_ARG, "dexsim_inverse_dynamics_derivatives: unknown flag bits (DEXSIM_ID_GRAVITY is the only flag)");
-  if ((rc = kin_deriv_outs("dexsim_inverse_dynamics_derivatives", "dtau_dq", dtau_dq, "dtau_dqd", dtau_dqd))) return rc;
-  NEED_BOUND(h);
-  K.qd = qd; K.qdd = qdd; K.dq = dtau_dq; K.dqd = dtau_dqd; K.gravity = flags & DEXSIM_ID_GRAVITY;
-  KIN_LAUNCH(k_kin_id_deriv<false>, 1, K);
-  return DEXSIM_OK;
-}
-
-// Three launches on the caller's stream: qdd, then -d tau / d (q, qd) at that qdd, then the mass solve of the 26 rows of each
-// derivative, in place.
-extern "C" int dexsim_forward_dynamics_derivatives(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd,
-                                                   const float* tau, int flags, float* qdd, float* dqdd_dq, float* dqdd_dqd, void* stream) {
-  FwdDyn F;
-  std::memset(&F, 0, sizeof F);
-  int rc = kin_rows_qd("dexsim_forward_dynamics_derivatives", h, env_ids, k, q, qd, &F.rows);
-  if (rc) return rc;
-  if ((flags & ~(DEXSIM_FD_GRAVITY | DEXSIM_FD_ARMATURE)) != 0)
-    return fail(DEXSIM_ERR_ARG,
-                "dexsim_forward_dynamics_derivatives: unknown flag bits (DEXSIM_FD_GRAVITY and DEXSIM_FD_ARMATURE are the flags)");
-  if ((rc = kin_out("dexsim_forward_dynamics_derivatives", "qdd", qdd, 4))) return rc;
-  if ((rc = kin_deriv_outs("dexsim_forward_dynamics_derivatives", "dqdd_dq", dqdd_dq, "dqdd_dqd", dqdd_dqd))) return rc;
-  NEED_BOUND(h);
-  F.qd = qd; F.rhs = tau; F.out = qdd; F.nrhs = 1; F.gravity = flags & DEXSIM_FD_GRAVITY; F.armature = flags & DEXSIM_FD_ARMATURE;
-  KIN_LAUNCH(k_kin_fwddyn<true>, 1, F);
-  IdDeriv K;
-  std::memset(&K, 0, sizeof K);
-  K.rows = F.rows; K.qd = qd; K.qdd = qdd; K.dq = dqdd_dq; K.dqd = dqdd_dqd; K.gravity = flags & DEXSIM_FD_GRAVITY;
-  KIN_LAUNCH(k_kin_id_deriv<true>, 1, K);
-  static_assert(DEXSIM_NJ <= DEXSIM_MSOLVE_MAX_RHS, "the mass solve takes a derivative's 26 rows in one call");
-  F.qd = nullptr; F.nrhs = DEXSIM_NJ; F.gravity = 0;
-  for (float* d : {dqdd_dq, dqdd_dqd}) {
-    if (!d) continue;
-    F.rhs = d; F.out = d;
-    KIN_LAUNCH(k_kin_fwddyn<false>, 1, F);
-  }
   return DEXSIM_OK;
 }

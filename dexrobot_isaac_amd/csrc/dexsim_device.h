@@ -81,6 +81,12 @@ struct Arena {
 #define DEXSIM_LAYOUT_ROWS 0
 #define DEXSIM_LAYOUT_QUAD 1
 
+// GPTR: view a pointer as global-address-space.  Field pointers that were loaded from memory (P->arena) are generic
+// to the compiler and would be accessed with FLAT instructions (vmcnt + lgkmcnt, aperture check); kernel-argument
+// copies are already known to be global, for them the cast is a no-op.
+#define GPTR(p) ((__attribute__((address_space(1))) __typeof__(*(p))*)(p))
+#define FLD(f, r) GPTR(A.f)[(size_t)(r) * N + e]
+
 // Quad layout (round 3): the per-finger factor hand-off -- fac_g (G_f, 24 words = 6 quads per finger), fac_finv (Fhat_f^-1 lower
 // triangle, 10 words in 3 quads per finger) and the finger part of jframe (axes + origins of the finger's 4 joints, 24 words = 6
 // quads per finger, behind the 36 row-layout words of the base joints) -- is stored [quad][env][4]: a lane moves four consecutive
@@ -150,6 +156,42 @@ struct DevParams {
 #define CNT_CONSECUTIVE 14 /* persistent */
 #define CNT_RC_FIRST 15    /* persistent: RewardCalculator lazy prev-state init pending */
 
+// the API tensors and per-launch words the host hands to the kernels by value (filled by dexsim_bind and the dexsim_set_* calls)
+struct ApiPtrs {
+  float* obs_buf; float* rew_buf; uint8_t* reset_buf; int64_t* episode_step_count; int64_t* episode_length;
+  float* dof_state; float* root_state; float* rigid_body_states; float* contact_forces_all; float* full_dof_targets;
+  const float* reset_samples;
+  uint8_t* masks; const float* raw_targets;
+  float* stats; int* counters;
+  // optional second destination of the step outputs (dexsim_set_step_sink): the caller's rollout-buffer slot, written by
+  // the same flush as obs_buf / rew_buf / reset_buf so that collecting a rollout costs no extra launch
+  float* sink_obs; float* sink_rew; uint8_t* sink_done;
+  float* sink_stats;     // optional copy of the step's statistics block (dexsim_set_stats_sink): row t of the rollout's (T, DEXSIM_STAT_WORDS) tensor
+  float* actions_copy;   // optional (N, num_actions) copy of the actions consumed by the step (dexsim_set_action_copy)
+  int skip_obs_all;      // dexsim_set_obs_dict_mode(1): the post block does not flush the 392 obs_all rows (the SoA rows behind obs_dict);
+                         // obs_buf -- the policy keys -- is unaffected
+  unsigned* probe;       // optional phase probe (dexsim_set_phase_probe): 4 words per workgroup, accumulated shader-clock ticks --
+                         // [0] phases 3 + 4 of the general contact path (rows + sweeps), [1] whole k_physics4 launches, [2] number of
+                         // sub-steps that ran the general path, [3] phase 4 alone (the sweeps)
+  int stamp;             // stamp of the current control step (see CNT_ANY_RESET)
+};
+
+// Coupling (constants.py:71-88): the DOFs that each of the 18 controls drives, in the reference's order, with their scales.
+// Controls 0-5 drive the base DOFs 0-5.  Every index is a compile-time constant in the unrolled loops that read the table.
+struct CouplingGroup { int n, dof[3]; float scale[3]; };
+constexpr CouplingGroup kCoupling[18] = {
+    {1, {0}, {1}}, {1, {1}, {1}}, {1, {2}, {1}}, {1, {3}, {1}}, {1, {4}, {1}}, {1, {5}, {1}},
+    {1, {6}, {1}},                          // thumb spread
+    {1, {7}, {1}},                          // thumb MCP
+    {2, {8, 9}, {1, 1}},                    // thumb DIP
+    {3, {10, 18, 22}, {1, 1, 2}},           // finger spread: r_f_joint5_1 (DOF 22) turns twice as far
+    {1, {11}, {1}}, {2, {12, 13}, {1, 1}},  // index MCP, DIP
+    {1, {15}, {1}}, {2, {16, 17}, {1, 1}},  // middle MCP, DIP
+    {1, {19}, {1}}, {2, {20, 21}, {1, 1}},  // ring MCP, DIP
+    {1, {23}, {1}}, {2, {24, 25}, {1, 1}},  // pinky MCP, DIP
+};
+constexpr int kHeldDof = 14;   // r_f_joint3_1 (middle spread): driven by no control, its target is held at 0
+
 // ------------------------------------------------------------------------------------------------- math
 typedef float f2 __attribute__((ext_vector_type(2)));   // maps onto the gfx950 packed-FP32 VALU ops
 typedef float f4 __attribute__((ext_vector_type(4)));   // 16-byte global accesses
@@ -208,6 +250,35 @@ DI float mulr(float a, float b) {
 // norm_n: |a| for a vector that is exactly zero or of model scale (a capsule axis): dot(a, a) zero or normal
 DI float norm_n(V3 a) { return sqrt_n(dot(a, a)); }
 DI float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// sphere (centre P in the box frame, radius r) against the solid box of half extent hb (cube)
+DI void sphere_box(V3 P, float r, float hb, V3& nl, V3& pl, float& gapraw) {
+  V3 qv = {clampf(P.x, -hb, hb), clampf(P.y, -hb, hb), clampf(P.z, -hb, hb)};
+  V3 d = P - qv;
+  float d2 = dot(d, d);
+  if (d2 > 1e-12f) {
+    float dist = sqrt_n(d2);   // d2 > 1e-12: dist > 1e-6, |d_i| <= dist
+    nl = {div_n(d.x, dist), div_n(d.y, dist), div_n(d.z, dist)};
+    pl = qv;
+    gapraw = dist - r;
+  } else {
+    float px = hb - fabsf(P.x), py = hb - fabsf(P.y), pz = hb - fabsf(P.z);
+    int ax = 0; float best = px;
+    if (py < best) { best = py; ax = 1; }
+    if (pz < best) { best = pz; ax = 2; }
+    float c = ax == 0 ? P.x : (ax == 1 ? P.y : P.z);
+    float sgn = c >= 0.f ? 1.f : -1.f;
+    nl = {ax == 0 ? sgn : 0.f, ax == 1 ? sgn : 0.f, ax == 2 ? sgn : 0.f};
+    pl = {ax == 0 ? sgn * hb : P.x, ax == 1 ? sgn * hb : P.y, ax == 2 ? sgn * hb : P.z};
+    gapraw = -best - r;
+  }
+}
+
+DI float seg_box_dfdt(V3 a, V3 d, float t, float hb) {
+  V3 Pt = {a.x + t * d.x, a.y + t * d.y, a.z + t * d.z};
+  V3 ex = {Pt.x - clampf(Pt.x, -hb, hb), Pt.y - clampf(Pt.y, -hb, hb), Pt.z - clampf(Pt.z, -hb, hb)};
+  return ex.x * d.x + ex.y * d.y + ex.z * d.z;
+}
 
 DI Q4 q4p(const float* p) { return {p[0], p[1], p[2], p[3]}; }
 DI Q4 qmul(Q4 a, Q4 b) { // xyzw Hamilton product

@@ -14,21 +14,6 @@
 //               stream instead of torch.rand (blind_grasping_task.py:449-547).
 //   k_finalize: the cross-env means / rates of TerminationManager.evaluate and consecutive successes.
 
-// Coupling (constants.py:71-88): the DOFs that each of the 18 controls drives, in the reference's order, with their scales.
-// Controls 0-5 drive the base DOFs 0-5.  Every index is a compile-time constant in the unrolled loops that read the table.
-struct CouplingGroup { int n, dof[3]; float scale[3]; };
-constexpr CouplingGroup kCoupling[18] = {
-    {1, {0}, {1}}, {1, {1}, {1}}, {1, {2}, {1}}, {1, {3}, {1}}, {1, {4}, {1}}, {1, {5}, {1}},
-    {1, {6}, {1}},                          // thumb spread
-    {1, {7}, {1}},                          // thumb MCP
-    {2, {8, 9}, {1, 1}},                    // thumb DIP
-    {3, {10, 18, 22}, {1, 1, 2}},           // finger spread: r_f_joint5_1 (DOF 22) turns twice as far
-    {1, {11}, {1}}, {2, {12, 13}, {1, 1}},  // index MCP, DIP
-    {1, {15}, {1}}, {2, {16, 17}, {1, 1}},  // middle MCP, DIP
-    {1, {19}, {1}}, {2, {20, 21}, {1, 1}},  // ring MCP, DIP
-    {1, {23}, {1}}, {2, {24, 25}, {1, 1}},  // pinky MCP, DIP
-};
-constexpr int kHeldDof = 14;   // r_f_joint3_1 (middle spread): driven by no control, its target is held at 0
 // HardwareMapping enum order -> primary DOF (hand_initializer.py:20-38, observation_encoder.py:496-574)
 constexpr int kActiveFingerDof[12] = {8, 7, 6, 10, 12, 11, 16, 15, 20, 19, 24, 23};
 

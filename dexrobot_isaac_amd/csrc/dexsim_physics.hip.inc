@@ -20,11 +20,6 @@
 // The arithmetic model is specified by oracle/dexsim_oracle.c (dense form); this file is its block-structured
 // MI355X implementation.
 
-// GPTR: view a pointer as global-address-space.  Field pointers that were loaded from memory (P->arena) are generic
-// to the compiler and would be accessed with FLAT instructions (vmcnt + lgkmcnt, aperture check); kernel-argument
-// copies are already known to be global, for them the cast is a no-op.
-#define GPTR(p) ((__attribute__((address_space(1))) __typeof__(*(p))*)(p))
-#define FLD(f, r) GPTR(A.f)[(size_t)(r) * N + e]
 // LDS row store of the contact solver: word w of the lane's row data lives at [w / 4][lane][w % 4], so that a lane reads
 // four consecutive row words with one 16-byte ds_read_b128 (conflict-free: 64 lanes x 16 B).  A contact's 3 x 28 words are
 // 21 LDS instructions instead of 84 -- a wave has at most 15 LDS instructions in flight, so the count sets the latency.
@@ -117,35 +112,6 @@ DI void push_contact(const Arena& A, int N, int e, int& nc, int type, int cap, i
   *FQ(cgeom, 2 * nc + 1) = f4{n.y, n.z, gap, mu};
   FLD(ccode, nc) = type | (cap << 2) | (sample << 7) | cinfo;
   nc++;
-}
-
-// sphere (centre P in the box frame, radius r) against the solid box of half extent hb (cube)
-DI void sphere_box(V3 P, float r, float hb, V3& nl, V3& pl, float& gapraw) {
-  V3 qv = {clampf(P.x, -hb, hb), clampf(P.y, -hb, hb), clampf(P.z, -hb, hb)};
-  V3 d = P - qv;
-  float d2 = dot(d, d);
-  if (d2 > 1e-12f) {
-    float dist = sqrt_n(d2);   // d2 > 1e-12: dist > 1e-6, |d_i| <= dist
-    nl = {div_n(d.x, dist), div_n(d.y, dist), div_n(d.z, dist)};
-    pl = qv;
-    gapraw = dist - r;
-  } else {
-    float px = hb - fabsf(P.x), py = hb - fabsf(P.y), pz = hb - fabsf(P.z);
-    int ax = 0; float best = px;
-    if (py < best) { best = py; ax = 1; }
-    if (pz < best) { best = pz; ax = 2; }
-    float c = ax == 0 ? P.x : (ax == 1 ? P.y : P.z);
-    float sgn = c >= 0.f ? 1.f : -1.f;
-    nl = {ax == 0 ? sgn : 0.f, ax == 1 ? sgn : 0.f, ax == 2 ? sgn : 0.f};
-    pl = {ax == 0 ? sgn * hb : P.x, ax == 1 ? sgn * hb : P.y, ax == 2 ? sgn * hb : P.z};
-    gapraw = -best - r;
-  }
-}
-
-DI float seg_box_dfdt(V3 a, V3 d, float t, float hb) {
-  V3 Pt = {a.x + t * d.x, a.y + t * d.y, a.z + t * d.z};
-  V3 ex = {Pt.x - clampf(Pt.x, -hb, hb), Pt.y - clampf(Pt.y, -hb, hb), Pt.z - clampf(Pt.z, -hb, hb)};
-  return ex.x * d.x + ex.y * d.y + ex.z * d.z;
 }
 
 // one capsule against the box (closest point of the axis + its far end, as sample spheres) and the ground (both ends)
@@ -1781,25 +1747,6 @@ __global__ __launch_bounds__(64) void k_solve(Arena A, const DevParams* __restri
 }
 
 // ------------------------------------------------------------------------------------------------- publish
-struct ApiPtrs {
-  float* obs_buf; float* rew_buf; uint8_t* reset_buf; int64_t* episode_step_count; int64_t* episode_length;
-  float* dof_state; float* root_state; float* rigid_body_states; float* contact_forces_all; float* full_dof_targets;
-  const float* reset_samples;
-  uint8_t* masks; const float* raw_targets;
-  float* stats; int* counters;
-  // optional second destination of the step outputs (dexsim_set_step_sink): the caller's rollout-buffer slot, written by
-  // the same flush as obs_buf / rew_buf / reset_buf so that collecting a rollout costs no extra launch
-  float* sink_obs; float* sink_rew; uint8_t* sink_done;
-  float* sink_stats;     // optional copy of the step's statistics block (dexsim_set_stats_sink): row t of the rollout's (T, DEXSIM_STAT_WORDS) tensor
-  float* actions_copy;   // optional (N, num_actions) copy of the actions consumed by the step (dexsim_set_action_copy)
-  int skip_obs_all;      // dexsim_set_obs_dict_mode(1): the post block does not flush the 392 obs_all rows (the SoA rows behind obs_dict);
-                         // obs_buf -- the policy keys -- is unaffected
-  unsigned* probe;       // optional phase probe (dexsim_set_phase_probe): 4 words per workgroup, accumulated shader-clock ticks --
-                         // [0] phases 3 + 4 of the general contact path (rows + sweeps), [1] whole k_physics4 launches, [2] number of
-                         // sub-steps that ran the general path, [3] phase 4 alone (the sweeps)
-  int stamp;             // stamp of the current control step (see CNT_ANY_RESET)
-};
-
 DI void store_pose(const Arena& A, int N, int e, int s, V3 p, Q4 q) {
   FLD(site_pose, 7 * s + 0) = p.x; FLD(site_pose, 7 * s + 1) = p.y; FLD(site_pose, 7 * s + 2) = p.z;
   FLD(site_pose, 7 * s + 3) = q.x; FLD(site_pose, 7 * s + 4) = q.y; FLD(site_pose, 7 * s + 5) = q.z;

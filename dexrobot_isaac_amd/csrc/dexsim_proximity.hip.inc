@@ -22,7 +22,7 @@
 //                      crosses +-hb.  f' is evaluated at 0, 1 and the six (clamped) breakpoints; the largest t with f' < 0 and the
 //                      smallest with f' >= 0 bracket a piece on which f' is linear: one interpolation gives the minimiser, and the
 //                      start of a flat stretch (always a breakpoint, or 0) when the minimum is not unique.  No iteration, no
-//                      branch.  The distance itself is sphere_box (dexsim_physics.hip.inc) at that point, or, where the axis
+//                      branch.  The distance itself is sphere_box (dexsim_device.h) at that point, or, where the axis
 //                      meets the cube, at the midpoint of the stretch inside it (slab clipping).
 //   capsule / capsule  clamped closest points of two segments, the standard two-stage clamping.
 

@@ -80,8 +80,14 @@ def test_build_profile_command_line(monkeypatch, tmp_path):
     assert build.build_profile(detail="PH2", out=out) == out
     tails = [["-DDEXSIM_PROFILE_PHASES", "-DDEXSIM_PROFILE_DETAIL=SCHUR|SWEEP05", "-DEXP_X=1"], ["-DDEXSIM_PROFILE_PHASES"],
              ["-DDEXSIM_PROFILE_PHASES", "-DDEXSIM_PROFILE_DETAIL=PH2"]]
-    assert len(calls) == 3
-    for (cmd, kw), defs in zip(calls, tails):
-        assert os.path.basename(cmd[0]) == "hipcc"
-        assert cmd[1:] == [*build.CODEGEN_FLAGS, "-fPIC", "-shared", *defs, "-o", out, os.path.join(build.CSRC, "dexsim.hip")]
+    objs = [f"{out[:-len('.so')]}.{name}.o" for name in build.SOURCES]
+    srcs = [os.path.join(build.CSRC, src) for src, _ in build.SOURCES.values()]
+    per_build = len(srcs) + 1   # one compile per unit (both at once: in either order), then the link
+    assert len(calls) == 3 * per_build
+    for i, defs in enumerate(tails):
+        *compiles, link = [cmd for cmd, kw in calls[per_build * i:per_build * (i + 1)]]
+        assert all(os.path.basename(cmd[0]) == "hipcc" for cmd in (*compiles, link))
+        assert sorted(cmd[1:] for cmd in compiles) == sorted([*build.CODEGEN_FLAGS, "-fPIC", *defs, "-c", "-o", obj, src]
+                                                             for obj, src in zip(objs, srcs))
+        assert link[1:] == ["--offload-arch=gfx950", "-fPIC", "-shared", "-o", out, *objs]
     assert os.path.abspath(build.PROFILE_LIB).startswith(os.path.join(ROOT, "build_variants") + os.sep)   # default: never next to the package
