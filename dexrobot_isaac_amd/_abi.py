@@ -136,83 +136,71 @@ class DexSimIK(C.Structure):
                 ("weight", f32 * NFINGER)]
 
 
-# every symbol include/dexsim.h declares (checked by tests/test_abi.py against the built library)
-EXPORTED_SYMBOLS = [
-    "dexsim_struct_sizes", "dexsim_arena_layout", "dexsim_obs_key_info", "dexsim_reward_term_name",
-    "dexsim_body_name", "dexsim_create", "dexsim_destroy", "dexsim_bind", "dexsim_init_state",
-    "dexsim_process_actions", "dexsim_begin_step", "dexsim_physics_step", "dexsim_post_physics", "dexsim_step",
-    "dexsim_reset_idx", "dexsim_reset", "dexsim_refresh_body_states", "dexsim_set_dof_state_indexed",
-    "dexsim_set_root_state_indexed", "dexsim_run_stage", "dexsim_time_stage", "dexsim_step_timing", "dexsim_set_step_sink", "dexsim_set_stats_sink", "dexsim_set_phase_probe", "dexsim_set_obs_dict_mode", "dexsim_set_action_copy", "dexsim_error_string",
-    "dexsim_last_error",
-    "dexsim_state_layout", "dexsim_save_state", "dexsim_load_state", "dexsim_copy_envs", "dexsim_get_step_stamp",
-    "dexsim_set_step_stamp",
-    "dexsim_camera_struct_size", "dexsim_render_layout", "dexsim_render",
-    "dexsim_body_jacobian", "dexsim_mass_matrix",
-    "dexsim_ik_struct_size", "dexsim_solve_ik",
-    "dexsim_proximity_pair", "dexsim_query_proximity",
-    "dexsim_inverse_dynamics", "dexsim_body_bias_accel",
-    "dexsim_forward_dynamics", "dexsim_mass_solve",
-    "dexsim_inverse_dynamics_derivatives", "dexsim_forward_dynamics_derivatives",
-]
+P, vp, sz, i64 = C.POINTER, C.c_void_p, C.c_size_t, C.c_int64
+
+# every entry point include/dexsim.h declares and its argument types, in header order (tests/test_abi.py holds the names
+# against the built library and the number of arguments against the header's declarations)
+PROTOTYPES = {
+    "dexsim_struct_sizes": [P(sz)],
+    "dexsim_arena_layout": [P(DexSimConfig), P(DexSimField), i32, P(i32), P(sz)],
+    "dexsim_obs_key_info": [i32, P(C.c_char_p), P(i32), P(i32)],
+    "dexsim_reward_term_name": [i32, P(C.c_char_p)],
+    "dexsim_body_name": [i32, P(C.c_char_p)],
+    "dexsim_create": [P(DexSimConfig), P(DexHandModel), i32, P(vp)],
+    "dexsim_destroy": [vp],
+    "dexsim_bind": [vp, P(DexSimBuffers)],
+    "dexsim_init_state": [vp, vp],
+    "dexsim_process_actions": [vp, vp, i32, vp],
+    "dexsim_begin_step": [vp, vp],
+    "dexsim_physics_step": [vp, i32, vp],
+    "dexsim_post_physics": [vp, i32, vp],
+    "dexsim_step": [vp, vp, vp],
+    "dexsim_reset_idx": [vp, vp, i32, vp],
+    "dexsim_reset": [vp, vp],
+    "dexsim_refresh_body_states": [vp, vp],
+    "dexsim_set_dof_state_indexed": [vp, vp, i32, vp],
+    "dexsim_set_root_state_indexed": [vp, vp, i32, vp],
+    "dexsim_set_step_sink": [vp, vp, vp, vp],
+    "dexsim_set_stats_sink": [vp, vp],
+    "dexsim_set_obs_dict_mode": [vp, i32],
+    "dexsim_set_phase_probe": [vp, vp],
+    "dexsim_set_action_copy": [vp, vp],
+    "dexsim_run_stage": [vp, i32, vp],
+    "dexsim_time_stage": [vp, i32, i32, vp, P(f32)],
+    "dexsim_step_timing": [vp, i32, P(f32), P(i32)],
+    "dexsim_state_layout": [P(DexSimConfig), P(DexSimField), i32, P(i32), P(sz)],
+    "dexsim_save_state": [vp, vp, vp, i32, vp, i64, vp],
+    "dexsim_load_state": [vp, vp, vp, i32, vp, i64, vp],
+    "dexsim_copy_envs": [vp, vp, vp, i32, vp],
+    "dexsim_get_step_stamp": [vp, P(i32)],
+    "dexsim_set_step_stamp": [vp, i32],
+    "dexsim_camera_struct_size": [P(sz)],
+    "dexsim_render_layout": [P(DexSimField), i32, P(i32), P(sz)],
+    "dexsim_render": [vp, P(DexSimCamera), vp, vp, vp, i32, vp, vp, vp, vp, vp],
+    "dexsim_body_jacobian": [vp, vp, i32, vp, P(i32), i32, vp, vp],
+    "dexsim_mass_matrix": [vp, vp, i32, vp, vp, vp, vp],
+    "dexsim_ik_struct_size": [P(sz)],
+    "dexsim_solve_ik": [vp, vp, i32, vp, vp, P(DexSimIK), vp, vp, vp, vp],
+    "dexsim_proximity_pair": [i32, P(i32), P(i32), P(i32)],
+    "dexsim_query_proximity": [vp, vp, i32, vp, vp, f32, vp, vp, vp, vp],
+    "dexsim_inverse_dynamics": [vp, vp, i32, vp, vp, vp, i32, vp, vp],
+    "dexsim_body_bias_accel": [vp, vp, i32, vp, vp, P(i32), i32, vp, vp],
+    "dexsim_forward_dynamics": [vp, vp, i32, vp, vp, vp, i32, vp, vp],
+    "dexsim_mass_solve": [vp, vp, i32, vp, vp, i32, i32, vp, vp],
+    "dexsim_inverse_dynamics_derivatives": [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp],
+    "dexsim_forward_dynamics_derivatives": [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp],
+    "dexsim_error_string": [i32],
+    "dexsim_last_error": [],
+}
+EXPORTED_SYMBOLS = list(PROTOTYPES)
 
 
 def declare_prototypes(lib):
     """Attach argtypes/restype for every entry point of include/dexsim.h to a loaded CDLL."""
-    P = C.POINTER
-    vp, sz = C.c_void_p, C.c_size_t
-    lib.dexsim_struct_sizes.argtypes = [P(sz)]
-    lib.dexsim_arena_layout.argtypes = [P(DexSimConfig), P(DexSimField), i32, P(i32), P(sz)]
-    lib.dexsim_obs_key_info.argtypes = [i32, P(C.c_char_p), P(i32), P(i32)]
-    lib.dexsim_reward_term_name.argtypes = [i32, P(C.c_char_p)]
-    lib.dexsim_body_name.argtypes = [i32, P(C.c_char_p)]
-    lib.dexsim_create.argtypes = [P(DexSimConfig), P(DexHandModel), i32, P(vp)]
-    lib.dexsim_destroy.argtypes = [vp]
-    lib.dexsim_bind.argtypes = [vp, P(DexSimBuffers)]
-    lib.dexsim_init_state.argtypes = [vp, vp]
-    lib.dexsim_process_actions.argtypes = [vp, vp, i32, vp]
-    lib.dexsim_begin_step.argtypes = [vp, vp]
-    lib.dexsim_physics_step.argtypes = [vp, i32, vp]
-    lib.dexsim_post_physics.argtypes = [vp, i32, vp]
-    lib.dexsim_step.argtypes = [vp, vp, vp]
-    lib.dexsim_reset_idx.argtypes = [vp, vp, i32, vp]
-    lib.dexsim_reset.argtypes = [vp, vp]
-    lib.dexsim_refresh_body_states.argtypes = [vp, vp]
-    lib.dexsim_set_dof_state_indexed.argtypes = [vp, vp, i32, vp]
-    lib.dexsim_set_root_state_indexed.argtypes = [vp, vp, i32, vp]
-    lib.dexsim_run_stage.argtypes = [vp, i32, vp]
-    lib.dexsim_time_stage.argtypes = [vp, i32, i32, vp, P(f32)]
-    lib.dexsim_step_timing.argtypes = [vp, i32, P(f32), P(i32)]
-    lib.dexsim_set_step_sink.argtypes = [vp, vp, vp, vp]
-    lib.dexsim_set_action_copy.argtypes = [vp, vp]
-    lib.dexsim_set_stats_sink.argtypes = [vp, vp]
-    lib.dexsim_set_phase_probe.argtypes = [vp, vp]
-    lib.dexsim_set_obs_dict_mode.argtypes = [vp, i32]
-    lib.dexsim_state_layout.argtypes = [P(DexSimConfig), P(DexSimField), i32, P(i32), P(sz)]
-    lib.dexsim_save_state.argtypes = [vp, vp, vp, i32, vp, C.c_int64, vp]
-    lib.dexsim_load_state.argtypes = [vp, vp, vp, i32, vp, C.c_int64, vp]
-    lib.dexsim_copy_envs.argtypes = [vp, vp, vp, i32, vp]
-    lib.dexsim_get_step_stamp.argtypes = [vp, P(i32)]
-    lib.dexsim_set_step_stamp.argtypes = [vp, i32]
-    lib.dexsim_camera_struct_size.argtypes = [P(sz)]
-    lib.dexsim_render_layout.argtypes = [P(DexSimField), i32, P(i32), P(sz)]
-    lib.dexsim_render.argtypes = [vp, P(DexSimCamera), vp, vp, vp, i32, vp, vp, vp, vp, vp]
-    lib.dexsim_body_jacobian.argtypes = [vp, vp, i32, vp, P(i32), i32, vp, vp]
-    lib.dexsim_mass_matrix.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    lib.dexsim_ik_struct_size.argtypes = [P(sz)]
-    lib.dexsim_solve_ik.argtypes = [vp, vp, i32, vp, vp, P(DexSimIK), vp, vp, vp, vp]
-    lib.dexsim_proximity_pair.argtypes = [i32, P(i32), P(i32), P(i32)]
-    lib.dexsim_query_proximity.argtypes = [vp, vp, i32, vp, vp, f32, vp, vp, vp, vp]
-    lib.dexsim_inverse_dynamics.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
-    lib.dexsim_body_bias_accel.argtypes = [vp, vp, i32, vp, vp, P(i32), i32, vp, vp]
-    lib.dexsim_forward_dynamics.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
-    lib.dexsim_mass_solve.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
-    lib.dexsim_inverse_dynamics_derivatives.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
-    lib.dexsim_forward_dynamics_derivatives.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
-    for name in EXPORTED_SYMBOLS:
-        getattr(lib, name).restype = i32
-    lib.dexsim_error_string.argtypes = [i32]
+    for name, argtypes in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = argtypes, i32
     lib.dexsim_error_string.restype = C.c_char_p
-    lib.dexsim_last_error.argtypes = []
     lib.dexsim_last_error.restype = C.c_char_p
     return lib
 

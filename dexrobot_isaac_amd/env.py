@@ -3,11 +3,11 @@
 Mirrors reference dexhand_env/tasks/dexhand_base.py (step :893-942, reset :805-838, reset_idx :743-803,
 get_observations_dict :948-956, observation_space/action_space :1150-1169) and the attribute names its callers
 read.  The heavy lifting is one C-ABI call per method; this file only holds views, dict
-bookkeeping and the hooks for host-side custom rules.  There is no CPU path in the product: `sim_device='cpu'`
+bookkeeping and the hooks for host-side custom rules; what the reference class does not have (state snapshots, cameras,
+the kinematics and dynamics queries) is the base class EnvQueries (queries.py).  There is no CPU path in the product: `sim_device='cpu'`
 raises (the reference's CPU pipeline is itself documented as broken for multi-env, docs/guide-debugging.md:309-353).
 """
 import copy
-import hashlib
 
 import numpy as np
 import torch
@@ -16,6 +16,7 @@ from . import _abi
 from ._lib import DexSimError
 from .config import (FINGER_COUPLING_MAP, HARDWARE_MAPPING, OBS_KEYS, REWARD_TERMS, build_sim_config,
                      obs_key_offsets)
+from .queries import EnvQueries, ProximityResult  # noqa: F401  (ProximityResult is imported from here)
 from .spaces import Box
 
 
@@ -314,41 +315,7 @@ class _TaskView:
         self.name = name
 
 
-class ProximityResult:
-    """What DexHandEnv.query_proximity returns: the three device tensors (None where not requested), the pair table and the names
-    behind the capsule and group indices."""
-    FINGER_NAMES = ("thumb", "index", "middle", "ring", "pinky")
-
-    def __init__(self, model, pairs, cap_env=None, self_min=None, pair_dist=None):
-        self.cap_env, self.self_min, self.pair_dist = cap_env, self_min, pair_dist
-        self.pairs = torch.as_tensor(pairs, dtype=torch.int64).view(_abi.NPROX_PAIRS, 3)   # (capsule A, capsule B, group), host
-        self._model = model
-
-    def capsule_body(self, c):
-        """Name of the rigid body capsule c belongs to (a row name of rigid_body_states)."""
-        c = int(c)
-        if not 0 <= c < _abi.NCAP:
-            raise IndexError(f"capsule index must be in [0, {_abi.NCAP}), got {c}")
-        slot = int(self._model.cap_fslot[c])
-        return self._model.body_names[[int(s) for s in self._model.body_fslot].index(slot)]
-
-    def group_fingers(self, g):
-        """The two sides of group g: a pair of finger names, or ("palm", finger name)."""
-        g = int(g)
-        if not 0 <= g < _abi.NPROX_GROUPS:
-            raise IndexError(f"group index must be in [0, {_abi.NPROX_GROUPS}), got {g}")
-        if g >= 10:
-            return ("palm", self.FINGER_NAMES[g - 10])
-        fa, fb = [(a, b) for a in range(5) for b in range(a + 1, 5)][g]
-        return (self.FINGER_NAMES[fa], self.FINGER_NAMES[fb])
-
-    @property
-    def min_pair(self):
-        """(k, 15) int64: the pair-table index of every group's closest pair (word 7 of self_min)."""
-        return self.self_min[..., 7].contiguous().view(torch.int32).to(torch.int64)
-
-
-class DexHandEnv:
+class DexHandEnv(EnvQueries):
     """Vectorised DexHand environment on one MI355X (one process per GPU; shard envs across ranks)."""
 
     def __init__(self, cfg, task_name, rl_device, sim_device, graphics_device_id=0, headless=True, force_render=False,
@@ -663,496 +630,6 @@ class DexHandEnv:
                 out[:, 6:] = finger_controller(self)
             return out
         self.action_processor.set_pre_action_rule(rule if (base_controller or finger_controller) else None)
-
-    # ------------------------------------------------------------------ save / restore / fork (dexsim_save_state and friends)
-    def _state_core(self, what):
-        core = self._core
-        for m in ("state_layout", "state_bank", "save_state", "load_state", "copy_envs", "get_step_stamp", "set_step_stamp"):
-            if not hasattr(core, m):
-                raise DexSimError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no {m}()")
-        return core
-
-    def _config_hash(self):
-        return hashlib.sha256(bytes(self._sim_cfg) + bytes(self._model_struct)).hexdigest()
-
-    def get_state(self):
-        """Full snapshot (EnvState) of this env at a control-step boundary; set_state() of it, here or in a fresh env of the
-        same configuration, continues bit for bit."""
-        core = self._state_core("get_state")
-        bank = core.state_bank(core.NS)
-        core.save_state(bank)
-        ap = self.action_processor
-        return EnvState(bank.version, bank.record_words, self.num_envs, self._config_hash(), bank.capacity, core.get_step_stamp(),
-                        bank.data, core.stats.clone(), core.counters.clone(), self.actions.clone(),
-                        ap._enabled_post_action_filters)
-
-    def set_state(self, state):
-        """Restore a snapshot taken by get_state().  Every env-owned tensor (obs_buf, rew_buf, reset_buf, extras, obs_dict,
-        dof_state, actor_root_state_tensor, ...) is written in place: the views callers hold stay valid."""
-        core = self._state_core("set_state")
-        from .core import StateBank
-        layout, words = core.state_layout()
-        for name, mine, theirs in (("version", _abi.STATE_VERSION, state.version), ("record_words", words, state.record_words),
-                                   ("num_envs", self.num_envs, state.num_envs), ("config_hash", self._config_hash(), state.config_hash)):
-            if mine != theirs:
-                raise DexSimError(f"set_state: the state does not fit this env: {name} is {theirs}, expected {mine}")
-        if state.capacity < core.NS:
-            raise DexSimError(f"set_state: the state does not fit this env: capacity is {state.capacity}, expected at least {core.NS}")
-        dev = core.device
-        bank = StateBank(state.bank.to(dev), state.capacity, state.record_words, layout, state.version)
-        core.load_state(bank)
-        core.stats.copy_(state.stats.to(dev))
-        core.counters.copy_(state.counters.to(dev))
-        core.set_step_stamp(state.stamp)
-        self.actions.copy_(state.actions.to(self.actions.device))
-        self.action_processor._enabled_post_action_filters = list(state.enabled_post_action_filters)
-
-    def state_bank(self, capacity):
-        """A state bank of `capacity` slots for save_states / load_states (a bank of grasp states, a curriculum, ...)."""
-        return self._state_core("state_bank").state_bank(capacity)
-
-    def save_states(self, bank, slots, env_ids):
-        """Records of envs `env_ids` -> slots `slots` of `bank`."""
-        self._state_core("save_states").save_state(bank, env_ids=env_ids, slots=slots)
-
-    def load_states(self, bank, slots, env_ids):
-        """Slots `slots` of `bank` -> envs `env_ids` (unique): reset-to-stored-state.  Only those envs change."""
-        self._state_core("load_states").load_state(bank, env_ids=env_ids, slots=slots)
-
-    def fork_envs(self, src_ids, dst_ids, check=True):
-        """Copy env src_ids[i] onto env dst_ids[i] (a source may repeat).  The destinations must be unique and none may also be a
-        source; check=True verifies that (and the id range) on the device, which costs a host synchronisation: pass
-        check=False when forking every step with ids known to be good."""
-        core = self._state_core("fork_envs")
-        src = torch.as_tensor(src_ids, device=core.device).to(torch.int64).view(-1)
-        dst = torch.as_tensor(dst_ids, device=core.device).to(torch.int64).view(-1)
-        if src.numel() != dst.numel():
-            raise DexSimError(f"fork_envs: {src.numel()} sources but {dst.numel()} destinations")
-        if check and src.numel():
-            n = self.num_envs
-            hits = torch.zeros(n, dtype=torch.int32, device=core.device)
-            ok = bool(((src >= 0) & (src < n)).all() & ((dst >= 0) & (dst < n)).all())
-            if not ok:
-                raise DexSimError(f"fork_envs: env ids must be in [0, {n})")
-            hits.index_add_(0, dst, torch.ones_like(dst, dtype=torch.int32))
-            is_src = torch.zeros(n, dtype=torch.bool, device=core.device)
-            is_src[src] = True
-            if bool((hits > 1).any()):
-                raise DexSimError("fork_envs: a destination env is listed more than once")
-            if bool(((hits > 0) & is_src).any()):
-                raise DexSimError("fork_envs: a destination env is also a source")
-        core.copy_envs(src, dst)
-
-    # ------------------------------------------------------------------ camera sensors (dexsim_render)
-    def _render_core(self, what):
-        core = self._core
-        if not hasattr(core, "render"):
-            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no render()")
-        return core
-
-    def _camera(self, name):
-        if name not in self._cameras:
-            raise KeyError(f"no camera named '{name}' (cameras: {sorted(self._cameras)})")
-        return self._cameras[name]
-
-    def create_camera(self, name, width, height, hfov_deg=75.0, eye=(-1.5, 0.0, 0.5), target=(0.0, 0.0, 0.15), parent=None,
-                      near=0.01, far=10.0):
-        """A camera sensor for every env (GraphicsManager.create_camera, graphics_manager.py:56-100).  eye / target: the look-at
-        pair in the parent frame, shared 3-vectors or (N, 3) tensors; parent: None = each env's world frame, or a joint index /
-        DOF name to mount the camera on that joint's frame (e.g. 5 or "ARRz": eye-in-hand on the palm joint), up = the parent's +z.
-        near / far: clip distances along the optical axis in metres."""
-        core = self._render_core("create_camera")
-        if name in self._cameras:
-            raise ValueError(f"camera '{name}' already exists")
-        if parent is None:
-            pj = -1
-        elif isinstance(parent, str):
-            if parent not in self.model.dof_names:
-                raise ValueError(f"create_camera: unknown joint '{parent}' (joints: {self.model.dof_names})")
-            pj = self.model.dof_names.index(parent)
-        else:
-            pj = int(parent)
-        if not -1 <= pj < _abi.NJ:
-            raise ValueError(f"create_camera: parent joint index must be in [0, {_abi.NJ}), got {parent}")
-        width, height = int(width), int(height)
-        if not (1 <= width <= _abi.RENDER_MAX_DIM and 1 <= height <= _abi.RENDER_MAX_DIM):
-            raise ValueError(f"create_camera: width and height must be in [1, {_abi.RENDER_MAX_DIM}], got {width} x {height}")
-        if not 0.0 < float(hfov_deg) < 180.0:
-            raise ValueError(f"create_camera: hfov_deg must be in (0, 180), got {hfov_deg}")
-        if not float(near) < float(far):
-            raise ValueError(f"create_camera: near ({near}) must be below far ({far})")
-        cam = _abi.DexSimCamera()
-        cam.width, cam.height, cam.hfov_deg = width, height, float(hfov_deg)
-        cam.near_clip, cam.far_clip, cam.parent_joint = float(near), float(far), pj
-        core.render_layout()
-        self._cameras[name] = {"cam": cam, "eye": None, "target": None, "buffers": {}}
-        self.set_camera_location(name, eye, target)
-        return name
-
-    def set_camera_location(self, name, eye, target):
-        """GraphicsManager.set_camera_location (graphics_manager.py:102-134): eye and target in the camera's parent frame, each a
-        shared 3-vector or an (N, 3) tensor with one row per env."""
-        c = self._camera(name)
-        for key, val in (("eye", eye), ("target", target)):
-            t = torch.as_tensor(val, dtype=torch.float32)
-            if tuple(t.shape) == (3,):
-                for i in range(3):
-                    getattr(c["cam"], key)[i] = float(t[i])
-                c[key] = None
-            elif tuple(t.shape) == (self.num_envs, 3):
-                c[key] = t.to(self._core.device).contiguous()
-            else:
-                raise ValueError(f"set_camera_location: {key} must have shape (3,) or ({self.num_envs}, 3), got {tuple(t.shape)}")
-
-    def render_camera(self, name, env_ids=None, outputs=("rgba", "depth", "seg")):
-        """GraphicsManager.render_all_cameras + capture_frame (graphics_manager.py:136-179) for one camera: a dict of device
-        tensors -- "rgba" (k, H, W, 4) uint8, "depth" (k, H, W) float32 (+inf without a hit), "seg" (k, H, W) int32 -- for the
-        envs `env_ids` (None = all, k = num_envs).  The tensors belong to the camera: they are allocated once per k and
-        overwritten by the next render_camera of the same camera and k."""
-        core = self._render_core("render_camera")
-        c = self._camera(name)
-        outputs = tuple(outputs)
-        if not outputs or any(o not in ("rgba", "depth", "seg") for o in outputs):
-            raise ValueError(f"render_camera: outputs must be a non-empty subset of ('rgba', 'depth', 'seg'), got {outputs}")
-        ids = None if env_ids is None else torch.as_tensor(env_ids, device=core.device).to(torch.int64).view(-1)
-        k = self.num_envs if ids is None else int(ids.numel())
-        cam, dev = c["cam"], core.device
-        H, W = int(cam.height), int(cam.width)
-        buf = c["buffers"].setdefault(k, {})
-        if "scene" not in buf:
-            buf["scene"] = torch.zeros(k, core.render_layout()[1], dtype=torch.float32, device=dev)
-        shapes = {"rgba": ((k, H, W, 4), torch.uint8), "depth": ((k, H, W), torch.float32), "seg": ((k, H, W), torch.int32)}
-        for o in outputs:
-            if o not in buf:
-                buf[o] = torch.zeros(shapes[o][0], dtype=shapes[o][1], device=dev)
-        if k == 0:
-            return {o: buf[o] for o in outputs}
-        pick = lambda t: None if t is None else (t if ids is None else t[ids].contiguous())
-        core.render(cam, buf["scene"], env_ids=ids, eye=pick(c["eye"]), target=pick(c["target"]),
-                    **{o: buf[o] for o in outputs})
-        return {o: buf[o] for o in outputs}
-
-    def render(self, mode="rgb_array"):
-        """env 0's (H, W, 3) uint8 frame of the camera named "video" (created by a video_config with a `resolution`, or by
-        create_camera("video", ...)); None without one -- headless: no viewer / recorder / streamer."""
-        if "video" not in getattr(self, "_cameras", {}):
-            return None
-        return self.render_camera("video", [0], ("rgba",))["rgba"][0, :, :, :3].cpu().numpy()
-
-    # ------------------------------------------------------------------ Jacobians, mass matrix, gravity force
-    def _kindyn_rows(self, what, method, env_ids, q):
-        """The HIP core (it must have `method`), (ids, q) as device tensors and the number of output rows k, for the queries
-        that are functions of q: get_jacobian, get_mass_matrix, solve_fingertip_ik, query_proximity."""
-        core = self._core
-        if not hasattr(core, method):
-            raise NotImplementedError(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no {method}()")
-        if q is not None:
-            q = torch.as_tensor(q, dtype=torch.float32, device=core.device)
-            if q.dim() != 2 or q.shape[1] != _abi.NJ or q.shape[0] < 1:
-                raise ValueError(f"{what}: q must have shape (k, {_abi.NJ}) with k >= 1, got {tuple(q.shape)}")
-            return core, None, q.contiguous(), int(q.shape[0])
-        if env_ids is None:
-            return core, None, None, self.num_envs
-        ids = torch.as_tensor(env_ids, device=core.device).to(torch.int64).view(-1)
-        if ids.numel() < 1:
-            raise ValueError(f"{what}: env_ids is empty")
-        return core, ids, None, int(ids.numel())
-
-    def _kindyn_out(self, what, out, shape, device):
-        if out is None:
-            return torch.empty(shape, dtype=torch.float32, device=device)      # the kernels write every element
-        if not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() \
-                or out.device != device:
-            raise ValueError(f"{what}: out must be a contiguous float32 tensor of shape {shape} on {device}")
-        return out
-
-    def _kindyn_bodies(self, what, bodies):
-        """(indices or None = all, nb) of a `bodies` argument: indices into the rows of rigid_body_states or names from
-        hand_model.BODY_NAMES."""
-        if bodies is None:
-            return None, _abi.NUM_HAND_BODIES
-        if isinstance(bodies, (str, int)):
-            bodies = [bodies]
-        idx = []
-        for b in bodies:
-            if isinstance(b, str):
-                if b not in self.model.body_names:
-                    raise ValueError(f"{what}: unknown body '{b}' (bodies: {self.model.body_names})")
-                b = self.model.body_names.index(b)
-            b = int(b)
-            if not 0 <= b < _abi.NUM_HAND_BODIES:
-                raise ValueError(f"{what}: body index must be in [0, {_abi.NUM_HAND_BODIES}), got {b}")
-            idx.append(b)
-        if not 1 <= len(idx) <= _abi.NUM_HAND_BODIES:
-            raise ValueError(f"{what}: between 1 and {_abi.NUM_HAND_BODIES} bodies, got {len(idx)}")
-        return idx, len(idx)
-
-    def get_jacobian(self, bodies=None, env_ids=None, q=None, out=None):
-        """gym.acquire_jacobian_tensor / refresh_jacobian_tensors for the hand: (k, nb, 6, 26) geometric Jacobians of the hand
-        bodies `bodies` -- indices into the rows of rigid_body_states or names from hand_model.BODY_NAMES such as
-        "r_f_link2_tip"; None = all 37 in order.  Rows 0-2: world linear velocity of the body origin, 3-5: world angular
-        velocity; column j: DOF j of dof_state, so jac[i, b] @ dof_vel[env] == rigid_body_states[env, b, 7:13].  Rows: the
-        envs `env_ids` (None = all), or the rows of a (k, 26) joint-position override `q` (env_ids is then ignored)."""
-        core, ids, q, k = self._kindyn_rows("get_jacobian", "body_jacobian", env_ids, q)
-        idx, nb = self._kindyn_bodies("get_jacobian", bodies)
-        out = self._kindyn_out("get_jacobian", out, (k, nb, 6, _abi.NJ), core.device)
-        core.body_jacobian(out, env_ids=ids, q=q, bodies=idx)
-        return out
-
-    def get_mass_matrix(self, env_ids=None, q=None, gravity=False, out=None):
-        """gym.acquire_mass_matrix_tensor / refresh_mass_matrix_tensors for the hand: the (k, 26, 26) joint-space inertia M(q)
-        (no armature, no PD terms).  gravity=True returns (M, g) with g (k, 26) the gravity force dV/dq: the generalized force
-        a controller adds to hold the hand.  Rows as for get_jacobian.  out: M, or the pair (M, g) when gravity=True."""
-        core, ids, q, k = self._kindyn_rows("get_mass_matrix", "mass_matrix", env_ids, q)
-        if gravity:
-            if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-                raise ValueError("get_mass_matrix: with gravity=True, out must be the pair (M, g)")
-            om, og = (None, None) if out is None else out
-            M = self._kindyn_out("get_mass_matrix", om, (k, _abi.NJ, _abi.NJ), core.device)
-            g = self._kindyn_out("get_mass_matrix", og, (k, _abi.NJ), core.device)
-            core.mass_matrix(mass=M, gravity=g, env_ids=ids, q=q)
-            return M, g
-        M = self._kindyn_out("get_mass_matrix", out, (k, _abi.NJ, _abi.NJ), core.device)
-        core.mass_matrix(mass=M, env_ids=ids, q=q)
-        return M
-
-    # ------------------------------------------------------------------ inverse dynamics, bias accelerations
-    def _kindyn_rows_qd(self, what, method, env_ids, q, qd):
-        """_kindyn_rows for the queries that are functions of (q, qd): the overrides go together."""
-        core, ids, qt, k = self._kindyn_rows(what, method, env_ids, q)
-        if (q is None) != (qd is None):
-            raise ValueError(f"{what}: q and qd go together: both None (the envs' state) or both (k, {_abi.NJ}) overrides")
-        return core, ids, qt, self._kindyn_vel(what, "qd", qd, k, core.device), k
-
-    def _kindyn_vel(self, what, name, t, k, device):
-        if t is None:
-            return None
-        t = torch.as_tensor(t, dtype=torch.float32, device=device)
-        if tuple(t.shape) != (k, _abi.NJ):
-            raise ValueError(f"{what}: {name} must have shape ({k}, {_abi.NJ}), got {tuple(t.shape)}")
-        return t.contiguous()
-
-    def get_inverse_dynamics(self, qdd=None, env_ids=None, q=None, qd=None, gravity=True, out=None):
-        """(k, 26) generalized forces tau = M(q) qdd + c(q, qd) (+ g(q) with gravity=True) that produce the joint accelerations
-        `qdd` (k, 26; None = zero), with the M and g of get_mass_matrix: no armature, no PD terms, no contact.  Rows: the envs
-        `env_ids` (None = all) at their dof_pos / dof_vel, or the rows of the (k, 26) overrides `q` and `qd`, which go together
-        (env_ids is then ignored).  Row i of qdd belongs to row i of the result on either path."""
-        core, ids, q, qd, k = self._kindyn_rows_qd("get_inverse_dynamics", "inverse_dynamics", env_ids, q, qd)
-        qdd = self._kindyn_vel("get_inverse_dynamics", "qdd", qdd, k, core.device)
-        out = self._kindyn_out("get_inverse_dynamics", out, (k, _abi.NJ), core.device)
-        core.inverse_dynamics(out, qdd=qdd, env_ids=ids, q=q, qd=qd, gravity=gravity)
-        return out
-
-    def get_bias_forces(self, env_ids=None, q=None, qd=None, gravity=True, out=None):
-        """get_inverse_dynamics at qdd = 0: the (k, 26) velocity-product force c(q, qd), plus g(q) with gravity=True -- what a
-        computed-torque controller adds to M(q) qdd."""
-        return self.get_inverse_dynamics(None, env_ids, q, qd, gravity, out)
-
-    def get_body_bias_acceleration(self, bodies=None, env_ids=None, q=None, qd=None, out=None):
-        """(k, nb, 6) Jdot qd of the hand bodies `bodies` (as for get_jacobian): world linear acceleration of the body origin
-        (0-2) and angular acceleration (3-5) at zero joint acceleration, without gravity, so that get_jacobian(...)[i, b] @ qdd +
-        this is the derivative of rigid_body_states[env, b, 7:13].  Rows as for get_inverse_dynamics."""
-        core, ids, q, qd, k = self._kindyn_rows_qd("get_body_bias_acceleration", "body_bias_accel", env_ids, q, qd)
-        idx, nb = self._kindyn_bodies("get_body_bias_acceleration", bodies)
-        out = self._kindyn_out("get_body_bias_acceleration", out, (k, nb, 6), core.device)
-        core.body_bias_accel(out, env_ids=ids, q=q, qd=qd, bodies=idx)
-        return out
-
-    # ------------------------------------------------------------------ forward dynamics, mass-matrix solves
-    def get_forward_dynamics(self, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False, out=None):
-        """(k, 26) joint accelerations qdd = (M(q) [+ A])^-1 (tau - c(q, qd) [- g(q)]) that the generalized forces `tau` (k, 26;
-        None = zero: the free acceleration) produce -- the inverse of get_inverse_dynamics, with the same M, c and g: no PD terms,
-        no contact, no joint-limit forces (fold them into tau).  armature=True solves with M + diag(model.armature).  Rows as for
-        get_inverse_dynamics; row i of tau belongs to row i of the result on either path."""
-        core, ids, q, qd, k = self._kindyn_rows_qd("get_forward_dynamics", "forward_dynamics", env_ids, q, qd)
-        tau = self._kindyn_vel("get_forward_dynamics", "tau", tau, k, core.device)
-        out = self._kindyn_out("get_forward_dynamics", out, (k, _abi.NJ), core.device)
-        core.forward_dynamics(out, tau=tau, env_ids=ids, q=q, qd=qd, gravity=gravity, armature=armature)
-        return out
-
-    def solve_mass_matrix(self, rhs, env_ids=None, q=None, armature=False, out=None):
-        """(M(q) [+ A])^-1 applied to `rhs` (k, 26) or (k, nrhs, 26), nrhs <= 32, without forming M; the result has rhs's shape.
-        Each row is factored once for all its right-hand sides.  With rows of get_jacobian as right-hand sides this is
-        M^-1 J^T (Lambda^-1 = J M^-1 J^T), with 26 unit columns M^-1 itself.  Rows as for get_mass_matrix; `out` may be `rhs`."""
-        core, ids, q, k = self._kindyn_rows("solve_mass_matrix", "mass_solve", env_ids, q)
-        rhs = torch.as_tensor(rhs, dtype=torch.float32, device=core.device)
-        if rhs.dim() not in (2, 3) or rhs.shape[0] != k or rhs.shape[-1] != _abi.NJ or \
-                (rhs.dim() == 3 and not 1 <= rhs.shape[1] <= _abi.MSOLVE_MAX_RHS):
-            raise ValueError(f"solve_mass_matrix: rhs must have shape ({k}, {_abi.NJ}) or ({k}, nrhs, {_abi.NJ}) with nrhs in "
-                             f"[1, {_abi.MSOLVE_MAX_RHS}], got {tuple(rhs.shape)}")
-        shape = tuple(rhs.shape)
-        out = self._kindyn_out("solve_mass_matrix", out, shape, core.device)
-        core.mass_solve(out.view(k, -1, _abi.NJ), rhs.contiguous().view(k, -1, _abi.NJ), env_ids=ids, q=q, armature=armature)
-        return out
-
-    # ------------------------------------------------------------------ derivatives of the inverse and the forward dynamics
-    def _kindyn_outs(self, what, out, shapes, device):
-        """_kindyn_out for a call with several outputs: `out` is None or a tuple / list with one tensor per shape."""
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != len(shapes)):
-            raise ValueError(f"{what}: out must be a tuple of {len(shapes)} tensors")
-        return [self._kindyn_out(what, o, s, device) for o, s in zip(out or [None] * len(shapes), shapes)]
-
-    def get_inverse_dynamics_derivatives(self, qdd=None, env_ids=None, q=None, qd=None, gravity=True, out=None):
-        """(dtau_dq, dtau_dqd), each (k, 26, 26): the derivatives of get_inverse_dynamics(qdd, ...) with respect to the joint
-        positions and velocities at fixed qdd, analytic.  D[i, r, c] = d tau_r / d q_c, so D[i] @ dq is the first-order change of
-        tau.  The two are TRANSPOSED VIEWS of the device's derivative-major arrays (dexsim.h): call .contiguous() for a dense
-        matrix, or .transpose(1, 2) for the (k, c, r) array as it was written.  Arguments and rows as for get_inverse_dynamics.
-        out: a pair of contiguous (k, 26, 26) tensors that receive the derivative-major arrays; the views returned are of them."""
-        what = "get_inverse_dynamics_derivatives"
-        core, ids, q, qd, k = self._kindyn_rows_qd(what, "inverse_dynamics_derivatives", env_ids, q, qd)
-        qdd = self._kindyn_vel(what, "qdd", qdd, k, core.device)
-        dq, dqd = self._kindyn_outs(what, out, [(k, _abi.NJ, _abi.NJ)] * 2, core.device)
-        core.inverse_dynamics_derivatives(dq, dqd, qdd=qdd, env_ids=ids, q=q, qd=qd, gravity=gravity)
-        return dq.transpose(1, 2), dqd.transpose(1, 2)
-
-    def get_forward_dynamics_derivatives(self, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False, out=None):
-        """(qdd, dqdd_dq, dqdd_dqd): the (k, 26) result of get_forward_dynamics(tau, ...) and its (k, 26, 26) derivatives with
-        respect to the joint positions and velocities at fixed tau, D[i, r, c] = d qdd_r / d q_c, as transposed views like
-        get_inverse_dynamics_derivatives.  d qdd / d tau is (M [+ A])^-1: solve_mass_matrix of 26 unit columns.  Unbounded at
-        the base's gimbal lock, where M is singular.  Arguments and rows as for get_forward_dynamics.  out: a triple of contiguous
-        tensors (k, 26), (k, 26, 26), (k, 26, 26) that receive qdd and the derivative-major arrays."""
-        what = "get_forward_dynamics_derivatives"
-        core, ids, q, qd, k = self._kindyn_rows_qd(what, "forward_dynamics_derivatives", env_ids, q, qd)
-        tau = self._kindyn_vel(what, "tau", tau, k, core.device)
-        qdd, dq, dqd = self._kindyn_outs(what, out, [(k, _abi.NJ)] + [(k, _abi.NJ, _abi.NJ)] * 2, core.device)
-        core.forward_dynamics_derivatives(qdd, dq, dqd, tau=tau, env_ids=ids, q=q, qd=qd, gravity=gravity, armature=armature)
-        return qdd, dq.transpose(1, 2), dqd.transpose(1, 2)
-
-    # ------------------------------------------------------------------ fingertip inverse kinematics
-    @property
-    def control_names(self):
-        """Names of the 18 active targets in their order: the six base joints, then the first DOF of each finger control's
-        coupling group (FINGER_COUPLING_MAP)."""
-        return list(self.model.dof_names[:6]) + [FINGER_COUPLING_MAP[c][0][0] for c in range(12)]
-
-    def solve_fingertip_ik(self, targets, env_ids=None, q=None, sites="tips", frame="world", free="fingers", weights=None,
-                           iters=16, damping=1e-3, max_step=0.5, return_info=False):
-        """Batched inverse kinematics for the five fingertips in control space, every iteration inside one kernel launch.
-        targets (k, 5, 3): wanted positions of the fingertip sites (sites="tips") or fingerpad sites (sites="pads"), thumb to
-        pinky, in the env's world frame (frame="world", as obs_dict["fingertip_poses_world"][..., :3]) or in the hand frame
-        (frame="hand", as fingertip_poses_hand / fingerpad_poses_hand; the base is then fixed).  Rows as for get_jacobian: the
-        envs `env_ids` (None = all) start from their current joint positions, the rows of a (k, 26) override `q` from that.
-        free: the controls that may move -- "fingers" (controls 6..17), "all", or a list of indices / names (control_names, or
-        the hardware names "th_rot", "ff_spr", ...); the others keep their start value.  weights: five values >= 0, 0 drops a
-        finger from the objective (a thumb-index pinch: (1, 1, 0, 0, 0)).  Damped least squares with damping `damping`; no
-        control changes by more than `max_step` per iteration; the result respects the active limits.  Base slides (m) and base
-        rotations (rad) share the one damping.
-
-        Returns controls (k, 18): the 18 active targets the action stage works in.  Feed them back as the raw targets of a
-        custom action rule -- env.action_processor.set_action_rule(lambda prev, rule, actions, cfg: controls) -- or, for a
-        policy-style action in position mode, through the limit scaling: action = 2 (u - lower) / (upper - lower) - 1 on the
-        controls the policy drives.  With return_info=True: (controls, {"q": (k, 26) coupled joint positions, "residual": (k, 5)
-        distance left per finger, dropped fingers included})."""
-        what = "solve_fingertip_ik"
-        core, ids, q, k = self._kindyn_rows(what, "solve_ik", env_ids, q)
-        if sites not in ("tips", "pads"):
-            raise ValueError(f"{what}: sites must be 'tips' or 'pads', got {sites!r}")
-        if frame not in ("world", "hand"):
-            raise ValueError(f"{what}: frame must be 'world' or 'hand', got {frame!r}")
-        names = self.control_names
-        hw = {n: names.index(dofs[0]) for n, dofs in HARDWARE_MAPPING}
-        if isinstance(free, str) and free in ("fingers", "all"):
-            idx = list(range(6, _abi.NACT)) if free == "fingers" else list(range(_abi.NACT))
-        else:
-            if isinstance(free, (str, int)):
-                free = [free]
-            idx = []
-            for c in free:
-                if isinstance(c, str):
-                    if c not in names and c not in hw:
-                        raise ValueError(f"{what}: free: unknown control '{c}' (controls: {names}, or {sorted(hw)})")
-                    c = names.index(c) if c in names else hw[c]
-                c = int(c)
-                if not 0 <= c < _abi.NACT:
-                    raise ValueError(f"{what}: free: control index must be in [0, {_abi.NACT}), got {c}")
-                idx.append(c)
-            if not idx:
-                raise ValueError(f"{what}: free: at least one control must be free")
-        mask = 0
-        for c in idx:
-            mask |= 1 << c
-        if frame == "hand" and mask & 63:
-            raise ValueError(f"{what}: free: hand-frame targets need the base controls 0..5 fixed")
-        w = [1.0] * _abi.NFINGER if weights is None else [float(x) for x in torch.as_tensor(weights, dtype=torch.float32).view(-1).tolist()]
-        if len(w) != _abi.NFINGER or not all(x >= 0.0 and x == x and x != float("inf") for x in w) or not any(x > 0.0 for x in w):
-            raise ValueError(f"{what}: weights must be {_abi.NFINGER} finite values >= 0, not all 0, got {w}")
-        iters = int(iters)
-        if not 1 <= iters <= _abi.IK_MAX_ITERS:
-            raise ValueError(f"{what}: iters must be in [1, {_abi.IK_MAX_ITERS}], got {iters}")
-        if not float(damping) > 0.0 or not float(max_step) > 0.0:
-            raise ValueError(f"{what}: damping and max_step must be positive, got {damping} and {max_step}")
-        targets = torch.as_tensor(targets, dtype=torch.float32, device=core.device)
-        if tuple(targets.shape) != (k, _abi.NFINGER, 3):
-            raise ValueError(f"{what}: targets must have shape ({k}, {_abi.NFINGER}, 3), got {tuple(targets.shape)}")
-        controls = torch.empty((k, _abi.NACT), dtype=torch.float32, device=core.device)
-        info = {}
-        if return_info:
-            info = {"q": torch.empty((k, _abi.NJ), dtype=torch.float32, device=core.device),
-                    "residual": torch.empty((k, _abi.NFINGER), dtype=torch.float32, device=core.device)}
-        if ids is not None:   # a row whose id is out of range is left as it is by the kernel: give it a defined value
-            controls.fill_(float("nan"))
-            for t in info.values():
-                t.fill_(float("nan"))
-        core.solve_ik(targets.contiguous(), controls, env_ids=ids, q=q, sites=0 if sites == "tips" else 1,
-                      frame=0 if frame == "world" else 1, free_mask=mask, weights=w, iters=iters, damping=float(damping),
-                      max_step=float(max_step), q_out=info.get("q"), residual=info.get("residual"))
-        return (controls, info) if return_info else controls
-
-    # ------------------------------------------------------------------ clearance queries (dexsim_query_proximity)
-    def query_proximity(self, env_ids=None, q=None, box_pose=None, box_size=None, outputs=("cap_env", "self_min", "pair_dist"), out=None):
-        """Clearances of the hand against the box, the ground and itself, one kernel launch: is a configuration free of collision,
-        and how far is every link from the object, the ground and the other fingers?  Returns a ProximityResult with
-          cap_env   (k, 18, 2, 8): per collision capsule, record 0 against the box and record 1 against the ground z = 0 --
-                    [signed distance, unit normal towards the capsule (3), witness point on the other shape (3), axis parameter t];
-                    without a box the box record is (+inf, 0, ...)
-          self_min  (k, 15, 8): the closest capsule pair of the ten finger pairs and of the palm with each finger --
-                    [distance, normal from B to A (3), witness on B's surface (3), pair index as int32 bits]
-          pair_dist (k, 120): the distance of every pair of `pairs`, the (120, 3) table (capsule A, capsule B, group)
-        (the tensors not named in `outputs` are None).  Rows as for get_jacobian: the envs `env_ids` (None = all), or the rows of a
-        (k, 26) joint-position override `q`.  The box: `box_pose` (k, 7) = centre xyz + quaternion xyzw when given; "env" together
-        with a `q` of num_envs rows takes every env's own box ("check my IK result against my box"); None = the envs' own box
-        without `q`, no box with it.  box_size: edge length, None = the configured one.  out: a dict of preallocated tensors by
-        output name.  The engine's own hand self-collision does not exist: negative self distances are not resolved by the
-        physics."""
-        what = "query_proximity"
-        core, ids, q, k = self._kindyn_rows(what, "proximity", env_ids, q)
-        names = ("cap_env", "self_min", "pair_dist")
-        if isinstance(outputs, str):
-            outputs = (outputs,)
-        outputs = tuple(outputs)
-        if not outputs or any(o not in names for o in outputs):
-            raise ValueError(f"{what}: outputs must be a non-empty subset of {names}, got {outputs}")
-        if isinstance(box_pose, str):
-            if box_pose != "env":
-                raise ValueError(f"{what}: box_pose must be a (k, 7) tensor, 'env' or None, got {box_pose!r}")
-            if q is None or k != self.num_envs:
-                raise ValueError(f"{what}: box_pose='env' needs a q override of num_envs = {self.num_envs} rows")
-            if not int(self._sim_cfg.has_box):
-                raise ValueError(f"{what}: box_pose='env' needs a task with a box")
-            box_pose = core.root_state[:, 1, :7].contiguous()
-        elif box_pose is not None:
-            box_pose = torch.as_tensor(box_pose, dtype=torch.float32, device=core.device)
-            if tuple(box_pose.shape) != (k, 7):
-                raise ValueError(f"{what}: box_pose must have shape ({k}, 7), got {tuple(box_pose.shape)}")
-            box_pose = box_pose.contiguous()
-        size = 0.0
-        if box_size is not None:
-            size = float(box_size)
-            if not (size > 0.0 and size != float("inf")):
-                raise ValueError(f"{what}: box_size must be a positive finite edge length, got {box_size}")
-        shapes = {"cap_env": (k, _abi.NCAP, 2, 8), "self_min": (k, _abi.NPROX_GROUPS, 8), "pair_dist": (k, _abi.NPROX_PAIRS)}
-        if out is not None and (not isinstance(out, dict) or any(o not in outputs for o in out)):
-            raise ValueError(f"{what}: out must be a dict of tensors keyed by the names in outputs, got {out if not isinstance(out, dict) else sorted(out)}")
-        bufs = {}
-        for o in outputs:
-            given = None if out is None else out.get(o)
-            bufs[o] = self._kindyn_out(what, given, shapes[o], core.device)
-            if given is None and ids is not None:   # a row whose id is out of range is left as it is by the kernel: give it a defined value
-                bufs[o].fill_(float("nan"))
-        core.proximity(env_ids=ids, q=q, box_pose=box_pose, box_size=size, **bufs)
-        if getattr(self, "_proximity_pairs", None) is None:
-            self._proximity_pairs = core.proximity_pairs()                     # a host table: read once
-        return ProximityResult(self.model, self._proximity_pairs, **bufs)
 
     def close(self):
         if self._core is not None:

@@ -13,32 +13,9 @@ Timing: HIP events around blocks of back-to-back solves, after a warm-up block; 
 both times, their ratio, the share of rows the kernel brings within 0.1 mm on every finger in `--iters` iterations, the median of
 the rows' worst residual and the largest difference of the two results on those rows.  The figures in DESIGN.md ("Measurements:
 fingertip IK") and profiles/ik come from this script."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-
-def time_block(fn, n):
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(n):
-        fn()
-    t1.record()
-    t1.synchronize()
-    return t0.elapsed_time(t1) * 1000.0          # us
-
-
-def measure(fn, launches, block):
-    time_block(fn, block)                        # warm-up
-    blocks = max(1, (launches + block - 1) // block)
-    return sum(time_block(fn, block) for _ in range(blocks)) / (blocks * block)
+import numpy as np
+import query_timing as qt
+import torch
 
 
 def quat_to_mat(q):
@@ -89,16 +66,13 @@ class TorchSites:
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", type=int, default=4096)
+    ap = qt.parser(launches=100, rows=4096)
     ap.add_argument("--iters", type=int, default=16)
-    ap.add_argument("--launches", type=int, default=100)
-    ap.add_argument("--out", default=None, help="also append the JSON line to this file")
     args = ap.parse_args()
     from dexrobot_isaac_amd import _abi, make_env
     from dexrobot_isaac_amd.config import FINGER_COUPLING_MAP
     from dexrobot_isaac_amd.hand_model import FINGERTIP_BODY_NAMES
-    dev = "cuda:0"
+    dev = qt.DEV
     k, NJ, NACT = args.rows, _abi.NJ, _abi.NACT
     env = make_env("BlindGrasping", k, dev, dev, 0)
     env.reset()
@@ -155,17 +129,14 @@ def main():
     worst = resid.amax(1)                                                       # per row, over the five fingers
     conv = worst <= 1e-4
     diff = float((result["u"] - controls)[conv].abs().max())
-    t_kernel = measure(kernel, args.launches, 20)
-    t_comp = measure(composed, args.launches, 5)
+    t_kernel = qt.measure(kernel, args.launches, 20)
+    t_comp = qt.measure(composed, args.launches, 5)
     line = {"rows": k, "iters": args.iters, "free": "fingers", "kernel_us": round(t_kernel, 1), "composed_us": round(t_comp, 1),
             "ratio": round(t_comp / t_kernel, 1), "kernel_us_per_iteration": round(t_kernel / args.iters, 2),
             "rows_within_0.1mm": round(float(conv.float().mean()), 4), "median_residual_m": float(f"{float(worst.median()):.3g}"),
             "max_abs_diff_of_controls_on_those_rows": float(f"{diff:.3g}"), "launches": args.launches}
-    print(json.dumps(line))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a") as f:
-            f.write(json.dumps(line) + "\n")
+    qt.emit(line)
+    qt.write(args, [line])
     env.close()
 
 

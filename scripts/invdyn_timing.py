@@ -11,76 +11,27 @@ written / 8 TB/s (HBM3E peak of the MI355X), their ratio and the ratio to the ya
 written once per launch and never read back; the inputs (q, qd, qdd: 312 B per row) are of the size of tau (104 B per row), so
 for tau the floor of the whole traffic is up to 4 x the write floor stated.  The figures in DESIGN.md ("Measurements: inverse
 dynamics") and profiles/inverse_dynamics/README.md come from this script."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
+import query_timing as qt
+import torch
 
 BLOCK = 20
 PEAK_BPS = 8.0e12
 YARDSTICK = "mass matrix + gravity"
-
-
-def time_block(fn, n):
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(n):
-        fn()
-    t1.record()
-    t1.synchronize()
-    return t0.elapsed_time(t1) * 1000.0          # us
-
-
-def measure(fn, launches):
-    fn()
-    time_block(fn, BLOCK)                        # warm-up
-    blocks = max(1, (launches + BLOCK - 1) // BLOCK)
-    return sum(time_block(fn, BLOCK) for _ in range(blocks)) / (blocks * BLOCK)
-
-
-def table(lines):
-    out = ["| N | case | rows | MB written | µs | floor µs | ratio to floor | ratio to M + gravity |", "|---|---|---|---|---|---|---|---|"]
-    for x in lines:
-        out.append(f"| {x['num_envs']} | {x['case']} | {x['rows']} | {x['MB_written']} | {x['us']} | {x['floor_us_at_8TBps']} | {x['ratio']} "
-                   f"| {x['ratio_to_mass_matrix']} |")
-    return "\n".join(out) + "\n"
+COLUMNS = [("N", "num_envs"), ("case", "case"), ("rows", "rows"), ("MB written", "MB_written"), ("µs", "us"),
+           ("floor µs", "floor_us_at_8TBps"), ("ratio to floor", "ratio"), ("ratio to M + gravity", "ratio_to_mass_matrix")]
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--num-envs", type=int, nargs="+", default=[4096, 16384])
-    ap.add_argument("--override-rows", type=int, default=65536)
-    ap.add_argument("--launches", type=int, default=200)
-    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
-    ap.add_argument("--readme", default=None, help="write the table of this run (markdown) to this file")
-    args = ap.parse_args()
+    args = qt.parser(launches=200, num_envs=[4096, 16384], override_rows=True, readme=True).parse_args()
     from dexrobot_isaac_amd import _abi
-    from dexrobot_isaac_amd.config import build_sim_config, default_cfg
-    from dexrobot_isaac_amd.core import DexSimCore
     from dexrobot_isaac_amd.hand_model import BODY_NAMES, FINGERTIP_BODY_NAMES
-    dev = "cuda:0"
+    dev = qt.DEV
     NJ, NB = _abi.NJ, _abi.NUM_HAND_BODIES
     six = [BODY_NAMES.index(n) for n in ["right_hand_base"] + FINGERTIP_BODY_NAMES]
     lines = []
     for n in args.num_envs:
-        cfg = default_cfg("BlindGrasping")
-        cfg["env"]["numEnvs"] = n
-        sc, model = build_sim_config(cfg)
-        core = DexSimCore(sc, model.to_struct(), dev)
-        core.reset()
-        g = torch.Generator(device=dev).manual_seed(0)
-        lo = torch.tensor(list(core.model.lo), device=dev)
-        hi = torch.tensor(list(core.model.hi), device=dev)
-        rates = lambda rows, a: a * (2 * torch.rand(rows, NJ, device=dev, generator=g) - 1)
-        core.dof_state[:, :, 0] = lo + (hi - lo) * torch.rand(n, NJ, device=dev, generator=g)
-        core.dof_state[:, :, 1] = rates(n, 3.0)
-        core.set_dof_state_indexed(torch.arange(n, device=dev))
-        qdd = rates(n, 10.0)
+        core, draws = qt.posed_core(n, speed=3.0)
+        qdd = draws.sym(10.0, n, NJ)
         tau = torch.empty(n, NJ, device=dev)
         a6, a37 = torch.empty(n, 6, 6, device=dev), torch.empty(n, NB, 6, device=dev)
         M, grav = torch.empty(n, NJ, NJ, device=dev), torch.empty(n, NJ, device=dev)
@@ -93,35 +44,26 @@ def main():
         ]
         if n == args.num_envs[-1]:
             k = args.override_rows
-            qo = lo + (hi - lo) * torch.rand(k, NJ, device=dev, generator=g)
-            vo, ao = rates(k, 3.0), rates(k, 10.0)
+            qo = draws.pose(k)
+            vo, ao = draws.sym(3.0, k, NJ), draws.sym(10.0, k, NJ)
             to = torch.empty(k, NJ, device=dev)
             Mo, go = torch.empty(k, NJ, NJ, device=dev), torch.empty(k, NJ, device=dev)
             cases.append(("tau = M qdd + c + g, overrides", k, to.numel() * 4, lambda: core.inverse_dynamics(to, qdd=ao, q=qo, qd=vo)))
             cases.append((YARDSTICK + ", q override", k, (Mo.numel() + go.numel()) * 4, lambda: core.mass_matrix(mass=Mo, gravity=go, q=qo)))
         block = []
         for name, rows, nbytes, fn in cases:
-            us = measure(fn, args.launches)
+            us = qt.measure(fn, args.launches, BLOCK)
             floor = nbytes / PEAK_BPS * 1e6
             block.append({"num_envs": n, "case": name, "rows": rows, "MB_written": round(nbytes / 1e6, 2), "us": round(us, 1),
                           "floor_us_at_8TBps": round(floor, 2), "ratio": round(us / floor, 1)})
-        for x in block:   # against the yardstick of the same row count
-            ref = next(y for y in block if y["case"].startswith(YARDSTICK) and y["rows"] == x["rows"])
-            x["ratio_to_mass_matrix"] = round(x["us"] / ref["us"], 2)
-            print(json.dumps(x), flush=True)
+        qt.add_ratio(block, "ratio_to_mass_matrix", YARDSTICK, 2)   # against the yardstick of the same row count
+        for x in block:
+            qt.emit(x)
         lines += block
         core.close()
         del core, tau, a6, a37, M, grav
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
-    if args.readme:
-        os.makedirs(os.path.dirname(os.path.abspath(args.readme)), exist_ok=True)
-        with open(args.readme, "w") as f:
-            f.write(table(lines))
+    qt.write(args, lines, COLUMNS)
 
 
 if __name__ == "__main__":

@@ -7,41 +7,14 @@ and through the q / box_pose override fed the same state.  Timing: HIP events ar
 block; `--launches` calls per figure.  One JSON line: microseconds per call for all three outputs on both paths and for each output
 alone, and the bytes a call writes.  The figures in DESIGN.md ("Measurements: clearance queries") and profiles/proximity come from
 this script."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
-
-
-def time_block(fn, n):
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(n):
-        fn()
-    t1.record()
-    t1.synchronize()
-    return t0.elapsed_time(t1) * 1000.0          # us
-
-
-def measure(fn, launches, block):
-    time_block(fn, block)                        # warm-up
-    blocks = max(1, (launches + block - 1) // block)
-    return sum(time_block(fn, block) for _ in range(blocks)) / (blocks * block)
+import query_timing as qt
+import torch
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", type=int, default=4096)
-    ap.add_argument("--launches", type=int, default=200)
-    ap.add_argument("--out", default=None, help="also append the JSON line to this file")
-    args = ap.parse_args()
+    args = qt.parser(launches=200, rows=4096).parse_args()
     from dexrobot_isaac_amd import _abi, make_env
-    dev = "cuda:0"
+    dev = qt.DEV
     k = args.rows
     env = make_env("BlindGrasping", k, dev, dev, 0)
     env.reset()
@@ -59,20 +32,15 @@ def main():
         cases[name + "_us"] = (lambda name=name, t=t: core.proximity(**{name: t}))
     line = {"rows": k, "launches": args.launches, "bytes_written": sum(t.numel() * 4 for t in bufs.values())}
     for name, fn in cases.items():
-        fn()
-        torch.cuda.synchronize()
-        line[name] = round(measure(fn, args.launches, 20), 1)
+        line[name] = round(qt.measure(fn, args.launches, 20), 1)
     state = {n: t.clone() for n, t in bufs.items()}
     core.proximity(q=q, box_pose=box, **bufs)
     torch.cuda.synchronize()
     line["override_equals_state_bitwise"] = all(torch.equal(state[n].view(torch.int32), bufs[n].view(torch.int32)) for n in bufs)
     line["min_box_distance_m"] = float(f"{float(bufs['cap_env'][:, :, 0, 0].min()):.4g}")
     line["min_self_distance_m"] = float(f"{float(bufs['pair_dist'].min()):.4g}")
-    print(json.dumps(line))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a") as f:
-            f.write(json.dumps(line) + "\n")
+    qt.emit(line)
+    qt.write(args, [line])
     env.close()
 
 

@@ -6,56 +6,30 @@ Per case: HIP events around blocks of 20 back-to-back launches, alternating with
 with as many bytes as the case moves one way (record_words * 4 * lanes), after a warm-up block of each; the mean per launch of
 both and their ratio are printed as one JSON line per case.  The figures in DESIGN.md ("Measurements: state save / load / fork")
 come from this script."""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
+import query_timing as qt
+import torch
 
 BLOCK = 20
 
 
-def time_block(fn, n):
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(n):
-        fn()
-    t1.record()
-    t1.synchronize()
-    return t0.elapsed_time(t1) * 1000.0          # us
-
-
 def measure(fn, base, launches):
+    """query_timing.measure with the blocks of `fn` and of `base` alternating, so that both see the same session: (us, base us)."""
     fn(); base()
-    time_block(fn, BLOCK); time_block(base, BLOCK)           # warm-up
+    qt.time_block(fn, BLOCK); qt.time_block(base, BLOCK)           # warm-up
     tf = tb = 0.0
     blocks = max(1, (launches + BLOCK - 1) // BLOCK)
     for _ in range(blocks):
-        tf += time_block(fn, BLOCK)
-        tb += time_block(base, BLOCK)
+        tf += qt.time_block(fn, BLOCK)
+        tb += qt.time_block(base, BLOCK)
     return tf / (blocks * BLOCK), tb / (blocks * BLOCK)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--num-envs", type=int, nargs="+", default=[4096, 65536])
-    ap.add_argument("--launches", type=int, default=100)
-    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
-    args = ap.parse_args()
-    from dexrobot_isaac_amd.config import build_sim_config, default_cfg
-    from dexrobot_isaac_amd.core import DexSimCore
-    dev = "cuda:0"
+    args = qt.parser(launches=100, num_envs=[4096, 65536]).parse_args()
+    dev = qt.DEV
     lines = []
     for n in args.num_envs:
-        cfg = default_cfg("BlindGrasping")
-        cfg["env"]["numEnvs"] = n
-        sc, model = build_sim_config(cfg)
-        core = DexSimCore(sc, model.to_struct(), dev)
-        core.reset()
+        core = qt.blind_grasping_core(n)
         _, words = core.state_layout()
         bank = core.state_bank(core.NS)
         core.save_state(bank)
@@ -81,17 +55,13 @@ def main():
             us, base_us = measure(fn, lambda: dst.copy_(src), args.launches)
             line = {"num_envs": n, "case": name, "lanes": lanes, "MB": round(nbytes / 1e6, 2), "us": round(us, 1),
                     "copy_us": round(base_us, 1), "ratio": round(us / base_us, 2), "GBps_one_way": round(nbytes / us / 1e3, 1)}
-            print(json.dumps(line), flush=True)
+            qt.emit(line)
             lines.append(line)
             del src, dst
         core.close()
         del core, bank, small
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+    qt.write(args, lines)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """What the tests of the query kernels share (test_render, test_kindyn, test_ik, test_proximity, test_inverse_dynamics,
 test_forward_dynamics): the queries are pure functions of q (and qd) that write caller-owned memory only, so every suite loads the
 library, poses cores, stubs the core under DexHandEnv, puts its outputs between guard rows and checks that nothing of the instance
-changed in the same way.  A plain module: no fixtures."""
+changed in the same way (purity_frame: a suite passes its calls).  A plain module: no fixtures."""
 import numpy as np
 
 from dexrobot_isaac_amd.config import build_sim_config, default_cfg
@@ -93,3 +93,36 @@ def snapshot(core):
 def same(a, b):
     import torch
     return all((a[k] == b[k]) if k == "stamp" else torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
+
+
+def purity_frame(calls, between=None, n=70, seed=4, steps=(3, 5)):
+    """The queries are pure and deterministic: two cores of n BlindGrasping envs, reset and stepped steps[0] times with the same
+    seeded actions; on one of them `calls(core)` (a list of host arrays), `between(core)` (the same queries on other rows and
+    with other arguments) and `calls(core)` again.  Nothing of the instance changed, the two results are bit-identical, and
+    after steps[1] more steps the core equals the twin that never made a call.  Returns the first result for the caller's own
+    assertions on it."""
+    import torch
+    from dexrobot_isaac_amd.core import DexSimCore
+    sc, ms = setup(n)
+    core, twin = DexSimCore(sc, ms, "cuda:0"), DexSimCore(sc, ms, "cuda:0")
+    g = torch.Generator().manual_seed(seed)
+    acts = [(2 * torch.rand(n, 18, generator=g) - 1).cuda() for _ in range(sum(steps))]
+    for c in (core, twin):
+        c.reset()
+        for a in acts[:steps[0]]:
+            c.step(a)
+    before = snapshot(core)
+    first = calls(core)
+    if between is not None:
+        between(core)
+    second = calls(core)
+    assert same(before, snapshot(core))                                        # nothing of the instance changed
+    raw = lambda a: np.ascontiguousarray(a).view(np.uint8)
+    assert len(first) == len(second) and all((raw(x) == raw(y)).all() for x, y in zip(first, second))   # two calls on one state: bit-identical
+    for a in acts[steps[0]:]:
+        core.step(a)
+        twin.step(a)
+    assert same(snapshot(core), snapshot(twin))                                # ... and the run continues like a twin that never called them
+    for c in (core, twin):
+        c.close()
+    return first

@@ -29,6 +29,16 @@ def test_header_symbols_are_exported(lib):
         assert hasattr(lib, sym), sym
 
 
+def test_prototype_table_has_the_header_arity():
+    """Every declaration of include/dexsim.h has as many parameters as its row of _abi.PROTOTYPES has argtypes."""
+    hdr = open(os.path.join(ROOT, "include", "dexsim.h")).read()
+    declared = re.findall(r"\b(dexsim_[a-z_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert {name for name, _ in declared} == set(_abi.PROTOTYPES)
+    for name, params in declared:
+        arity = 0 if params.strip() == "void" else len(params.split(","))
+        assert arity == len(_abi.PROTOTYPES[name]), name
+
+
 def test_struct_sizes_match(lib):
     _abi.check_struct_sizes(lib)
 

@@ -34,8 +34,8 @@ from tests import dynderiv_ref as dd
 from tests import fwddyn_ref as fr
 from tests import invdyn_ref as ir
 from tests import kindyn_ref as kr
-from tests.query_rig import (bits, dev as _dev, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, same as _same, setup as _setup,
-                             snapshot as _snapshot, stub_core)
+from tests.query_rig import (bits, dev as _dev, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, purity_frame,
+                             setup as _setup, stub_core)
 
 N = 70
 NJ = _abi.NJ
@@ -465,34 +465,18 @@ def test_addressing(posed):
 @pytest.mark.gpu
 def test_purity():
     import torch
-    from dexrobot_isaac_amd.core import DexSimCore
-    sc, ms = _setup(N)
-    core, twin = DexSimCore(sc, ms, "cuda:0"), DexSimCore(sc, ms, "cuda:0")
-    g = torch.Generator().manual_seed(4)
-    acts = [(2 * torch.rand(N, 18, generator=g) - 1).cuda() for _ in range(8)]
-    for c in (core, twin):
-        c.reset()
-        for a in acts[:3]:
-            c.step(a)
-    before = _snapshot(core)
     rng = np.random.default_rng(41)
     qdd, tau = rng.uniform(-1, 1, (N, NJ)).astype(f32), rng.uniform(-1, 1, (N, NJ)).astype(f32)
-    a1, b1 = gpu_idd(core, N, qdd=qdd), gpu_fdd(core, N, tau=tau)
-    gpu_idd(core, 3, env_ids=[69, 1, 64], gravity=False, which=(False, True))
-    gpu_fdd(core, 3, env_ids=[69, 1, 64], gravity=False, armature=True, which=(True, False))
     rnd = lambda *s: torch.rand(*s, device="cuda:0")
-    gpu_idd(core, 100, q=rnd(100, NJ), qd=rnd(100, NJ), qdd=rnd(100, NJ))
-    gpu_fdd(core, 100, q=rnd(100, NJ), qd=rnd(100, NJ), tau=rnd(100, NJ))
-    a2, b2 = gpu_idd(core, N, qdd=qdd), gpu_fdd(core, N, tau=tau)
-    assert _same(before, _snapshot(core))                                      # nothing of the instance changed
-    assert all((bits(x) == bits(y)).all() for x, y in zip(a1 + b1, a2 + b2))
-    assert not any(np.isnan(x).any() for x in a1 + b1) and np.abs(a1[0]).max() > 0 and np.abs(b1[1]).max() > 0
-    for a in acts[3:]:
-        core.step(a)
-        twin.step(a)
-    assert _same(_snapshot(core), _snapshot(twin))                             # ... and the run continues like a twin that never called them
-    for c in (core, twin):
-        c.close()
+
+    def between(core):
+        gpu_idd(core, 3, env_ids=[69, 1, 64], gravity=False, which=(False, True))
+        gpu_fdd(core, 3, env_ids=[69, 1, 64], gravity=False, armature=True, which=(True, False))
+        gpu_idd(core, 100, q=rnd(100, NJ), qd=rnd(100, NJ), qdd=rnd(100, NJ))
+        gpu_fdd(core, 100, q=rnd(100, NJ), qd=rnd(100, NJ), tau=rnd(100, NJ))
+    got = purity_frame(lambda core: [*gpu_idd(core, N, qdd=qdd), *gpu_fdd(core, N, tau=tau)], between, n=N)
+    a1, b1 = got[:2], got[2:]                                                  # (dtau_dq, dtau_dqd), (qdd, dqdd_dq, dqdd_dqd)
+    assert len(b1) == 3 and not any(np.isnan(x).any() for x in a1 + b1) and np.abs(a1[0]).max() > 0 and np.abs(b1[1]).max() > 0
 
 
 @pytest.mark.gpu

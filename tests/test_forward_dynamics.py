@@ -36,8 +36,8 @@ from oracle.oracle import Oracle
 from tests import fwddyn_ref as fr
 from tests import invdyn_ref as ir
 from tests import kindyn_ref as kr
-from tests.query_rig import (bits, dev as _dev, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, same as _same, setup as _setup,
-                             snapshot as _snapshot, stub_core)
+from tests.query_rig import (bits, dev as _dev, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, purity_frame,
+                             setup as _setup, stub_core)
 
 N = 70
 NJ = _abi.NJ
@@ -440,34 +440,17 @@ def test_addressing(posed):
 @pytest.mark.gpu
 def test_purity():
     import torch
-    from dexrobot_isaac_amd.core import DexSimCore
-    sc, ms = _setup(N)
-    core, twin = DexSimCore(sc, ms, "cuda:0"), DexSimCore(sc, ms, "cuda:0")
-    g = torch.Generator().manual_seed(4)
-    acts = [(2 * torch.rand(N, 18, generator=g) - 1).cuda() for _ in range(8)]
-    for c in (core, twin):
-        c.reset()
-        for a in acts[:3]:
-            c.step(a)
-    before = _snapshot(core)
     rng = np.random.default_rng(41)
     tau, rhs = rng.uniform(-1, 1, (N, NJ)).astype(np.float32), rng.uniform(-1, 1, (N, 5, NJ)).astype(np.float32)
-    x1, m1 = gpu_fd(core, N, tau=tau), gpu_ms(core, N, rhs)
-    gpu_fd(core, 3, env_ids=[69, 1, 64], gravity=False, armature=True)
-    gpu_ms(core, 3, rhs[:3], env_ids=[69, 1, 64], armature=True)
     rnd = lambda *s: torch.rand(*s, device="cuda:0")
-    gpu_fd(core, 100, q=rnd(100, NJ), qd=rnd(100, NJ), tau=rnd(100, NJ))
-    gpu_ms(core, 100, rnd(100, 32, NJ).cpu().numpy(), q=rnd(100, NJ), in_place=True)
-    x2, m2 = gpu_fd(core, N, tau=tau), gpu_ms(core, N, rhs)
-    assert _same(before, _snapshot(core))                                      # nothing of the instance changed
-    assert (bits(x1) == bits(x2)).all() and (bits(m1) == bits(m2)).all()
+
+    def between(core):
+        gpu_fd(core, 3, env_ids=[69, 1, 64], gravity=False, armature=True)
+        gpu_ms(core, 3, rhs[:3], env_ids=[69, 1, 64], armature=True)
+        gpu_fd(core, 100, q=rnd(100, NJ), qd=rnd(100, NJ), tau=rnd(100, NJ))
+        gpu_ms(core, 100, rnd(100, 32, NJ).cpu().numpy(), q=rnd(100, NJ), in_place=True)
+    x1, m1 = purity_frame(lambda core: [gpu_fd(core, N, tau=tau), gpu_ms(core, N, rhs)], between, n=N)
     assert not np.isnan(x1).any() and not np.isnan(m1).any() and np.abs(x1).max() > 0
-    for a in acts[3:]:
-        core.step(a)
-        twin.step(a)
-    assert _same(_snapshot(core), _snapshot(twin))                             # ... and the run continues like a twin that never called them
-    for c in (core, twin):
-        c.close()
 
 
 @pytest.mark.gpu

@@ -18,8 +18,8 @@ import pytest
 
 from dexrobot_isaac_amd import _abi
 from tests import kindyn_ref as kr
-from tests.query_rig import (bits, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, same as _same, setup as _setup,
-                             snapshot as _snapshot, stub_core)
+from tests.query_rig import (bits, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, purity_frame, setup as _setup,
+                             stub_core)
 
 N = 70
 NB, NJ = _abi.NUM_HAND_BODIES, _abi.NJ
@@ -321,30 +321,12 @@ def test_addressing(posed):
 @pytest.mark.gpu
 def test_purity():
     import torch
-    from dexrobot_isaac_amd.core import DexSimCore
-    sc, ms = _setup(N)
-    core, twin = DexSimCore(sc, ms, "cuda:0"), DexSimCore(sc, ms, "cuda:0")
-    g = torch.Generator().manual_seed(4)
-    acts = [(2 * torch.rand(N, 18, generator=g) - 1).cuda() for _ in range(8)]
-    for c in (core, twin):
-        c.reset()
-        for a in acts[:3]:
-            c.step(a)
-    before = _snapshot(core)
-    j1 = gpu_jac(core, N)
-    gpu_jac(core, 3, env_ids=[69, 1, 64], bodies=[12, 18])
-    m1 = gpu_mass(core, N)
-    gpu_mass(core, 100, q=torch.rand(100, NJ, device="cuda:0"))
-    gpu_jac(core, 100, q=torch.rand(100, NJ, device="cuda:0"), bodies=[6])
-    j2, m2 = gpu_jac(core, N), gpu_mass(core, N)
-    assert _same(before, _snapshot(core))                                      # nothing of the instance changed
-    assert (bits(j1) == bits(j2)).all() and all((bits(x) == bits(y)).all() for x, y in zip(m1, m2))
-    for a in acts[3:]:
-        core.step(a)
-        twin.step(a)
-    assert _same(_snapshot(core), _snapshot(twin))                             # ... and the run continues like a twin that never called them
-    for c in (core, twin):
-        c.close()
+
+    def between(core):
+        gpu_jac(core, 3, env_ids=[69, 1, 64], bodies=[12, 18])
+        gpu_mass(core, 100, q=torch.rand(100, NJ, device="cuda:0"))
+        gpu_jac(core, 100, q=torch.rand(100, NJ, device="cuda:0"), bodies=[6])
+    purity_frame(lambda core: [gpu_jac(core, N), *gpu_mass(core, N)], between, n=N)
 
 
 @pytest.mark.gpu

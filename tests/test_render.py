@@ -23,7 +23,7 @@ from dexrobot_isaac_amd import _abi, _lib
 from dexrobot_isaac_amd.build import build_lib
 from dexrobot_isaac_amd.config import build_sim_config, default_cfg
 from tests import render_ref as rr
-from tests.query_rig import pose_core, same as _same, snapshot as _snapshot
+from tests.query_rig import pose_core, purity_frame
 
 MAX_UNSTABLE = 0.03
 
@@ -358,27 +358,8 @@ def test_no_box_and_static_box():
 
 @pytest.mark.gpu
 def test_purity_and_determinism():
-    import torch
-    n = 70
-    core, sc, _ = _core("BlindGrasping", n)
-    twin, _, _ = _core("BlindGrasping", n)
-    g = torch.Generator().manual_seed(3)
-    acts = [(2 * torch.rand(n, 18, generator=g) - 1).cuda() for _ in range(13)]
-    for a in acts[:3]:
-        core.step(a)
-        twin.step(a)
-    before = _snapshot(core)
     cam = make_camera(50, 30, eye=(-0.3, 0.25, 0.6), target=(0.0, 0.0, 0.3))
-    r1 = gpu_render(core, cam)
-    assert _same(before, _snapshot(core))                         # a render between two steps changes nothing
-    r2 = gpu_render(core, cam)
-    assert all((x.view(np.uint8) == y.view(np.uint8)).all() for x, y in zip(r1, r2))   # two renders of one state: bit-identical
-    for a in acts[3:]:
-        core.step(a)
-        twin.step(a)
-    assert _same(_snapshot(core), _snapshot(twin))                # ... and the run continues like a twin that never rendered
-    for c in (core, twin):
-        c.close()
+    purity_frame(lambda core: gpu_render(core, cam), n=70, seed=3, steps=(3, 10))     # a render between two steps changes nothing
 
 
 @pytest.mark.gpu
