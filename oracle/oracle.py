@@ -1,6 +1,7 @@
 """ctypes wrapper around the CPU oracle (oracle/dexsim_oracle.c).  TEST INFRASTRUCTURE ONLY.
 
 Imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg -- never by the product package.
+Oracle.warm_cache() returns the warm-start cache in the form of tests/hip_backend.py's, for tests/physics_rig.py.
 """
 import ctypes as C
 import os
@@ -94,6 +95,10 @@ class Oracle:
         out = np.zeros((64, 10), dtype=np.float64)     # >= DEXSIM_KMAX rows
         k = self.lib.orc_get_contacts(self.h, env, out.ctypes.data)
         return out[:k]
+
+    def warm_cache(self):
+        """The contact solver's warm-start cache, as HipBackend.warm_cache() gives it: (wlam [88 x 3][N], wtag [88][N], wgen [N])."""
+        return self.get("wlam"), self.get("wtag").astype(np.int64), self.get("wgen")[0].astype(np.int64)
 
     def obs_buf(self):
         out = np.zeros((self.n, self.num_obs), dtype=np.float32)

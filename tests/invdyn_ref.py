@@ -92,3 +92,22 @@ def err_acc(acc, acc64):
         den = np.abs(acc64[:, :, sl]).max(axis=(1, 2))
         out.append(float(np.where(den > 0, num / np.where(den > 0, den, 1.0), num).max()))
     return tuple(out)
+
+
+FACTOR = 4                 # the device may miss the fp64 reference by this many times the fp32 reference's own error
+
+
+def gpu_tau(core, k, qdd=None, env_ids=None, q=None, qd=None, gravity=True):
+    """core.inverse_dynamics into a guarded output (tests/query_rig.py), as a numpy array."""
+    from tests.query_rig import dev, guarded, guards_ok
+    full, out = guarded(k, NJ)
+    core.inverse_dynamics(out, qdd=dev(qdd), env_ids=env_ids, q=dev(q), qd=dev(qd), gravity=gravity)
+    guards_ok(full)
+    return out.cpu().numpy()
+
+
+def check_tau(tau, tau64, M64, e, what):
+    assert not np.isnan(tau).any(), f"{what}: an element was not written"
+    E = err_tau(tau, tau64, M64)
+    print(f"{what}: E_tau = {E:.3g} (fp32 oracle: {e:.3g}, bound {FACTOR * e:.3g})")
+    assert E <= FACTOR * e

@@ -94,3 +94,15 @@ def err_g(g, g64, M64):
     num = (np.abs(np.asarray(g, dtype=np.float64) - g64) / d).max(1)
     den = (np.abs(g64) / d).max(1)
     return float((num / den).max())
+
+
+def gpu_mass(core, k, env_ids=None, q=None, mass=True, gravity=True):
+    """core.mass_matrix into guarded outputs (tests/query_rig.py): (M, g) as numpy arrays, None for one not asked for."""
+    from tests.query_rig import guarded, guards_ok
+    fm, M = guarded(k, NJ, NJ) if mass else (None, None)
+    fg, g = guarded(k, NJ) if gravity else (None, None)
+    core.mass_matrix(mass=M, gravity=g, env_ids=env_ids, q=q)
+    for f in (fm, fg):
+        if f is not None:
+            guards_ok(f)
+    return (None if M is None else M.cpu().numpy()), (None if g is None else g.cpu().numpy())

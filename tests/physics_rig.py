@@ -1,0 +1,405 @@
+"""What the physics parity tests share (test_gpu_parity, test_tumbled_box, test_wide_poses, test_physics_configs, test_model_structure):
+configurations, the backends loaded with one state, snapshots, the references of the tumbled samples and the comparisons with their
+bounds.  A plain module: no fixtures, no torch at import (the HIP backend is imported where one is built).
+
+Bounds.  Integers (list length, type, capsule, corner per slot) are exact over the envs whose list length agrees in the fp64 oracle, the
+fp32 oracle and the backend under test; at most LEFT_OUT of the envs may be left out.  Points and gaps: 2e-6 m.  Normals of hand / box
+entries: C_RULE E / dist + 1e-7 with E the largest err_n dist of the fp32 oracle against the fp64 oracle on the same sample.  States: the
+error against fp64 at the 99.9th percentile and at the maximum is at most C_RULE x the fp32 oracle's own error on the same entries, plus
+the floors 1e-7 and 1e-6 (accumulate / assert_c_rule).  A helper that takes a tolerance has no default for it: the tests state them."""
+import contextlib
+import functools
+import math
+import os
+
+import numpy as np
+
+from dexrobot_isaac_amd.config import build_sim_config, default_cfg
+from dexrobot_isaac_amd.hand_model import HandModel, rot_z
+from tests import tumbled_states as ts
+from tests.tumbled_states import f32
+
+N, SEED = 256, 11                  # the tumbled samples: four workgroups, every box class in each
+C_RULE = 3.0                       # test_gpu_parity.py::test_hip_error_is_a_small_multiple_of_fp32_roundoff derives it
+LEFT_OUT = 0.02
+SYNC = ("q", "qd", "box_pos", "box_quat", "box_lin", "box_ang")
+FIELDS = SYNC + ("cforce",)
+BOX_FIELDS = ("box_pos", "box_quat", "box_lin", "box_ang")
+
+
+# ------------------------------------------------------------------------------------------------- hand models without the folded structure
+SWITCH = "DEXSIM_GENERAL_MODEL_PATH"
+
+
+@contextlib.contextmanager
+def general_path():
+    """dexsim_create inside the block clears the model classification (tests/test_model_structure.py)."""
+    old = os.environ.get(SWITCH)
+    os.environ[SWITCH] = "1"
+    try:
+        yield
+    finally:
+        if old is None:
+            del os.environ[SWITCH]
+        else:
+            os.environ[SWITCH] = old
+
+
+def _tilt_axis(m, j):          # a flexion axis tilted by 1e-2 rad, renormalised
+    a = np.array([0.0, -math.cos(1e-2), math.sin(1e-2)])
+    m.jaxis[j] = a / np.linalg.norm(a)
+
+
+def _break_poff4(m):
+    m.jpoff[4] = (0.0, 2e-3, 0.0)
+
+
+def _break_axis(m):
+    _tilt_axis(m, 6 + 4 * 1 + 1)
+
+
+def _break_qoff(m):
+    j = 6 + 4 * 2 + 2
+    m.jRoff[j] = m.jRoff[j] @ rot_z(1e-2)
+
+
+def _break_com(m):
+    m.com[6 + 4 * 3 + 2, 1] = 1e-3
+
+
+def _break_all(m):
+    _break_poff4(m), _break_axis(m), _break_qoff(m), _break_com(m)
+
+
+def _mixed(m):                 # fingers 1 and 3 lack the structure, 2 and 4 (and the thumb) keep it
+    m.com[6 + 4 * 1 + 3, 1] = 1e-3
+    _tilt_axis(m, 6 + 4 * 3 + 2)
+
+
+_ROT = (math.sin(0.05) / math.sqrt(2.0), math.sin(0.05) / math.sqrt(2.0), 0.0, math.cos(0.05))   # 0.1 rad about (1, 1, 0)
+MODELS = {
+    "poff4": (_break_poff4, None), "axis": (_break_axis, None), "qoff": (_break_qoff, None), "com": (_break_com, None),
+    "hand_rot": (None, _ROT), "all": (_break_all, _ROT), "mixed": (_mixed, None),
+}
+
+
+# ------------------------------------------------------------------------------------------------- configuration
+@functools.lru_cache(maxsize=None)
+def setup(task, n, model=None, ground_friction=None, hand_friction=None, **over):
+    """(sc, model, ms) of n envs, built once per process.  `over`: dotted keys into default_cfg(task), list indices included
+    ("sim.gravity.0"); `model`: a name of MODELS; ground_friction (hard-wired in config.py) and hand_friction (fixed by the MJCF-less
+    model) are set on the built DexSimConfig / HandModel before to_struct()."""
+    cfg = default_cfg(task)
+    cfg["env"]["numEnvs"] = n
+    for key, value in over.items():
+        d, parts = cfg, key.split(".")
+        for p in parts[:-1]:
+            d = d[p]
+        d[int(parts[-1]) if isinstance(d, list) else parts[-1]] = value
+    hand = None
+    if model is not None:
+        edit, rot = MODELS[model]
+        if rot is not None:
+            cfg["env"]["initialHandRot"] = list(rot)
+        hand = HandModel(cfg["env"]["initialHandPos"], cfg["env"]["initialHandRot"])
+        if edit is not None:
+            edit(hand)
+    sc, hand = build_sim_config(cfg, model=hand)
+    if ground_friction is not None:
+        sc.ground_friction = ground_friction
+    if hand_friction is not None:
+        hand.hand_friction = hand_friction
+    return sc, hand, hand.to_struct()
+
+
+# ------------------------------------------------------------------------------------------------- backends and state
+def load(b, st):
+    for k, v in st.items():
+        b.set(k, v)
+
+
+def hip(sc, ms, fused=True):
+    from tests.hip_backend import HipBackend
+    return HipBackend(sc, ms, fused=fused)
+
+
+def backends(sc, ms, st=None, f64=False, fused=True, threads=0):
+    """(fp32 oracle, HipBackend) -- with f64 = True (fp64 oracle, fp32 oracle, HipBackend) -- each loaded with the state `st`."""
+    from oracle.oracle import Oracle
+    out = ((Oracle(sc, ms, f64=True, threads=threads),) if f64 else ()) + (Oracle(sc, ms, threads=threads), hip(sc, ms, fused))
+    for b in out:
+        load(b, st or {})
+    return out
+
+
+def random_state(rng, model, n, near_box=True):
+    """A spread of physically meaningful states: hand above / beside / pressing on the box."""
+    q = rng.uniform(0.0, 0.5, (26, n))
+    q[:3] = rng.uniform(-0.15, 0.15, (3, n))
+    q[2] = rng.uniform(-0.42, -0.2, n) if near_box else rng.uniform(-0.2, 0.2, n)
+    q[3:6] = rng.uniform(-0.3, 0.3, (3, n))
+    q = np.clip(q, model.lo[:, None] + 1e-3, model.hi[:, None] - 1e-3)
+    qd = rng.normal(0, 0.3, (26, n))
+    tg = q + rng.normal(0, 0.05, (26, n))
+    box_pos = np.stack([rng.uniform(-0.03, 0.03, n), rng.uniform(-0.03, 0.03, n), rng.uniform(0.0245, 0.03, n)])
+    yaw = rng.uniform(-np.pi, np.pi, n)
+    box_quat = np.stack([0 * yaw, 0 * yaw, np.sin(yaw / 2), np.cos(yaw / 2)])
+    return dict(q=q, qd=qd, targets=tg, box_pos=box_pos, box_quat=box_quat,
+                box_lin=rng.normal(0, 0.05, (3, n)), box_ang=rng.normal(0, 0.3, (3, n)))
+
+
+def lowered_hand_state(rng, n, z, dz, rot):
+    """The hand at rest, lowered to z + U(-dz, dz) over the upright box at rest at the origin: base rotations U(-rot, rot), finger
+    joints U(0, 0.3), every target on its joint."""
+    q = np.zeros((26, n))
+    q[2] = z + rng.uniform(-dz, dz, n)
+    q[3:6] = rng.uniform(-rot, rot, (3, n))
+    q[6:] = rng.uniform(0, 0.3, (20, n))
+    return dict(q=q, qd=0 * q, targets=q, box_pos=np.array([[0.0], [0.0], [0.0255]]) + 0 * q[:3],
+                box_quat=np.array([[0.0], [0.0], [0.0], [1.0]]) + 0 * q[:4], box_lin=0 * q[:3], box_ang=0 * q[:3])
+
+
+def tumbled_state(kind, n, seed=SEED, **cfg):
+    """The first n envs of the N-env sample of tests/tumbled_states.py drawn for the BlindGrasping configuration setup(..., **cfg)."""
+    sc, model, _ = setup("BlindGrasping", N, **cfg)
+    return {k: v[:, :n].copy() for k, v in ts.sample(kind, N, seed, config=(sc, model)).items()}
+
+
+# ------------------------------------------------------------------------------------------------- snapshots
+def lists(b, n):
+    return [b.contacts(e).copy() for e in range(n)]
+
+
+def bg_cache(b):
+    """Warm-start cache of the box / ground slots 80-83: impulses (12, n) and the corner each slot holds (4, n), -1 = not valid."""
+    lam, tag, gen = b.warm_cache()
+    tag = tag[80:84]
+    return lam[240:252].copy(), np.where((tag >> 3) == gen[None, :], tag & 7, -1)
+
+
+def snap(b, fields=FIELDS):
+    s = {f: b.get(f) for f in fields}
+    s["ncontact"] = b.get("ncontact")[0].astype(int)
+    s["lam"], s["corner"] = bg_cache(b)
+    return s
+
+
+# ------------------------------------------------------------------------------------------------- references, computed once
+def teacher_ref(sc, ms, start):
+    """Three teacher-forced sub-steps on the fp64 and the fp32 oracle (fresh instances): after each, q, qd and the box state of both
+    are put to the fp64 oracle's values rounded to float32, so that every sub-step starts from one state.  Per sub-step: the
+    float32 state it started from, both snapshots and (first sub-step) both contact lists."""
+    from oracle.oracle import Oracle
+    n = int(sc.num_envs)
+    o64, o32 = Oracle(sc, ms, f64=True), Oracle(sc, ms)
+    load(o64, start), load(o32, start)
+    out = []
+    for sub in range(3):
+        o64.substep(last=True), o32.substep(last=True)
+        rec = dict(start=start, s64=snap(o64), s32=snap(o32))
+        if sub == 0:
+            rec["lists64"], rec["lists32"] = lists(o64, n), lists(o32, n)
+            _, rec["wtag64"], rec["wgen64"] = o64.warm_cache()
+        out.append(rec)
+        start = {k: f32(o64.get(k)) for k in SYNC}
+        load(o64, start), load(o32, start)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def tumbled_teacher_ref(kind, n, seed=SEED, **cfg):
+    """teacher_ref of the tumbled sample `kind`, first n envs, at the configuration setup("BlindGrasping", n, **cfg)."""
+    sc, _, ms = setup("BlindGrasping", n, **cfg)
+    return teacher_ref(sc, ms, tumbled_state(kind, n, seed, **cfg))
+
+
+@functools.lru_cache(maxsize=None)
+def tumbled_free_ref(kind, n, steps, fields=FIELDS, seed=SEED, **cfg):
+    """The tumbled sample free-running for `steps` physics steps (sim.substeps sub-steps each) on both oracles: snapshots after each."""
+    from oracle.oracle import Oracle
+    sc, _, ms = setup("BlindGrasping", n, **cfg)
+    o64, o32 = Oracle(sc, ms, f64=True), Oracle(sc, ms)
+    st = tumbled_state(kind, n, seed, **cfg)
+    load(o64, st), load(o32, st)
+    out = []
+    for _ in range(steps):
+        o64.physics_step(), o32.physics_step()
+        out.append(dict(s64=snap(o64, fields), s32=snap(o32, fields)))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------- comparisons: contact lists
+def same_lists(a, b):
+    return a.shape == b.shape and bool((a[:, 8] == b[:, 8]).all()) and bool((a[a[:, 8] != 2, 9] == b[a[:, 8] != 2, 9]).all())
+
+
+def assert_same_entries(co, ch, atol):
+    """The list `ch` under test against the oracle's `co`, entry by entry: type exact, capsule id of the hand entries exact (it is
+    undefined for box / ground), point, normal, gap and friction within atol."""
+    assert co.shape == ch.shape
+    assert (co[:, 8] == ch[:, 8]).all()
+    hand = co[:, 8] != 2
+    assert (co[hand, 9] == ch[hand, 9]).all()
+    np.testing.assert_allclose(ch[:, :8], co[:, :8], atol=atol)
+
+
+def dist(row, sc, ms):
+    """gap + rest_offset + capsule radius of a hand / box entry: the distance of the axis point from the box."""
+    return row[6] + float(sc.rest_offset) + float(ms.cap_r[int(row[9])])
+
+
+def normal_scale(lists64, lists32, envs, sc, ms):
+    """E: the largest err_n dist of the fp32 oracle's hand / box normals against the fp64 oracle's."""
+    E = 0.0
+    for e in envs:
+        for r64, r32 in zip(lists64[e], lists32[e]):
+            if r64[8] == 1:
+                E = max(E, np.abs(r32[3:6] - r64[3:6]).max() * dist(r64, sc, ms))
+    return E
+
+
+def agree(same, *counts):
+    for a in counts[1:]:
+        same = same & (counts[0] == a)
+    assert 1.0 - same.mean() <= LEFT_OUT, f"{(~same).sum()} of {same.size} envs left out"
+    return same
+
+
+def check_manifold(b, rec, sc, ms):
+    """The backend under test `b` has taken the first teacher-forced sub-step of a hand-on-box sample: its list of every env against
+    the fp64 oracle's."""
+    n = len(rec["lists64"])
+    got = lists(b, n)
+    same = agree(np.ones(n, bool), rec["s64"]["ncontact"], rec["s32"]["ncontact"], np.array([len(c) for c in got]))
+    envs = np.nonzero(same)[0]
+    _, corner = bg_cache(b)
+    assert (corner[:, same] == rec["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
+    E = normal_scale(rec["lists64"], rec["lists32"], envs, sc, ms)
+    worst, worst_pg, entries = 0.0, 0.0, 0
+    for e in envs:
+        co, ch = rec["lists64"][e], got[e]
+        assert same_lists(co, ch), e                                             # type, and capsule of the hand entries
+        if not len(co):
+            continue
+        worst_pg = max(worst_pg, np.abs(ch[:, [0, 1, 2, 6]] - co[:, [0, 1, 2, 6]]).max())
+        np.testing.assert_allclose(ch[:, [0, 1, 2, 6, 7]], co[:, [0, 1, 2, 6, 7]], rtol=0, atol=2e-6)
+        for ro, rh in zip(co, ch):
+            err = np.abs(rh[3:6] - ro[3:6]).max()
+            if ro[8] == 1:
+                d = dist(ro, sc, ms)
+                worst = max(worst, err * d)
+                assert err <= C_RULE * E / d + 1e-7, (e, int(ro[9]), err, d, E)
+            else:
+                assert err <= 1e-7, (e, err)                                     # the ground's normal
+        entries += len(co)
+    print(f"\n{entries} entries in {len(envs)} envs; E = {E:.3e} m, worst err_n dist under test {worst:.3e} m, points / gaps {worst_pg:.2e}")
+    assert entries > 3 * n
+
+
+# ------------------------------------------------------------------------------------------------- comparisons: states by the c rule
+def accumulate(report, name, ref, a32, ah, mask):
+    e32, eh = np.abs(a32 - ref)[mask].ravel(), np.abs(ah - ref)[mask].ravel()
+    if not e32.size:
+        return
+    r = report.setdefault(name, [0.0, 0.0, 0.0, 0.0])
+    r[0], r[1] = max(r[0], np.percentile(e32, 99.9)), max(r[1], np.percentile(eh, 99.9))
+    r[2], r[3] = max(r[2], e32.max()), max(r[3], eh.max())
+
+
+def accumulate_snap(report, s64, s32, sh, same, fields):
+    for f in fields:
+        accumulate(report, f, s64[f], s32[f], sh[f], np.broadcast_to(same, s64[f].shape))
+    # cached impulses of the box / ground slots that hold the same corner in all three
+    ok = (s64["corner"] >= 0) & (s64["corner"] == s32["corner"]) & (s64["corner"] == sh["corner"]) & same
+    accumulate(report, "wlam 80-83", s64["lam"], s32["lam"], sh["lam"], np.repeat(ok, 3, axis=0))
+
+
+def assert_c_rule(report, label):
+    print(f"\n{label}\nfield: p99.9 |f32-f64|, p99.9 |under test-f64|, max |f32-f64|, max |under test-f64|, ratios")
+    for f, r in report.items():
+        print(f"  {f:10s} {r[0]:.3e} {r[1]:.3e} {r[2]:.3e} {r[3]:.3e}   {r[1] / max(r[0], 1e-30):.2f} {r[3] / max(r[2], 1e-30):.2f}")
+    for f, r in report.items():
+        assert r[1] <= C_RULE * r[0] + 1e-7, (f, r)
+        assert r[3] <= C_RULE * r[2] + 1e-6, (f, r)
+
+
+def check_teacher_forced(make, recs, kind, label=""):
+    """The backend that make() returns through the teacher-forced sub-steps of the references `recs` (teacher_ref): contact counts
+    over the envs that agree, slot corners exact, states by the c rule."""
+    n = recs[0]["s64"]["ncontact"].size
+    b = make()
+    same, report = np.ones(n, bool), {}
+    for rec in recs:
+        load(b, rec["start"])
+        b.substep(last=True)
+        sh = snap(b)
+        if kind == "box_alone":
+            assert sh["ncontact"].max() <= 4 and rec["s64"]["ncontact"].max() <= 4       # the early box solve really ran
+        same = agree(same, rec["s64"]["ncontact"], rec["s32"]["ncontact"], sh["ncontact"])   # (an env left out stays out: its cache differs)
+        assert (sh["corner"][:, same] == rec["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
+        accumulate_snap(report, rec["s64"], rec["s32"], sh, same, FIELDS)
+    assert_c_rule(report, f"teacher-forced, {label}{kind}, n = {n}")
+    assert "wlam 80-83" in report
+    return report
+
+
+def check_free_step(sh, ref, where=""):
+    """The snapshot `sh` under test after a free-running physics step against both oracles' (a record of tumbled_free_ref): contact
+    counts and slot corners exact in every env."""
+    for s in (ref["s64"], ref["s32"]):
+        assert (sh["ncontact"] == s["ncontact"]).all(), f"contact count differs in {(sh['ncontact'] != s['ncontact']).sum()} envs{where}"
+        assert (sh["corner"] == s["corner"]).all(), f"slots 80-83 differ in {(sh['corner'] != s['corner']).any(0).sum()} envs{where}"
+
+
+# ------------------------------------------------------------------------------------------------- comparisons: whole control steps
+def random_actions(rng, n, scale=1.0):
+    return (scale * (2 * rng.random((n, 18)) - 1)).astype(np.float32)
+
+
+def control_steps(o, hb, rng, steps, reset_atol, obs_bar, rew_atol, rew_rtol, q_atol):
+    """reset and `steps` random-action control steps with in-step resets of the backend `hb` against the fp32 oracle `o`: done flags
+    and the reset count of every step exact, two physics steps exactly where an env was reset, rewards and the final q within
+    their tolerances, the worst observation error of the run below obs_bar, and more resets than envs."""
+    n = o.n
+    np.testing.assert_allclose(hb.reset(), o.reset(), atol=reset_atol)
+    worst = 0.0
+    for t in range(steps):
+        a = random_actions(rng, n)
+        oo, ro, do = o.step(a)
+        oh, rh, dh = hb.step(a)
+        assert (do == dh.astype(bool)).all(), t
+        assert hb.stats()[16] == o.stats()[16] and hb.stats()[17] == (2 if do.any() else 1)
+        worst = max(worst, float(np.abs(oh - oo).max()))
+        np.testing.assert_allclose(rh, ro, atol=rew_atol, rtol=rew_rtol)
+    assert worst < obs_bar, worst
+    assert o.get("reset_count").sum() > n
+    np.testing.assert_allclose(hb.get("q"), o.get("q"), atol=q_atol)
+
+
+def free_running(o, hb, rng, steps, reset_atol, median, p99, mismatches, resets, twin=None, label=None):
+    """reset and `steps` free-running random-action control steps of `hb` against the fp32 oracle `o`.  fp32 roundoff grows through
+    contacts, so the bars are statistical for trajectories (median and 99th percentile of the per-env observation error) and a count
+    for the integer bookkeeping (done mismatches in all, reset count per step).  `twin`: a second backend that must give hb's values
+    with `==` in every step."""
+    n = o.n
+    obs_o, obs_h = o.reset(), hb.reset()
+    np.testing.assert_allclose(obs_h, obs_o, atol=reset_atol)
+    assert twin is None or (obs_h == twin.reset()).all()
+    errs, mism = [], 0
+    for t in range(steps):
+        a = random_actions(rng, n)
+        oo, ro, do = o.step(a)
+        oh, rh, dh = hb.step(a)
+        if twin is not None:
+            og, rg, dg = twin.step(a)
+            assert (oh == og).all() and (rh == rg).all() and (dh == dg).all(), f"step {t}: the switch changes values"
+        errs.append(np.abs(oh - oo).max(axis=1))
+        mism += int((do != dh.astype(bool)).sum())
+        assert abs(hb.stats()[16] - o.stats()[16]) <= resets     # resets this step
+    errs = np.stack(errs)
+    if label is not None:
+        print(f"{label}: median {np.median(errs):.3g}  p99 {np.percentile(errs, 99):.3g}  done mismatches {mism}")
+    assert np.median(errs) < median
+    assert np.percentile(errs, 99) < p99
+    assert mism <= mismatches
+    assert o.get("reset_count").sum() > n                    # resets (timeouts) really happened

@@ -1,38 +1,26 @@
 """GPU parity tests (-m gpu): the HIP kernels, called through the C-ABI, against
   (1) the golden vectors produced by the reference's own Python (L2), and
   (2) the CPU oracle on identical seeded state (physics; teacher-forced sub-steps and free-running steps).
-Tolerances are stated per test; integer / boolean outputs must match exactly."""
+Tolerances are stated per test; integer / boolean outputs must match exactly.  Configurations, the loaded backends and the
+comparisons that more than one test uses: tests/physics_rig.py."""
 import os
 
 import numpy as np
 import pytest
 
 from dexrobot_isaac_amd.config import build_sim_config, default_cfg
+from tests import physics_rig as pr
+from tests.l2_replay import ALL_SCENARIOS as SCENARIOS
 
 pytestmark = pytest.mark.gpu
-
-from tests.l2_replay import ALL_SCENARIOS as SCENARIOS  # noqa: E402
-
-
-def _mk(task, n, **over):
-    cfg = default_cfg(task)
-    cfg["env"]["numEnvs"] = n
-    for k, v in over.items():
-        d = cfg
-        parts = k.split(".")
-        for p in parts[:-1]:
-            d = d[p]
-        d[parts[-1]] = v
-    return build_sim_config(cfg)
 
 
 @pytest.mark.parametrize("name", SCENARIOS)
 def test_hip_l2_replays_reference_golden(golden_dir, name):
-    from tests.hip_backend import HipBackend
     from tests.l2_replay import replay, scenario_config
     npz = np.load(os.path.join(golden_dir, f"l2_{name}.npz"), allow_pickle=False)
     sc, model = build_sim_config(scenario_config(npz))
-    hb = HipBackend(sc, model.to_struct())
+    hb = pr.hip(sc, model.to_struct())
     err = replay(hb, npz)     # obs within 2e-5 abs / 1e-5 rel, rewards 2e-6 rel, done exact
     assert err["obs"] < 2e-5 and err["active_prev_targets"] < 1e-6
     # the replay also compared, ON THE HIP PATH: every final obs_dict component and reward component of the scenario, the
@@ -48,41 +36,16 @@ def test_hip_l2_replays_reference_golden(golden_dir, name):
         assert ("ev:targets" in err) == (name in ("blind_cfg_base", "base_cfg_base"))
 
 
-def _random_state(rng, model, n, near_box=True):
-    """A spread of physically meaningful states: hand above / beside / pressing on the box."""
-    q = rng.uniform(0.0, 0.5, (26, n))
-    q[:3] = rng.uniform(-0.15, 0.15, (3, n))
-    q[2] = rng.uniform(-0.42, -0.2, n) if near_box else rng.uniform(-0.2, 0.2, n)
-    q[3:6] = rng.uniform(-0.3, 0.3, (3, n))
-    q = np.clip(q, model.lo[:, None] + 1e-3, model.hi[:, None] - 1e-3)
-    qd = rng.normal(0, 0.3, (26, n))
-    tg = q + rng.normal(0, 0.05, (26, n))
-    box_pos = np.stack([rng.uniform(-0.03, 0.03, n), rng.uniform(-0.03, 0.03, n), rng.uniform(0.0245, 0.03, n)])
-    yaw = rng.uniform(-np.pi, np.pi, n)
-    box_quat = np.stack([0 * yaw, 0 * yaw, np.sin(yaw / 2), np.cos(yaw / 2)])
-    return dict(q=q, qd=qd, targets=tg, box_pos=box_pos, box_quat=box_quat,
-                box_lin=rng.normal(0, 0.05, (3, n)), box_ang=rng.normal(0, 0.3, (3, n)))
-
-
 @pytest.mark.parametrize("fused", [True, False], ids=["k_substep", "k_dynamics+k_solve"])
 @pytest.mark.parametrize("task", ["BlindGrasping", "BaseTask"])
 def test_teacher_forced_substep_matches_oracle(task, fused):
     """One sub-step (dynamics + contact solve + integrate) from identical state.
     Tolerance: 2e-4 abs on q / box pose, 2e-3 on velocities (PGS amplifies fp32 roundoff of the two
     factorisations: dense Cholesky in the oracle vs Schur-complement blocks on the GPU), contact count exact."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 256
-    sc, model = _mk(task, n)
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms, fused=fused)
-    rng = np.random.default_rng(5)
-    st = _random_state(rng, model, n)
-    for k, v in st.items():
-        if task == "BaseTask" and k.startswith("box"):
-            continue
-        o.set(k, v)
-        hb.set(k, v)
+    sc, model, ms = pr.setup(task, n)
+    st = pr.random_state(np.random.default_rng(5), model, n)
+    o, hb = pr.backends(sc, ms, {k: v for k, v in st.items() if task == "BlindGrasping" or not k.startswith("box")}, fused=fused)
     for sub in range(3):
         o.substep(last=True)
         hb.substep(last=True)
@@ -112,14 +75,10 @@ def test_broadphase_regimes_match_oracle(z_range):
     """The sub-step kernel has three regimes per workgroup -- hand bounding sphere clear (early box solve), sphere not
     clear but every capsule passes its bounds, and the general contact path -- and mixes of them across workgroups.
     Each must give the oracle's contact lists and state after a full physics step (4 sub-steps in one launch)."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 320                                          # 5 workgroups
-    sc, model = _mk("BlindGrasping", n)
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
+    sc, model, ms = pr.setup("BlindGrasping", n)
     rng = np.random.default_rng(17)
-    st = _random_state(rng, model, n)
+    st = pr.random_state(rng, model, n)
     st["q"][2] = rng.uniform(z_range[0], z_range[1], n)
     if z_range == (-0.222, -0.216):                  # straight fingers a few mm to 3 cm off the box: capsule bounds fail, nothing touches (the box-only fast-out)
         st["q"][:2] = rng.uniform(-0.01, 0.01, (2, n)); st["q"][3:6] = 0.0; st["q"][6:] = rng.uniform(0.0, 0.05, (20, n))
@@ -137,9 +96,7 @@ def test_broadphase_regimes_match_oracle(z_range):
     st["qd"] *= 0.2
     if z_range == (-0.222, -0.216):
         st["targets"][:, 192:] = st["q"][:, 192:]    # (the hands of the contact-free workgroups hold their pose)
-    for k, v in st.items():
-        o.set(k, v)
-        hb.set(k, v)
+    o, hb = pr.backends(sc, ms, st)
     o.physics_step()
     hb.physics_step()
     nc_o, nc_h = o.get("ncontact")[0], hb.get("ncontact")[0]
@@ -162,18 +119,14 @@ def test_split_schur_phase_matches_the_one_wave_version():
     runs it on one wave.  Same expressions, same accumulation order -- the two launches still differ in where the compiler
     contracts multiply-adds, so the comparison is to a few ulp (2e-6 of the largest velocity, 1e-7 on positions), which a
     wrong or stale hand-over word would miss by orders of magnitude; padded lanes included."""
-    from tests.hip_backend import HipBackend
     n = 200                                          # 4 workgroups, the last one padded
-    sc, model = _mk("BlindGrasping", n)
-    ms = model.to_struct()
-    a, b = HipBackend(sc, ms, fused=True), HipBackend(sc, ms, fused=False)
+    sc, model, ms = pr.setup("BlindGrasping", n)
+    a, b = pr.hip(sc, ms, fused=True), pr.hip(sc, ms, fused=False)
     rng = np.random.default_rng(23)
-    st = _random_state(rng, model, n, near_box=False)
+    st = pr.random_state(rng, model, n, near_box=False)
     st["q"][2] = rng.uniform(-0.05, 0.2, n)
     st["q"] = np.clip(st["q"], model.lo[:, None] + 1e-3, model.hi[:, None] - 1e-3)
-    for k, v in st.items():
-        a.set(k, v)
-        b.set(k, v)
+    pr.load(a, st), pr.load(b, st)
     for sub in range(3):
         a.substep(last=True)
         b.substep(last=True)
@@ -187,26 +140,15 @@ def test_split_schur_phase_matches_the_one_wave_version():
 
 def test_contact_manifold_matches_oracle():
     """Narrowphase only: identical contact lists (type, capsule, order) and geometry within 1e-6."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 128
-    sc, model = _mk("BlindGrasping", n)
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
-    st = _random_state(np.random.default_rng(9), model, n)
-    for k, v in st.items():
-        o.set(k, v)
-        hb.set(k, v)
+    sc, model, ms = pr.setup("BlindGrasping", n)
+    o, hb = pr.backends(sc, ms, pr.random_state(np.random.default_rng(9), model, n))
     o.substep(last=True)
     hb.substep(last=True)
     total = 0
     for e in range(n):
-        co, ch = o.contacts(e), hb.contacts(e)
-        assert co.shape == ch.shape
-        assert (co[:, 8] == ch[:, 8]).all()                      # contact type
-        hand = co[:, 8] != 2
-        assert (co[hand, 9] == ch[hand, 9]).all()                # capsule id (undefined for box/ground)
-        np.testing.assert_allclose(ch[:, :8], co[:, :8], atol=2e-6)
+        co = o.contacts(e)
+        pr.assert_same_entries(co, hb.contacts(e), atol=2e-6)
         total += len(co)
     assert total > 4 * n
 
@@ -215,32 +157,14 @@ def test_free_running_steps_match_oracle():
     """Whole env.step() pipeline for 30 control steps with the same device/host Philox reset stream.
     fp32 roundoff grows through contacts, so the bar is statistical for trajectories (median obs error
     < 1e-4, 99th percentile < 5e-3) and exact for the integer bookkeeping of envs that did not diverge."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 192
-    sc, model = _mk("BlindGrasping", n, **{"env.episodeLength": 25})
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
-    obs_o, obs_h = o.reset(), hb.reset()
-    np.testing.assert_allclose(obs_h, obs_o, atol=2e-4)
-    rng = np.random.default_rng(3)
-    errs, mism = [], 0
-    for t in range(30):
-        a = (2 * rng.random((n, 18)) - 1).astype(np.float32)
-        oo, ro, do = o.step(a)
-        oh, rh, dh = hb.step(a)
-        errs.append(np.abs(oh - oo).max(axis=1))
-        mism += int((do != dh.astype(bool)).sum())
-        assert abs(hb.stats()[16] - o.stats()[16]) <= 2      # resets this step
-    errs = np.stack(errs)
-    assert np.median(errs) < 1e-4
-    assert np.percentile(errs, 99) < 5e-3
-    assert mism <= 2
-    assert o.get("reset_count").sum() > n                    # resets (timeouts at 24) really happened
+    sc, _, ms = pr.setup("BlindGrasping", n, **{"env.episodeLength": 25})      # (timeouts at 24)
+    o, hb = pr.backends(sc, ms)
+    pr.free_running(o, hb, np.random.default_rng(3), 30, reset_atol=2e-4, median=1e-4, p99=5e-3, mismatches=2, resets=2)
     # the contact solver's warm-start cache went through the same life on both sides: one generation per sub-step and reset,
     # the same slots valid (tag = 8 * generation [+ corner]), the same impulses in them
     lam_h, tag_h, gen_h = hb.warm_cache()
-    lam_o, tag_o, gen_o = o.get("wlam"), o.get("wtag").astype(np.int64), o.get("wgen")[0].astype(np.int64)
+    lam_o, tag_o, gen_o = o.warm_cache()
     assert (gen_h == gen_o).all() and gen_o.min() >= 30 * 4
     valid_o, valid_h = (tag_o >> 3) == gen_o, (tag_h >> 3) == gen_h
     agree = (valid_o == valid_h).all(axis=0)
@@ -251,12 +175,10 @@ def test_free_running_steps_match_oracle():
 
 
 def test_body_states_and_indexed_setters():
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     import torch
     n = 70                                                   # not a multiple of 64: padded lanes exercised
-    sc, model = _mk("BlindGrasping", n)
-    hb = HipBackend(sc, model.to_struct())
+    sc, model, ms = pr.setup("BlindGrasping", n)
+    hb = pr.hip(sc, ms)
     core = hb.core
     hb.reset()
     core.refresh_body_states()
@@ -470,8 +392,8 @@ def test_step_timing_and_step_stage_entry_points():
     import torch
     from dexrobot_isaac_amd import _abi
     from dexrobot_isaac_amd.core import DexSimCore
-    sc, model = _mk("BlindGrasping", 256)
-    core = DexSimCore(sc, model.to_struct(), "cuda:0")
+    sc, _, ms = pr.setup("BlindGrasping", 256)
+    core = DexSimCore(sc, ms, "cuda:0")
     core.reset()
     a = 2 * torch.rand(256, 18, device="cuda:0") - 1
     core.step_timing(True)
@@ -495,20 +417,12 @@ def test_fused_physics_launch_equals_four_single_substep_launches(near_box):
     lists other than 0-3, slots that change their corner within the four sub-steps, and edge / vertex hand contacts."""
     import torch
     from dexrobot_isaac_amd import _abi
-    from tests.hip_backend import HipBackend
     tumbled = isinstance(near_box, str)
     n = 256 if tumbled else 192
-    sc, model = _mk("BlindGrasping", n)
-    ms = model.to_struct()
-    a, b = HipBackend(sc, ms), HipBackend(sc, ms)
-    if tumbled:
-        from tests.tumbled_states import sample
-        st = sample(near_box, n, 11)
-    else:
-        st = _random_state(np.random.default_rng(23), model, n, near_box=near_box)
-    for k, v in st.items():
-        a.set(k, v)
-        b.set(k, v)
+    sc, model, ms = pr.setup("BlindGrasping", n)
+    a, b = pr.hip(sc, ms), pr.hip(sc, ms)
+    st = pr.tumbled_state(near_box, n) if tumbled else pr.random_state(np.random.default_rng(23), model, n, near_box=near_box)
+    pr.load(a, st), pr.load(b, st)
     a.core.run_stage(_abi.STAGE["PHYSICS"])
     for _ in range(4):
         b.core.run_stage(_abi.STAGE["SUBSTEP"])
@@ -540,8 +454,8 @@ def test_step_sink_writes_rollout_rows():
     from dexrobot_isaac_amd.core import DexSimCore
     from dexrobot_isaac_amd.rollout import RolloutBuffer
     n = 200                                              # not a multiple of 64: exercises the partial last workgroup
-    sc, model = _mk("BlindGrasping", n, **{"env.episodeLength": 6})
-    core = DexSimCore(sc, model.to_struct(), "cuda:0")
+    sc, _, ms = pr.setup("BlindGrasping", n, **{"env.episodeLength": 6})
+    core = DexSimCore(sc, ms, "cuda:0")
     core.reset()
     rb = RolloutBuffer(8, n, int(sc.num_obs), "cuda:0")
     g = torch.Generator(device="cuda:0").manual_seed(11)
@@ -574,12 +488,9 @@ def test_reset_gate_when_only_the_last_workgroup_resets():
     open the gated launch for every workgroup -- extra physics step for all envs, phase 1 of the reset for the flagged
     ones -- and the gate must close again in the following steps.  Checked against the oracle."""
     import torch
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 64 * 257 + 5
-    sc, model = _mk("BlindGrasping", n, **{"env.episodeLength": 40})
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms, threads=8), HipBackend(sc, ms)
+    sc, _, ms = pr.setup("BlindGrasping", n, **{"env.episodeLength": 40})
+    o, hb = pr.backends(sc, ms, threads=8)
     obs_o, obs_h = o.reset(), hb.reset()
     es = np.zeros((1, n))
     es[0, 64 * 257:] = 37                                    # the five envs of the last (padded) workgroup time out at step 1
@@ -609,12 +520,9 @@ def test_config2_base_task_position_1024_free_running():
     """BASELINE configs[1] at its stated shape: BaseTask, num_envs=1024, position control, no object (articulated
     forward dynamics only), 30 free-running control steps with random actions against the oracle.  No contacts, so the
     trajectories do not bifurcate: every env is compared, max error over all envs and steps."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 1024
-    sc, model = _mk("BaseTask", n, **{"task.controlMode": "position"})
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms, threads=8), HipBackend(sc, ms)
+    sc, _, ms = pr.setup("BaseTask", n, **{"task.controlMode": "position"})
+    o, hb = pr.backends(sc, ms, threads=8)
     np.testing.assert_allclose(hb.reset(), o.reset(), atol=2e-5)
     rng = np.random.default_rng(21)
     worst_obs = worst_rew = 0.0
@@ -636,15 +544,12 @@ def test_config5_dr_8192_with_reset_churn():
     staggered so that some env resets in every control step (reset_idx churn: the device-gated second physics step runs
     every step), 30 control steps with random actions against the oracle on the same device/host Philox streams.  The bar
     is the free-running one: exact integer bookkeeping for envs that did not bifurcate, statistical for trajectories."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 8192
     cfg = default_cfg("BlindGrasping")
     cfg["env"]["numEnvs"] = n
     dr = {"mass": (0.05, 0.2), "friction": (0.5, 1.5), "seed": 4242}
     sc, model = build_sim_config(cfg, dr=dr)
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms, threads=16), HipBackend(sc, ms)
+    o, hb = pr.backends(sc, model.to_struct(), threads=16)
     np.testing.assert_allclose(hb.get("box_mass"), o.get("box_mass"), rtol=5e-7)
     np.testing.assert_allclose(hb.get("box_mu"), o.get("box_mu"), rtol=5e-7)
     np.testing.assert_allclose(hb.reset(), o.reset(), atol=2e-4)
@@ -676,38 +581,24 @@ def test_hip_error_is_a_small_multiple_of_fp32_roundoff():
     against fp64 must stay within a small multiple c of the fp32 oracle's own error against fp64, at the 99.9th percentile
     and at the maximum, over the envs whose contact sets agree in all three (a contact appearing or not is a discontinuity,
     not roundoff)."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 512
-    sc, model = _mk("BlindGrasping", n)
-    ms = model.to_struct()
-    o64, o32, hb = Oracle(sc, ms, f64=True), Oracle(sc, ms), HipBackend(sc, ms)
+    sc, model, ms = pr.setup("BlindGrasping", n)
+    o64, o32, hb = pr.backends(sc, ms, f64=True)
     rng = np.random.default_rng(41)
     report = {}
     for trial, near in enumerate((True, False, True)):
-        st = _random_state(rng, model, n, near_box=near)
+        st = pr.random_state(rng, model, n, near_box=near)
         for b in (o64, o32, hb):
-            for k, v in st.items():
-                b.set(k, np.asarray(v, dtype=np.float32))    # identical fp32-representable state everywhere
-        for b in (o64, o32, hb):
+            pr.load(b, {k: np.asarray(v, dtype=np.float32) for k, v in st.items()})    # identical fp32-representable state everywhere
             b.substep(last=True)
         same = (o64.get("ncontact")[0] == o32.get("ncontact")[0]) & (o64.get("ncontact")[0] == hb.get("ncontact")[0])
         assert same.mean() > 0.97
         for f in ("q", "qd", "box_pos", "box_lin", "box_ang", "cforce"):
-            ref = o64.get(f)[:, same]
-            e32 = np.abs(o32.get(f)[:, same] - ref).ravel()
-            eh = np.abs(hb.get(f)[:, same] - ref).ravel()
-            r = report.setdefault(f, [0.0, 0.0, 0.0, 0.0])
-            r[0] = max(r[0], np.percentile(e32, 99.9)); r[1] = max(r[1], np.percentile(eh, 99.9))
-            r[2] = max(r[2], e32.max()); r[3] = max(r[3], eh.max())
-    print("\nfield: p99.9 |f32-f64|, p99.9 |HIP-f64|, max |f32-f64|, max |HIP-f64|")
-    for f, r in report.items():
-        print(f"  {f:8s} {r[0]:.3e} {r[1]:.3e} {r[2]:.3e} {r[3]:.3e}")
-    c = 3.0     # measured: 1.0-1.5 with round 1's sequential solver, 1.2-2.7 with round 2's block solver (the box twist goes
-                # through per-block copies and a sum over the blocks: profiles/round2_e/README.md)
-    for f, r in report.items():
-        assert r[1] <= c * r[0] + 1e-7, (f, r)
-        assert r[3] <= c * r[2] + 1e-6, (f, r)
+            pr.accumulate(report, f, o64.get(f), o32.get(f), hb.get(f), np.broadcast_to(same, o64.get(f).shape))
+    # c = pr.C_RULE = 3 and the floors 1e-7 / 1e-6; measured: 1.0-1.5 with round 1's sequential solver, 1.2-2.7 with round 2's block
+    # solver (the box twist goes through per-block copies and a sum over the blocks: profiles/round2_e/README.md)
+    assert pr.C_RULE == 3.0
+    pr.assert_c_rule(report, "random states, one teacher-forced sub-step each, n = 512")
 
 
 @pytest.mark.parametrize("task,substeps", [("BlindGrasping", 4), ("BaseTask", 4), ("BlindGrasping", 2), ("BaseTask", 2),
@@ -721,17 +612,15 @@ def test_fused_step_equals_staged_step_bitwise(task, substeps):
     this ties the fused production post block (7 waves, box-wave pre-tasks) to the stand-alone k_post that the golden
     replays exercise, and the action block inside a physics launch to the same block launched alone."""
     n = 200                                                  # 4 workgroups, the last one padded
-    sc, model = _mk(task, n, **{"env.episodeLength": 7, "sim.substeps": substeps})
+    sc, _, ms = pr.setup(task, n, **{"env.episodeLength": 7, "sim.substeps": substeps})
     assert int(sc.substeps) == substeps
-    _fused_equals_staged_bitwise(sc, model, task, n)
+    _fused_equals_staged_bitwise(sc, ms, task, n)
 
 
-def _fused_equals_staged_bitwise(sc, model, task, n):
+def _fused_equals_staged_bitwise(sc, ms, task, n):
     import torch
-    from tests.hip_backend import HipBackend
-    ms = model.to_struct()
     na = int(sc.num_actions)
-    a, b = HipBackend(sc, ms), HipBackend(sc, ms)
+    a, b = pr.hip(sc, ms), pr.hip(sc, ms)
     a.reset(); b.reset()
     g = torch.Generator(device="cuda:0").manual_seed(77)
     fields = ("q", "qd", "targets", "obs_all", "rew_comp", "rew", "reset_flag", "episode_step", "active_prev_targets",
@@ -774,7 +663,7 @@ def test_fused_step_equals_staged_step_bitwise_at_non_default_configurations(gol
     n = 200
     sc, model = build_sim_config(_golden_cfg(golden_dir, name, n, episodeLength=7))
     assert (int(sc.num_actions), int(sc.num_obs), int(sc.episode_length)) == (na, nobs, 7)
-    _fused_equals_staged_bitwise(sc, model, task, n)
+    _fused_equals_staged_bitwise(sc, model.to_struct(), task, n)
 
 
 @pytest.mark.parametrize("zero_targets", [False, True], ids=["targets", "zero_targets"])
@@ -789,23 +678,16 @@ def test_action_stage_matches_oracle(mode, hand_base, zero_targets):
     most two fp32 operations on values below 4 rad, so a contraction difference between hipcc and the C compiler stays
     below that)."""
     import torch
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 200
-    sc, model = _mk("BlindGrasping", n, **{"task.controlMode": mode, "task.policy_controls_hand_base": hand_base})
+    sc, _, ms = pr.setup("BlindGrasping", n, **{"task.controlMode": mode, "task.policy_controls_hand_base": hand_base})
     na = int(sc.num_actions)
     assert na == (18 if hand_base else 12)
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
     rng = np.random.default_rng(13)
     lo, hi = np.array(sc.active_lower)[:, None], np.array(sc.active_upper)[:, None]
     prev = rng.uniform(lo, hi, (18, n)).astype(np.float32)
     state = {"active_prev_targets": prev, "active_rule_targets": np.clip(prev + rng.normal(0, 0.02, (18, n)), lo, hi),
              "targets": rng.uniform(-1, 1, (26, n)), "actions": rng.uniform(-1, 1, (18, n))}
-    for k, v in state.items():
-        v = np.asarray(v, dtype=np.float32)
-        o.set(k, v)
-        hb.set(k, v)
+    o, hb = pr.backends(sc, ms, {k: np.asarray(v, dtype=np.float32) for k, v in state.items()})
     copy = torch.full((n, na), 7.0, device="cuda:0")
     hb.core.set_action_copy(copy)
     act = rng.uniform(-1, 1, (n, na)).astype(np.float32)
@@ -836,11 +718,9 @@ def test_level2_gym_shim_matches_fused_step():
     setters must teleport exactly the listed envs."""
     import torch
     from tests.dexsim_gym_shim import DexSimGym
-    from tests.hip_backend import HipBackend
     n = 130
-    sc, model = _mk("BlindGrasping", n, **{"env.episodeLength": 6})
-    ms = model.to_struct()
-    a, gym = HipBackend(sc, ms), DexSimGym(sc, ms)
+    sc, _, ms = pr.setup("BlindGrasping", n, **{"env.episodeLength": 6})
+    a, gym = pr.hip(sc, ms), DexSimGym(sc, ms)
     b = gym.core
     a.reset(); b.reset()
     g = torch.Generator(device="cuda:0").manual_seed(5)
@@ -884,33 +764,16 @@ def test_saturated_contact_list_matches_oracle():
     blocks are pairs of contacts and a workgroup has 768 work items, twice its item lanes (the generic variant of the sweeps,
     two rounds per pass).  Contact lists must be identical, the state after a full physics step within the teacher-forced
     tolerances."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     from dexrobot_isaac_amd import _abi
     n = 192
-    sc, model = _mk("BlindGrasping", n)
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
-    rng = np.random.default_rng(2)
-    q = np.zeros((26, n))
-    q[2] = -0.42 + rng.uniform(-0.02, 0.02, n)
-    q[3:6] = rng.uniform(-0.15, 0.15, (3, n))
-    q[6:] = rng.uniform(0, 0.3, (20, n))
-    st = dict(q=q, qd=0 * q, targets=q, box_pos=np.array([[0.0], [0.0], [0.0255]]) + 0 * q[:3],
-              box_quat=np.array([[0.0], [0.0], [0.0], [1.0]]) + 0 * q[:4], box_lin=0 * q[:3], box_ang=0 * q[:3])
-    for k, v in st.items():
-        o.set(k, v)
-        hb.set(k, v)
+    sc, _, ms = pr.setup("BlindGrasping", n)
+    o, hb = pr.backends(sc, ms, pr.lowered_hand_state(np.random.default_rng(2), n, z=-0.42, dz=0.02, rot=0.15))
     o.substep(last=True)
     hb.substep(last=True)
     nc_o, nc_h = o.get("ncontact")[0], hb.get("ncontact")[0]
     assert (nc_o == nc_h).all() and nc_o.max() == _abi.KMAX and (nc_o > 16).mean() > 0.9
     for e in range(0, n, 7):
-        co, ch = o.contacts(e), hb.contacts(e)
-        assert co.shape == ch.shape and (co[:, 8] == ch[:, 8]).all()
-        hand = co[:, 8] != 2
-        assert (co[hand, 9] == ch[hand, 9]).all()
-        np.testing.assert_allclose(ch[:, :8], co[:, :8], atol=2e-6)
+        pr.assert_same_entries(o.contacts(e), hb.contacts(e), atol=2e-6)
     np.testing.assert_allclose(hb.get("q"), o.get("q"), atol=2e-4)
     np.testing.assert_allclose(hb.get("qd"), o.get("qd"), atol=1e-2, rtol=5e-3)      # 24 coupled contacts: PGS amplifies roundoff
     np.testing.assert_allclose(hb.get("box_pos"), o.get("box_pos"), atol=2e-4)
@@ -927,22 +790,9 @@ def test_generic_sweep_variants_match_oracle(z):
     """Between the common case (one contact per item lane, resident rows) and the saturated list: hands low enough for 8-14
     hand contacts per env, so that a workgroup has more work items than item lanes (384) and lanes with single-contact blocks
     sit next to lanes whose blocks are pairs.  One sub-step from identical state, then two free physics steps."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 128
-    sc, model = _mk("BlindGrasping", n)
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
-    rng = np.random.default_rng(2)
-    q = np.zeros((26, n))
-    q[2] = z + rng.uniform(-0.004, 0.004, n)
-    q[3:6] = rng.uniform(-0.1, 0.1, (3, n))
-    q[6:] = rng.uniform(0, 0.3, (20, n))
-    st = dict(q=q, qd=0 * q, targets=q, box_pos=np.array([[0.0], [0.0], [0.0255]]) + 0 * q[:3],
-              box_quat=np.array([[0.0], [0.0], [0.0], [1.0]]) + 0 * q[:4], box_lin=0 * q[:3], box_ang=0 * q[:3])
-    for k, v in st.items():
-        o.set(k, v)
-        hb.set(k, v)
+    sc, _, ms = pr.setup("BlindGrasping", n)
+    o, hb = pr.backends(sc, ms, pr.lowered_hand_state(np.random.default_rng(2), n, z=z, dz=0.004, rot=0.1))
     o.substep(last=True)
     hb.substep(last=True)
     nc_o, nc_h = o.get("ncontact")[0], hb.get("ncontact")[0]
@@ -958,8 +808,7 @@ def test_generic_sweep_variants_match_oracle(z):
     np.testing.assert_allclose(hb.get("qd"), o.get("qd"), atol=1e-2, rtol=5e-3)
     np.testing.assert_allclose(hb.get("box_pos"), o.get("box_pos"), atol=2e-4)
     np.testing.assert_allclose(hb.get("cforce"), o.get("cforce"), atol=0.5, rtol=5e-2)
-    lam_h, tag_h, gen_h = hb.warm_cache()
-    tag_o, gen_o = o.get("wtag").astype(np.int64), o.get("wgen")[0].astype(np.int64)
+    (_, tag_h, gen_h), (_, tag_o, gen_o) = hb.warm_cache(), o.warm_cache()
     assert (gen_h == gen_o).all() and (((tag_h >> 3) == gen_h) == ((tag_o >> 3) == gen_o)).all()   # the same cache slots written
     for _ in range(2):
         o.physics_step()
@@ -976,27 +825,11 @@ def test_other_substep_counts_match_oracle(substeps, iters):
     launches: the action block on the first launch, the post-physics block / reset tail on the last (32 sub-steps = 8 + 8
     launches, 2 sub-steps = 2 + 2, 6 = 3 + 3).  Whole control steps with in-step resets against the oracle; the integer
     bookkeeping must agree exactly."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 130
-    sc, model = _mk("BlindGrasping", n, **{"sim.substeps": substeps, "sim.physx.num_position_iterations": iters, "env.episodeLength": 8})
+    sc, _, ms = pr.setup("BlindGrasping", n, **{"sim.substeps": substeps, "sim.physx.num_position_iterations": iters, "env.episodeLength": 8})
     assert int(sc.substeps) == substeps and int(sc.num_position_iterations) == iters
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
-    np.testing.assert_allclose(hb.reset(), o.reset(), atol=2e-4)
-    rng = np.random.default_rng(13)
-    worst = 0.0
-    for t in range(12):
-        a = (2 * rng.random((n, 18)) - 1).astype(np.float32)
-        oo, ro, do = o.step(a)
-        oh, rh, dh = hb.step(a)
-        assert (do == dh.astype(bool)).all(), t
-        assert hb.stats()[16] == o.stats()[16] and hb.stats()[17] == (2 if do.any() else 1)
-        worst = max(worst, float(np.abs(oh - oo).max()))
-        np.testing.assert_allclose(rh, ro, atol=2e-2, rtol=1e-4)
-    assert worst < 5e-3, worst
-    assert o.get("reset_count").sum() > n
-    np.testing.assert_allclose(hb.get("q"), o.get("q"), atol=5e-4)
+    o, hb = pr.backends(sc, ms)
+    pr.control_steps(o, hb, np.random.default_rng(13), 12, reset_atol=2e-4, obs_bar=5e-3, rew_atol=2e-2, rew_rtol=1e-4, q_atol=5e-4)
 
 
 def test_general_contact_path_is_bitwise_reproducible():
@@ -1006,10 +839,10 @@ def test_general_contact_path_is_bitwise_reproducible():
     import torch
     from dexrobot_isaac_amd.core import DexSimCore
     n = 1024
-    sc, model = _mk("BlindGrasping", n)
+    sc, _, ms = pr.setup("BlindGrasping", n)
     outs = []
     for _ in range(2):
-        core = DexSimCore(sc, model.to_struct(), "cuda:0")
+        core = DexSimCore(sc, ms, "cuda:0")
         core.reset()
         g = torch.Generator(device="cuda:0").manual_seed(3)
         q = core.field("q")
@@ -1059,10 +892,10 @@ def test_warm_start_generation_wrap_on_the_hip_path():
     from dexrobot_isaac_amd import _abi
     from dexrobot_isaac_amd.core import DexSimCore
     n, wrap = 256, 1 << 27
-    sc, model = _mk("BlindGrasping", n)
+    sc, _, ms = pr.setup("BlindGrasping", n)
     outs = []
     for gen0 in (1000, wrap - 30):
-        core = DexSimCore(sc, model.to_struct(), "cuda:0")
+        core = DexSimCore(sc, ms, "cuda:0")
         core.reset()
         g = torch.Generator(device="cuda:0").manual_seed(3)
         q = core.field("q")
@@ -1106,12 +939,9 @@ def test_config3_headline_workload_as_itself_through_the_synchronous_reset():
     Tolerances: free-running bar (no hand contacts in this regime: the error does not grow through contacts) -- median obs
     error < 1e-4, 99.9th percentile < 5e-3 over ALL 205 steps; rewards 2e-2 abs; done flags, reset counts and physics-step
     counts exact."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 4096
-    sc, model = _mk("BlindGrasping", n)
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms, threads=16), HipBackend(sc, ms)
+    sc, _, ms = pr.setup("BlindGrasping", n)
+    o, hb = pr.backends(sc, ms, threads=16)
     np.testing.assert_allclose(hb.reset(), o.reset(), atol=2e-4)
     rng = np.random.default_rng(2024)
     errs, sync_steps = [], []
@@ -1148,9 +978,7 @@ def test_loaded_mjcf_with_perturbed_numbers_drives_the_hip_path():
     from dexrobot_isaac_amd import default_cfg, make_env
     from dexrobot_isaac_amd.hand_model import HandModel
     from dexrobot_isaac_amd.mjcf import export_mjcf, load_mjcf
-    from oracle.oracle import Oracle
     from oracle.py_backend import OracleCore
-    from tests.hip_backend import HipBackend
 
     class Perturbed(HandModel):
         L_PROX = [0.043, 0.037, 0.049, 0.042, 0.030]
@@ -1193,14 +1021,11 @@ def test_loaded_mjcf_with_perturbed_numbers_drives_the_hip_path():
     env.close(), dflt.close()
     # teacher-forced sub-step in a contact state (hands low over their boxes): contact lists and velocities vs the oracle
     sc, _ = build_sim_config({**cfg, "env": {**cfg["env"], "numEnvs": n}}, model=loaded)
-    ms = loaded.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
     rng = np.random.default_rng(5)
     q = np.zeros((26, n))
     q[2] = rng.uniform(-0.43, -0.38, n)
     q[6:] = rng.uniform(0.0, 0.3, (20, n))
-    for b in (o, hb):
-        b.set("q", q); b.set("qd", 0 * q); b.set("targets", q)
+    o, hb = pr.backends(sc, loaded.to_struct(), dict(q=q, qd=0 * q, targets=q))
     for _ in range(3):
         o.substep(True); hb.substep(True)
     nc_o, nc_h = o.get("ncontact")[0], hb.get("ncontact")[0]
@@ -1300,24 +1125,18 @@ def test_joint_limit_rows_match_oracle():
     finger joints sit within the margin of a limit while the hand touches box and ground.  Lists identical entry by entry
     (type, capsule / joint level, gap), state to the usual teacher-forced tolerances, the limit rows' impulses to 2e-3 abs /
     2 % rel, statistics (rows are not contacts) exact; plus free-running control steps through dexsim_step."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
     n = 256
-    sc, model = _mk("BlindGrasping", n, **{"sim.dexsim_joint_limit_rows": True})
+    sc, model, ms = pr.setup("BlindGrasping", n, **{"sim.dexsim_joint_limit_rows": True})
     assert int(sc.joint_limit_rows) == 1
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
     rng = np.random.default_rng(17)
-    st = _random_state(rng, model, n)
+    st = pr.random_state(rng, model, n)
     near = rng.random((20, n)) < 0.4                      # 40 % of the finger joints on / next to a limit
     side = rng.random((20, n)) < 0.7
     lo, hi = model.lo[6:, None], model.hi[6:, None]
     off = rng.uniform(0.0, 0.012, (20, n))
     st["q"][6:] = np.where(near, np.where(side, lo + off, hi - off), st["q"][6:])
     st["targets"][6:] = np.where(near, st["q"][6:] - np.where(side, 0.2, -0.2), st["targets"][6:])    # PD pushes into the stop
-    for k, v in st.items():
-        o.set(k, v)
-        hb.set(k, v)
+    o, hb = pr.backends(sc, ms, st)
     rows_seen = 0
     for sub in range(3):
         o.substep(last=True)
@@ -1325,26 +1144,22 @@ def test_joint_limit_rows_match_oracle():
         nc_o, nc_h = o.get("ncontact")[0], hb.get("ncontact")[0]
         assert (nc_o == nc_h).all(), f"list length differs in {(nc_o != nc_h).sum()} envs at sub-step {sub}"
         for e in range(0, n, 4):
-            co, ch = o.contacts(e), hb.contacts(e)
-            assert (co[:, 8] == ch[:, 8]).all() and (co[co[:, 8] != 2, 9] == ch[co[:, 8] != 2, 9]).all()
-            np.testing.assert_allclose(ch[:, :8], co[:, :8], atol=2e-6)
+            co = o.contacts(e)
+            pr.assert_same_entries(co, hb.contacts(e), atol=2e-6)
             rows_seen += int((co[:, 8] == 3).sum())
         np.testing.assert_allclose(hb.get("q"), o.get("q"), atol=2e-4)
         np.testing.assert_allclose(hb.get("qd"), o.get("qd"), atol=5e-3, rtol=2e-3)
         np.testing.assert_allclose(hb.get("cforce"), o.get("cforce"), atol=5e-2, rtol=2e-2)
-        lam_h, tag_h, gen_h = hb.warm_cache()
-        lam_o, tag_o, gen_o = o.get("wlam"), o.get("wtag").astype(np.int64), o.get("wgen")[0].astype(np.int64)
+        (lam_h, tag_h, gen_h), (lam_o, tag_o, gen_o) = hb.warm_cache(), o.warm_cache()
         vo, vh = (tag_o[88:] >> 3) == gen_o, (tag_h[88:] >> 3) == gen_h
         assert (vo == vh).all() and (gen_o == gen_h).all()
         lo3, lh3 = lam_o[88 * 3:].reshape(40, 3, n)[:, 0], lam_h[88 * 3:].reshape(40, 3, n)[:, 0]
         np.testing.assert_allclose(lh3[vo], lo3[vo], atol=2e-3, rtol=2e-2)
-        for k in ("q", "qd", "box_pos", "box_quat", "box_lin", "box_ang"):
-            hb.set(k, o.get(k))
+        pr.load(hb, {k: o.get(k) for k in pr.SYNC})
     assert rows_seen > n // 4 and float(np.abs(lo3[vo]).max()) > 1e-3       # rows exist and some carry load
     # free-running control steps through the production launch (dexsim_step), in-step resets included
-    sc2, model2 = _mk("BlindGrasping", 192, **{"sim.dexsim_joint_limit_rows": True, "env.episodeLength": 12})
-    ms2 = model2.to_struct()
-    o2, h2 = Oracle(sc2, ms2), HipBackend(sc2, ms2)
+    sc2, _, ms2 = pr.setup("BlindGrasping", 192, **{"sim.dexsim_joint_limit_rows": True, "env.episodeLength": 12})
+    o2, h2 = pr.backends(sc2, ms2)
     np.testing.assert_allclose(h2.reset(), o2.reset(), atol=2e-4)
     for b in (o2, h2):                                      # hands low over their boxes: contacts from the first step on
         q = b.get("q")

@@ -34,7 +34,7 @@ from tests.query_rig import (bits, dev as _dev, guarded as _guarded, guards_ok a
 
 N = 70
 NB, NJ = _abi.NUM_HAND_BODIES, _abi.NJ
-FACTOR = 4
+FACTOR = ir.FACTOR
 
 
 # ------------------------------------------------------------------------------------------------- CPU
@@ -176,11 +176,7 @@ def test_env_argument_validation():
 
 
 # ------------------------------------------------------------------------------------------------- GPU helpers
-def gpu_tau(core, k, qdd=None, env_ids=None, q=None, qd=None, gravity=True):
-    full, out = _guarded(k, NJ)
-    core.inverse_dynamics(out, qdd=_dev(qdd), env_ids=env_ids, q=_dev(q), qd=_dev(qd), gravity=gravity)
-    _guards_ok(full)
-    return out.cpu().numpy()
+gpu_tau, check_tau = ir.gpu_tau, ir.check_tau
 
 
 def gpu_acc(core, k, env_ids=None, q=None, qd=None, bodies=None):
@@ -221,13 +217,6 @@ def posed():
     c["vel"] = gpu_tau(core, N, gravity=False)
     c["acc"] = gpu_acc(core, N)
     return c
-
-
-def check_tau(tau, tau64, M64, e, what):
-    assert not np.isnan(tau).any(), f"{what}: an element was not written"
-    E = ir.err_tau(tau, tau64, M64)
-    print(f"{what}: E_tau = {E:.3g} (fp32 oracle: {e:.3g}, bound {FACTOR * e:.3g})")
-    assert E <= FACTOR * e
 
 
 def check_acc(acc, acc64, e_lin, e_ang, what):

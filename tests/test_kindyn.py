@@ -120,14 +120,7 @@ def gpu_jac(core, k, env_ids=None, q=None, bodies=None):
     return out.cpu().numpy()
 
 
-def gpu_mass(core, k, env_ids=None, q=None, mass=True, gravity=True):
-    fm, M = _guarded(k, NJ, NJ) if mass else (None, None)
-    fg, g = _guarded(k, NJ) if gravity else (None, None)
-    core.mass_matrix(mass=M, gravity=g, env_ids=env_ids, q=q)
-    for f in (fm, fg):
-        if f is not None:
-            _guards_ok(f)
-    return (None if M is None else M.cpu().numpy()), (None if g is None else g.cpu().numpy())
+gpu_mass = kr.gpu_mass
 
 
 def _case(ms, sc, seed):

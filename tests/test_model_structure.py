@@ -6,45 +6,12 @@ once by dexsim_create, clears the classification: the same library then runs the
   (1) the specialised kernels give the general kernels' values, compared with `==` over control steps and contact-rich physics steps;
   (2) a model that lacks one of the properties (by a small amount) runs the general code and still matches the oracle;
   (3) so does a model in which only some fingers lack them (the kernels are chosen for the whole model)."""
-import contextlib
-import math
-import os
-
 import numpy as np
 import pytest
 
-from dexrobot_isaac_amd.config import build_sim_config, default_cfg
-from dexrobot_isaac_amd.hand_model import HandModel, rot_z
+from tests.physics_rig import MODELS, backends, free_running, general_path, hip, setup
 
 pytestmark = pytest.mark.gpu
-
-SWITCH = "DEXSIM_GENERAL_MODEL_PATH"
-
-
-@contextlib.contextmanager
-def general_path():
-    """dexsim_create inside the block clears the model classification."""
-    old = os.environ.get(SWITCH)
-    os.environ[SWITCH] = "1"
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ[SWITCH]
-        else:
-            os.environ[SWITCH] = old
-
-
-def _cfg(task, n, **over):
-    cfg = default_cfg(task)
-    cfg["env"]["numEnvs"] = n
-    for k, v in over.items():
-        d = cfg
-        parts = k.split(".")
-        for p in parts[:-1]:
-            d = d[p]
-        d[parts[-1]] = v
-    return cfg
 
 
 def _snapshot(core):
@@ -75,8 +42,7 @@ def test_specialised_forms_equal_the_general_forms(task, n, over):
     contact path).  Every removed term is an exact zero and every removed factor an exact one: `==`, not a tolerance."""
     import torch
     from dexrobot_isaac_amd.core import DexSimCore
-    sc, model = build_sim_config(_cfg(task, n, **over))
-    ms = model.to_struct()
+    sc, _, ms = setup(task, n, **over)
     spec = DexSimCore(sc, ms, "cuda:0")
     with general_path():
         gen = DexSimCore(sc, ms, "cuda:0")
@@ -116,86 +82,19 @@ def test_specialised_forms_equal_the_general_forms(task, n, over):
         c.close()
 
 
-# ---- models that lack the structure
-def _tilt_axis(m, j):          # a flexion axis tilted by 1e-2 rad, renormalised
-    a = np.array([0.0, -math.cos(1e-2), math.sin(1e-2)])
-    m.jaxis[j] = a / np.linalg.norm(a)
-
-
-def _break_poff4(m):
-    m.jpoff[4] = (0.0, 2e-3, 0.0)
-
-
-def _break_axis(m):
-    _tilt_axis(m, 6 + 4 * 1 + 1)
-
-
-def _break_qoff(m):
-    j = 6 + 4 * 2 + 2
-    m.jRoff[j] = m.jRoff[j] @ rot_z(1e-2)
-
-
-def _break_com(m):
-    m.com[6 + 4 * 3 + 2, 1] = 1e-3
-
-
-def _break_all(m):
-    _break_poff4(m), _break_axis(m), _break_qoff(m), _break_com(m)
-
-
-def _mixed(m):                 # fingers 1 and 3 lack the structure, 2 and 4 (and the thumb) keep it
-    m.com[6 + 4 * 1 + 3, 1] = 1e-3
-    _tilt_axis(m, 6 + 4 * 3 + 2)
-
-
-_ROT = (math.sin(0.05) / math.sqrt(2.0), math.sin(0.05) / math.sqrt(2.0), 0.0, math.cos(0.05))   # 0.1 rad about (1, 1, 0)
-MODELS = {
-    "poff4": (_break_poff4, None), "axis": (_break_axis, None), "qoff": (_break_qoff, None), "com": (_break_com, None),
-    "hand_rot": (None, _ROT), "all": (_break_all, _ROT), "mixed": (_mixed, None),
-}
-
-
 @pytest.mark.parametrize("name", list(MODELS))
 def test_models_without_the_structure_match_the_oracle(name):
-    """One model per property of the hand model's structure, each lacking it by a small amount (some of them properties the kernels
-    do not rely on: those models run the specialised kernels), one lacking all, one with fingers of different shapes: 20
-    free-running control steps at N = 70 (two workgroups, one padded) against the CPU oracle at the bars of
+    """One model per property of the hand model's structure (tests/physics_rig.py::MODELS), each lacking it by a small amount (some of
+    them properties the kernels do not rely on: those models run the specialised kernels), one lacking all, one with fingers of
+    different shapes: 20 free-running control steps at N = 70 (two workgroups, one padded) against the CPU oracle at the bars of
     test_gpu_parity.py::test_free_running_steps_match_oracle (median obs error < 1e-4, 99th percentile < 5e-3, <= 2 done
     mismatches), and the same values with and without the switch."""
-    from oracle.oracle import Oracle
-    from tests.hip_backend import HipBackend
-    edit, rot = MODELS[name]
-    n = 70
-    cfg = _cfg("BlindGrasping", n, **{"env.episodeLength": 12})
-    if rot is not None:
-        cfg["env"]["initialHandRot"] = list(rot)
-    model = HandModel(cfg["env"]["initialHandPos"], cfg["env"]["initialHandRot"])
-    if edit is not None:
-        edit(model)
-    sc, model = build_sim_config(cfg, model=model)
-    ms = model.to_struct()
-    o, hb = Oracle(sc, ms), HipBackend(sc, ms)
+    sc, _, ms = setup("BlindGrasping", 70, model=name, **{"env.episodeLength": 12})      # (timeouts at 11)
+    o, hb = backends(sc, ms)
     with general_path():
-        hg = HipBackend(sc, ms)
-    obs_o, obs_h, obs_g = o.reset(), hb.reset(), hg.reset()
-    np.testing.assert_allclose(obs_h, obs_o, atol=2e-4)
-    assert (obs_h == obs_g).all()
-    rng = np.random.default_rng(3)
-    errs, mism = [], 0
-    for t in range(20):
-        a = (2 * rng.random((n, 18)) - 1).astype(np.float32)
-        oo, ro, do = o.step(a)
-        oh, rh, dh = hb.step(a)
-        og, rg, dg = hg.step(a)
-        assert (oh == og).all() and (rh == rg).all() and (dh == dg).all(), f"step {t}: the switch changes values"
-        errs.append(np.abs(oh - oo).max(axis=1))
-        mism += int((do != dh.astype(bool)).sum())
-        assert abs(hb.stats()[16] - o.stats()[16]) <= 2      # resets this step
-    errs = np.stack(errs)
-    print(f"{name}: median {np.median(errs):.3g}  p99 {np.percentile(errs, 99):.3g}  done mismatches {mism}")
-    assert np.median(errs) < 1e-4
-    assert np.percentile(errs, 99) < 5e-3
-    assert mism <= 2
-    assert o.get("reset_count").sum() > n                    # resets (timeouts at 11) really happened
+        hg = hip(sc, ms)
+    free_running(o, hb, np.random.default_rng(3), 20, reset_atol=2e-4, median=1e-4, p99=5e-3, mismatches=2, resets=2, twin=hg, label=name)
     assert (hb.get("q") == hg.get("q")).all() and (hb.get("qd") == hg.get("qd")).all()
     hb.core.close(), hg.core.close()
+
+

@@ -22,10 +22,10 @@ sides of their decision at a 2 mm contact offset and at both box sizes.
 
 Bounds: none of this file's own.  Integers exact over the envs whose list length agrees in both oracles and the kernels, at most
 LEFT_OUT = 2 % left out; points and gaps 2e-6 m; normals c E / dist + 1e-7; states c x the fp32 oracle's own error at the 99.9th
-percentile and at the maximum plus the floors 1e-7 and 1e-6, c = 3: all through the functions of tests/test_tumbled_box.py, which has
+percentile and at the maximum plus the floors 1e-7 and 1e-6, c = 3: all through the functions of tests/physics_rig.py, which has
 them from test_gpu_parity.py::test_hip_error_is_a_small_multiple_of_fp32_roundoff.  Whole control steps: the assertions of
-test_gpu_parity.py::test_other_substep_counts_match_oracle.  Queries: 4 x the fp32 reference's own error, through the functions of
-test_kindyn.py, test_inverse_dynamics.py and test_proximity.py.
+test_gpu_parity.py::test_other_substep_counts_match_oracle.  Queries: 4 x the fp32 reference's own error, through the functions those
+suites share (tests/kindyn_ref.py, tests/invdyn_ref.py, tests/proximity_ref.py).
 
 The CPU tests show that the references alone meet what the GPU tests rely on (both oracles list the same contacts, nothing left out),
 and that every varied field BITES: the fp64 oracle with that one field back at its default differs from the configured one by at least
@@ -37,11 +37,11 @@ import functools
 import numpy as np
 import pytest
 
-from dexrobot_isaac_amd.config import build_sim_config, default_cfg
-from tests import test_tumbled_box as tb
+from dexrobot_isaac_amd.config import default_cfg
+from tests import physics_rig as pr
 from tests import tumbled_states as ts
 
-N, PADDED = tb.N, 200
+N, PADDED = pr.N, 200
 N_STEP = 130                            # whole control steps: test_other_substep_counts_match_oracle's size
 N_QUERY = 70                            # the query suites' size
 BITE = 10.0                             # a field put back must move a compared quantity by this many bounds (a condition on the input)
@@ -57,63 +57,36 @@ CONFIGS = {
     "world": {"sim.dt": 0.8 * _DT, "sim.gravity.0": 0.8, "sim.gravity.1": -0.5, "sim.gravity.2": -9.2, "sim.dexsim_erp": 0.35,
               "sim.physx.max_depenetration_velocity": 0.02},
 }
-SEEDS = {name: tb.SEED for name in CONFIGS}          # a configuration whose sample conditions fail gets another seed, not another condition
+SEEDS = {name: pr.SEED for name in CONFIGS}          # a configuration whose sample conditions fail gets another seed, not another condition
 NAMES = list(CONFIGS)
 CAP = "sim.physx.max_depenetration_velocity"
 PAIRS = [(name, field) for name in NAMES for field in CONFIGS[name] if (name, field) != ("fast_yaml", CAP)]
 KINDS = ("hand_on_box", "box_alone", "hand_near_box")
 
 
-@functools.lru_cache(maxsize=None)
+def _fields(name, back=None):
+    """Configuration `name` as the keywords of pr.setup; `back`: one of its fields left at the default."""
+    return {k: v for k, v in CONFIGS[name].items() if k != back}
+
+
 def _setup(name, n, back=None, episode_length=None):
-    """(sc, model, ms) of configuration `name` for n envs; `back`: one of its fields left at the default."""
-    cfg = default_cfg("BlindGrasping")
-    cfg["env"]["numEnvs"] = n
-    if episode_length is not None:
-        cfg["env"]["episodeLength"] = episode_length
-    late = {}
-    for key, value in CONFIGS[name].items():
-        if key == back:
-            continue
-        if "." not in key:
-            late[key] = value
-            continue
-        d, parts = cfg, key.split(".")
-        for p in parts[:-1]:
-            d = d[p]
-        last = parts[-1]
-        d[int(last) if isinstance(d, list) else last] = value
-    sc, model = build_sim_config(cfg)
-    if "ground_friction" in late:
-        sc.ground_friction = late["ground_friction"]
-    if "hand_friction" in late:
-        model.hand_friction = late["hand_friction"]
-    return sc, model, model.to_struct()
+    """(sc, model, ms) of configuration `name` for n envs."""
+    more = {} if episode_length is None else {"env.episodeLength": episode_length}
+    return pr.setup("BlindGrasping", n, **more, **_fields(name, back))
 
 
 def _state(name, kind, n):
     """The first n envs of the configuration's N-env sample (always drawn for the configuration itself, never for a `back` variant)."""
-    sc, model, _ = _setup(name, N)
-    return {k: v[:, :n].copy() for k, v in ts.sample(kind, N, SEEDS[name], config=(sc, model)).items()}
+    return pr.tumbled_state(kind, n, SEEDS[name], **_fields(name))
 
 
-# ------------------------------------------------------------------------------------------------- references, computed once
-@functools.lru_cache(maxsize=None)
 def _teacher_ref(name, kind, n):
-    sc, _, ms = _setup(name, n)
-    return tb.teacher_ref(sc, ms, _state(name, kind, n))
+    return pr.tumbled_teacher_ref(kind, n, SEEDS[name], **_fields(name))
 
 
-@functools.lru_cache(maxsize=None)
 def _physics_ref(name, kind, n):
     """One physics step (sim.substeps sub-steps, free-running) of the sample on both oracles."""
-    from oracle.oracle import Oracle
-    sc, _, ms = _setup(name, n)
-    o64, o32 = Oracle(sc, ms, f64=True), Oracle(sc, ms)
-    st = _state(name, kind, n)
-    tb._load(o64, st), tb._load(o32, st)
-    o64.physics_step(), o32.physics_step()
-    return dict(s64=tb._snap(o64), s32=tb._snap(o32))
+    return pr.tumbled_free_ref(kind, n, 1, pr.FIELDS, SEEDS[name], **_fields(name))[0]
 
 
 def _hand_entries(lists):
@@ -122,62 +95,47 @@ def _hand_entries(lists):
 
 # ------------------------------------------------------------------------------------------------- the comparisons (GPU tests and stand-ins)
 def _check_lists(make, name):
-    """3.1: the first teacher-forced sub-step of hand_on_box, tb._check_manifold."""
+    """3.1: the first teacher-forced sub-step of hand_on_box, pr.check_manifold."""
     sc, _, ms = _setup(name, N)
     rec = _teacher_ref(name, "hand_on_box", N)[0]
     b = make()
-    tb._load(b, rec["start"])
+    pr.load(b, rec["start"])
     b.substep(last=True)
-    tb._check_manifold(b, rec, sc, ms)
+    pr.check_manifold(b, rec, sc, ms)
 
 
 def _check_teacher(make, name, kind, n):
-    return tb._check_teacher_forced(make, kind, n, recs=_teacher_ref(name, kind, n), label=f"{name}, ")
+    return pr.check_teacher_forced(make, _teacher_ref(name, kind, n), kind, label=f"{name}, ")
 
 
 def _check_physics_step(make, name, kind, n):
     """One free-running physics step: contact counts and slot corners exact against both oracles, states by the c rule.  On
-    hand_near_box also the first sub-step alone: no hand entry in any env, the lists of tb._check_manifold's kind."""
+    hand_near_box also the first sub-step alone: no hand entry in any env, the lists of pr.check_manifold's kind."""
     b = make()
     if kind == "hand_near_box":
         rec = _teacher_ref(name, kind, n)[0]
-        tb._load(b, rec["start"])
+        pr.load(b, rec["start"])
         b.substep(last=True)
-        lists = tb._lists(b, n)
+        lists = pr.lists(b, n)
         assert _hand_entries(lists) == 0 and _hand_entries(rec["lists64"]) == 0, "a hand entry where nothing of the hand touches"
-        assert all(tb._same_lists(a, c) for a, c in zip(rec["lists64"], lists))
-        assert (tb._bg_cache(b)[1] == rec["s64"]["corner"]).all()
+        assert all(pr.same_lists(a, c) for a, c in zip(rec["lists64"], lists))
+        assert (pr.bg_cache(b)[1] == rec["s64"]["corner"]).all()
         b = make()
     ref = _physics_ref(name, kind, n)
-    tb._load(b, _state(name, kind, n))
+    pr.load(b, _state(name, kind, n))
     b.physics_step()
-    sh = tb._snap(b)
-    for s in (ref["s64"], ref["s32"]):
-        assert (sh["ncontact"] == s["ncontact"]).all(), f"contact count differs in {(sh['ncontact'] != s['ncontact']).sum()} envs"
-        assert (sh["corner"] == s["corner"]).all(), f"slots 80-83 differ in {(sh['corner'] != s['corner']).any(0).sum()} envs"
+    sh = pr.snap(b)
+    pr.check_free_step(sh, ref)
     report = {}
-    tb._accumulate_snap(report, ref["s64"], ref["s32"], sh, np.ones(n, bool), tb.FIELDS)
-    tb._assert_c_rule(report, f"one physics step, {name}, {kind}, n = {n}")
+    pr.accumulate_snap(report, ref["s64"], ref["s32"], sh, np.ones(n, bool), pr.FIELDS)
+    pr.assert_c_rule(report, f"one physics step, {name}, {kind}, n = {n}")
     return report
 
 
-def _check_control_steps(o, hb, n):
-    """The body of test_gpu_parity.py::test_other_substep_counts_match_oracle: 12 random-action control steps with in-step resets
-    (env.episodeLength = 8) of `hb` against the fp32 oracle `o`."""
-    np.testing.assert_allclose(hb.reset(), o.reset(), atol=2e-4)
-    rng = np.random.default_rng(13)
-    worst = 0.0
-    for t in range(12):
-        a = (2 * rng.random((n, 18)) - 1).astype(np.float32)
-        oo, ro, do = o.step(a)
-        oh, rh, dh = hb.step(a)
-        assert (do == dh.astype(bool)).all(), t
-        assert hb.stats()[16] == o.stats()[16] and hb.stats()[17] == (2 if do.any() else 1)
-        worst = max(worst, float(np.abs(oh - oo).max()))
-        np.testing.assert_allclose(rh, ro, atol=2e-2, rtol=1e-4)
-    assert worst < 5e-3, worst
-    assert o.get("reset_count").sum() > n
-    np.testing.assert_allclose(hb.get("q"), o.get("q"), atol=5e-4)
+def _check_control_steps(o, hb):
+    """12 random-action control steps with in-step resets (env.episodeLength = 8) of `hb` against the fp32 oracle `o`, at the bars of
+    test_gpu_parity.py::test_other_substep_counts_match_oracle."""
+    pr.control_steps(o, hb, np.random.default_rng(13), 12, reset_atol=2e-4, obs_bar=5e-3, rew_atol=2e-2, rew_rtol=1e-4, q_atol=5e-4)
 
 
 # ------------------------------------------------------------------------------------------------- CPU: the samples
@@ -189,7 +147,7 @@ def test_sample_conditions(name):
     sc, _, ms = _setup(name, N)
     for kind in KINDS:
         recs = _teacher_ref(name, kind, N)
-        assert all(tb._same_lists(a, b) for a, b in zip(recs[0]["lists64"], recs[0]["lists32"])), kind
+        assert all(pr.same_lists(a, b) for a, b in zip(recs[0]["lists64"], recs[0]["lists32"])), kind
         for rec in recs:
             assert (rec["s64"]["ncontact"] == rec["s32"]["ncontact"]).all() and (rec["s64"]["corner"] == rec["s32"]["corner"]).all(), kind
         if kind != "hand_on_box":
@@ -200,7 +158,7 @@ def test_sample_conditions(name):
     assert all((c[:, 8] != 2).any() for c in on["lists64"])
     hand_ground, hand_box = int((types == 0).sum()), int((types == 1).sum())
     near = _teacher_ref(name, "hand_near_box", N)[0]
-    E = tb._normal_scale(on["lists64"], on["lists32"], range(N), sc, ms)
+    E = pr.normal_scale(on["lists64"], on["lists32"], range(N), sc, ms)
     print(f"\n{name}: hand / ground {hand_ground}, hand / box {hand_box} entries; E = {E:.3e} m; box / ground counts 0-4 (box alone): "
           f"{np.bincount(_teacher_ref(name, 'box_alone', N)[0]['s64']['ncontact'], minlength=5).tolist()}")
     assert hand_ground > 0 and hand_box > 0
@@ -211,11 +169,11 @@ def test_sample_conditions(name):
     from oracle.oracle import Oracle
     lower = Oracle(sc, ms, f64=True)
     st = _state(name, "hand_near_box", N)
-    st["q"][2] = ts._f32(st["q"][2] - 0.004)
-    tb._load(lower, st)
+    st["q"][2] = ts.f32(st["q"][2] - 0.004)
+    pr.load(lower, st)
     lower.substep(last=True)
-    assert all((c[:, 8] != 2).any() for c in tb._lists(lower, N))
-    assert 0 < E < 1e-7 and min(tb._dist(r, sc, ms) for c in on["lists64"] for r in c[c[:, 8] == 1]) > 1e-3
+    assert all((c[:, 8] != 2).any() for c in pr.lists(lower, N))
+    assert 0 < E < 1e-7 and min(pr.dist(r, sc, ms) for c in on["lists64"] for r in c[c[:, 8] == 1]) > 1e-3
 
 
 # ------------------------------------------------------------------------------------------------- CPU: each varied field bites
@@ -226,22 +184,22 @@ def _margins_substep(name, back):
     rec = _teacher_ref(name, "hand_on_box", N)[0]
     sc, _, ms = _setup(name, N, back)
     o = Oracle(sc, ms, f64=True)
-    tb._load(o, rec["start"])
+    pr.load(o, rec["start"])
     o.substep(last=True)
-    s, lists = tb._snap(o), tb._lists(o, N)
+    s, lists = pr.snap(o), pr.lists(o, N)
     m = {}
     same = s["ncontact"] == rec["s64"]["ncontact"]
-    m["list length"] = (1.0 - same.mean()) / tb.LEFT_OUT                      # the bound on envs whose lists differ in length
+    m["list length"] = (1.0 - same.mean()) / pr.LEFT_OUT                      # the bound on envs whose lists differ in length
     if not same.any():
         return m
     gaps = [np.abs(a[:, [0, 1, 2, 6, 7]] - b[:, [0, 1, 2, 6, 7]]).max() for a, b in zip(lists, rec["lists64"]) if a.shape == b.shape and len(a)]
     m["points / gaps / mu"] = max(gaps, default=0.0) / 2e-6
-    for f in tb.FIELDS:
+    for f in pr.FIELDS:
         e32 = np.abs(rec["s32"][f] - rec["s64"][f])[:, same].max()
-        m[f] = np.abs(s[f] - rec["s64"][f])[:, same].max() / (tb.C_RULE * e32 + 1e-6)
+        m[f] = np.abs(s[f] - rec["s64"][f])[:, same].max() / (pr.C_RULE * e32 + 1e-6)
     ok = np.repeat((s["corner"] >= 0) & (s["corner"] == rec["s64"]["corner"]) & (rec["s32"]["corner"] == rec["s64"]["corner"]) & same, 3, axis=0)
     if ok.any():
-        m["wlam 80-83"] = np.abs(s["lam"] - rec["s64"]["lam"])[ok].max() / (tb.C_RULE * np.abs(rec["s32"]["lam"] - rec["s64"]["lam"])[ok].max() + 1e-6)
+        m["wlam 80-83"] = np.abs(s["lam"] - rec["s64"]["lam"])[ok].max() / (pr.C_RULE * np.abs(rec["s32"]["lam"] - rec["s64"]["lam"])[ok].max() + 1e-6)
     return m
 
 
@@ -281,7 +239,7 @@ def test_each_varied_field_bites(name, field):
     checks = (lambda: _check_lists(lambda: stand_in(N), name),
               lambda: _check_teacher(lambda: stand_in(N), name, "hand_on_box", N),
               lambda: _check_teacher(lambda: stand_in(N), name, "box_alone", N),
-              lambda: _check_control_steps(Oracle(*_setup(name, N_STEP, None, 8)[::2]), stand_in(N_STEP, 8), N_STEP))
+              lambda: _check_control_steps(Oracle(*_setup(name, N_STEP, None, 8)[::2]), stand_in(N_STEP, 8)))
     for check in checks:
         try:
             check()
@@ -303,9 +261,9 @@ def test_fast_yaml_depenetration_cap_is_out_of_reach():
         deepest = min(c[:, 6].min() for c in rec["lists64"] if len(c))
         assert 0 < -deepest * float(sc.erp) / h < default < float(sc.max_depenetration_velocity), (kind, deepest)
     back = Oracle(*_setup("fast_yaml", N, CAP)[::2], f64=True)
-    tb._load(back, rec["start"])
+    pr.load(back, rec["start"])
     back.substep(last=True)
-    assert all(np.array_equal(back.get(f), rec["s64"][f]) for f in tb.FIELDS)
+    assert all(np.array_equal(back.get(f), rec["s64"][f]) for f in pr.FIELDS)
 
 
 def test_stand_in_of_the_configuration_itself_passes():
@@ -346,16 +304,14 @@ def test_world_gravity_loads_the_x_and_y_slides():
 
 @functools.lru_cache(maxsize=None)
 def _big_box_proximity_ref():
-    from tests import proximity_ref as pr
-    from tests import test_proximity as tp
+    from tests import proximity_ref as prox
     sc, _, ms = _setup("big_box", N_QUERY)
-    hp = pr.HandProx(ms, sc)
-    q, box = hp.test_poses(N_QUERY, tp.SEED)
-    return dict(tp._reference(hp, q, box), hp=hp, q=q, box=box)
+    hp = prox.HandProx(ms, sc)
+    q, box = hp.test_poses(N_QUERY, prox.SEED)
+    return dict(prox.reference(hp, q, box), hp=hp, q=q, box=box)
 
 
 def test_big_box_proximity_reference_differs_from_the_default_size():
-    from tests import test_proximity as tp
     r = _big_box_proximity_ref()
     assert r["hp"].box_size == pytest.approx(0.08)
     other = r["hp"].query(r["q"], r["box"], 0.05)
@@ -365,9 +321,8 @@ def test_big_box_proximity_reference_differs_from_the_default_size():
 
 # ------------------------------------------------------------------------------------------------- GPU
 def _hip(name, n, fused=True, episode_length=None):
-    from tests.hip_backend import HipBackend
     sc, _, ms = _setup(name, n, None, episode_length)
-    return HipBackend(sc, ms, fused=fused)
+    return pr.hip(sc, ms, fused)
 
 
 FORMS = pytest.mark.parametrize("fused", [True, False], ids=["k_substep", "k_dynamics+k_solve"])
@@ -407,7 +362,7 @@ def test_fused_physics_launch_equals_single_substep_launches(name):
     from dexrobot_isaac_amd import _abi
     a, b = _hip(name, N), _hip(name, N)
     st = _state(name, "hand_on_box", N)
-    tb._load(a, st), tb._load(b, st)
+    pr.load(a, st), pr.load(b, st)
     a.core.run_stage(_abi.STAGE["PHYSICS"])
     for _ in range(int(_setup(name, N)[0].substeps)):
         b.core.run_stage(_abi.STAGE["SUBSTEP"])
@@ -424,7 +379,7 @@ def test_control_steps_with_resets(name):
     fast_yaml is the true physics=fast case."""
     from oracle.oracle import Oracle
     sc, _, ms = _setup(name, N_STEP, None, 8)
-    _check_control_steps(Oracle(sc, ms), _hip(name, N_STEP, episode_length=8), N_STEP)
+    _check_control_steps(Oracle(sc, ms), _hip(name, N_STEP, episode_length=8))
 
 
 @pytest.mark.gpu
@@ -434,8 +389,6 @@ def test_queries_under_world_gravity():
     from dexrobot_isaac_amd.core import DexSimCore
     from tests import invdyn_ref as ir
     from tests import kindyn_ref as kr
-    from tests import test_inverse_dynamics as tid
-    from tests import test_kindyn as tk
     from tests.query_rig import pose_core
     sc, _, ms = _setup("world", N_QUERY)
     r = _world_gravity_ref()
@@ -443,7 +396,7 @@ def test_queries_under_world_gravity():
     core.reset()
     qd, qdd = ir.random_rates(N_QUERY, 31)
     pose_core(core, r["q"], qd=qd)
-    M, g = tk.gpu_mass(core, N_QUERY)
+    M, g = kr.gpu_mass(core, N_QUERY)
     E_M, E_g = kr.err_M(M, r["M64"]), kr.err_g(g, r["g64"], r["M64"])
     print(f"\nworld: E_M = {E_M:.3g} (fp32 oracle {r['e_M']:.3g}), E_g = {E_g:.3g} (fp32 oracle {r['e_g']:.3g})")
     assert not np.isnan(M).any() and not np.isnan(g).any()
@@ -454,20 +407,20 @@ def test_queries_under_world_gravity():
     full64 = ir.tau_of(M64, b64, qdd)
     e_full = ir.err_tau(ir.tau_of(M32, b32, qdd, np.float32), full64, M64)
     e_bias = ir.err_tau(b32.astype(np.float32), b64, M64)
-    tid.check_tau(tid.gpu_tau(core, N_QUERY, qdd=qdd), full64, M64, e_full, "world, full (qdd, gravity)")
-    tid.check_tau(tid.gpu_tau(core, N_QUERY), b64, M64, e_bias, "world, bias force (gravity)")
-    tid.check_tau(tid.gpu_tau(core, N_QUERY, q=r["q"], qd=np.zeros_like(qd)), r["g64"], r["M64"], r["e_g"], "world, gravity force alone")
+    ir.check_tau(ir.gpu_tau(core, N_QUERY, qdd=qdd), full64, M64, e_full, "world, full (qdd, gravity)")
+    ir.check_tau(ir.gpu_tau(core, N_QUERY), b64, M64, e_bias, "world, bias force (gravity)")
+    ir.check_tau(ir.gpu_tau(core, N_QUERY, q=r["q"], qd=np.zeros_like(qd)), r["g64"], r["M64"], r["e_g"], "world, gravity force alone")
 
 
 @pytest.mark.gpu
 def test_proximity_takes_the_configured_box_size():
     """dexsim_query_proximity with box_size = 0 under big_box against tests/proximity_ref.py at 0.08, test_proximity.py's bounds."""
     from dexrobot_isaac_amd.core import DexSimCore
-    from tests import test_proximity as tp
+    from tests import proximity_ref as prox
     from tests.query_rig import pose_core
     sc, _, ms = _setup("big_box", N_QUERY)
     r = _big_box_proximity_ref()
     core = DexSimCore(sc, ms, "cuda:0")
     core.reset()
     pose_core(core, r["q"], r["box"])
-    tp._check_against(tp.gpu_query(core, N_QUERY), r, label="big_box, box_size = 0: ")
+    prox.check_against(prox.gpu_query(core, N_QUERY), r, label="big_box, box_size = 0: ")

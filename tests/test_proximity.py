@@ -33,11 +33,10 @@ from tests import proximity_ref as pr
 from tests.query_rig import (bits, guarded as _guarded, guards_ok as _guards_ok, load_lib, pose_core, same as _same, setup as _setup,
                              snapshot as _snapshot, stub_core)
 
-N = 70
+N, SEED = pr.ROWS, pr.SEED
 NJ, NCAP, NG, NP = _abi.NJ, _abi.NCAP, _abi.NPROX_GROUPS, _abi.NPROX_PAIRS
-SEED = 23
-SHAPES = {"cap_env": (NCAP, 2, 8), "self_min": (NG, 8), "pair_dist": (NP,)}
-ALL = ("cap_env", "self_min", "pair_dist")
+SHAPES, ALL = pr.SHAPES, pr.ALL
+_reference, gpu_query, _check_against = pr.reference, pr.gpu_query, pr.check_against
 
 
 # ------------------------------------------------------------------------------------------------- CPU
@@ -222,38 +221,6 @@ def hp():
     return pr.HandProx(ms, sc)
 
 
-def _select(r64):
-    """The well-conditioned records of a float64 reference result (module docstring)."""
-    rows = np.arange(r64["min_idx"].shape[0])[:, None]
-    sel = dict(group=(r64["min_margin"] > 1e-4) & (r64["pair"]["sin2"][rows, r64["min_idx"]] >= 0.0025),
-               pair=r64["pair"]["sin2"] >= 0.0025, ground=r64["ground_margin"] > 1e-5)
-    if r64["box"] is not None:
-        bx = r64["box"]
-        zone = (bx["axis_dist"] > 1e-7) & (bx["axis_dist"] < 1e-5)
-        sel["box_d"] = ~zone
-        sel["box"] = (bx["unique"] & (bx["axis_dist"] >= 1e-5)) | (bx["meets"] & ~zone & (bx["face_margin"] > 1e-4))
-    return sel
-
-
-def _reference(hp, q, box, size=None):
-    """float64 and float32 reference of the rows, the selections and the tolerances: 4 x the float32-vs-float64 difference."""
-    r64, r32 = hp.query(q, box, size), hp.query(q, box, size, dtype=np.float32)
-    assert r32["cap_env"].dtype == np.float32 and r32["pair_dist"].dtype == np.float32
-    sel = _select(r64)
-    diff = lambda a, b, m=None: float(np.abs(a.astype(np.float64) - b)[... if m is None else m].max())
-    e = dict(ground_d=diff(r32["cap_env"][:, :, 1, 0], r64["cap_env"][:, :, 1, 0]),
-             ground_p=diff(r32["cap_env"][:, :, 1, 4:7], r64["cap_env"][:, :, 1, 4:7], sel["ground"]),
-             pair_d=diff(r32["pair_dist"], r64["pair_dist"]),
-             group_n=diff(r32["self_min"][..., 1:4], r64["self_min"][..., 1:4], sel["group"]),
-             group_p=diff(r32["self_min"][..., 4:7], r64["self_min"][..., 4:7], sel["group"]))
-    assert (r32["min_idx"][sel["group"]] == r64["min_idx"][sel["group"]]).all()
-    if box is not None:
-        b32, b64 = r32["cap_env"][:, :, 0], r64["cap_env"][:, :, 0]
-        e.update(box_d=diff(b32[..., 0], b64[..., 0], sel["box_d"]), box_n=diff(b32[..., 1:4], b64[..., 1:4], sel["box"]),
-                 box_p=diff(b32[..., 4:7], b64[..., 4:7], sel["box"]), box_t=diff(b32[..., 7], b64[..., 7], sel["box"]))
-    return dict(r64=r64, sel=sel, e=e, tol={k: 4 * v for k, v in e.items()})
-
-
 @pytest.fixture(scope="module")
 def poses(hp):
     q, box = hp.test_poses(N, SEED)
@@ -273,67 +240,6 @@ def test_reference_roundoff_and_selection(hp, poses):
 
 
 # ------------------------------------------------------------------------------------------------- GPU helpers
-def gpu_query(core, k, env_ids=None, q=None, box=None, size=0.0, want=ALL):
-    """core.proximity into guarded outputs: dict of numpy arrays by output name."""
-    import torch
-    bufs = {o: _guarded(k, *SHAPES[o]) for o in want}
-    dev = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32), device=core.device)
-    core.proximity(env_ids=env_ids, q=dev(q), box_pose=dev(box), box_size=size, **{o: v for o, (_, v) in bufs.items()})
-    for full, _ in bufs.values():
-        _guards_ok(full)
-    return {o: v.cpu().numpy() for o, (_, v) in bufs.items()}
-
-
-def _err(dev, ref, mask=None):
-    d = np.abs(dev.astype(np.float64) - ref)
-    return float(d[... if mask is None else mask].max())
-
-
-def _check_against(out, ref, box=True, label=""):
-    """The distance and well-conditioned-record checks of the module docstring; returns the measured device errors."""
-    r64, sel, tol = ref["r64"], ref["sel"], ref["tol"]
-    assert not any(np.isnan(v).any() for v in out.values()), "an element was not written"
-    m = {}
-    ce, sm = out["cap_env"], out["self_min"]
-    m["ground_d"] = _err(ce[:, :, 1, 0], r64["cap_env"][:, :, 1, 0])
-    m["ground_p"] = _err(ce[:, :, 1, 4:7], r64["cap_env"][:, :, 1, 4:7], sel["ground"])
-    m["pair_d"] = _err(out["pair_dist"], r64["pair_dist"])
-    m["group_d"] = _err(sm[..., 0], r64["self_min"][..., 0])
-    m["group_n"] = _err(sm[..., 1:4], r64["self_min"][..., 1:4], sel["group"])
-    m["group_p"] = _err(sm[..., 4:7], r64["self_min"][..., 4:7], sel["group"])
-    if box:
-        b, b64 = ce[:, :, 0], r64["cap_env"][:, :, 0]
-        m["box_d"] = _err(b[..., 0], b64[..., 0], sel["box_d"])
-        m["box_n"], m["box_p"] = _err(b[..., 1:4], b64[..., 1:4], sel["box"]), _err(b[..., 4:7], b64[..., 4:7], sel["box"])
-        m["box_t"] = _err(b[..., 7], b64[..., 7], sel["box"])
-    print(f"{label}device against the float64 reference:", {k: f"{v:.3g}" for k, v in m.items()})
-    print(f"{label}bounds (4 x reference float32 against float64):", {k: f"{v:.3g}" for k, v in tol.items()})
-    # exact parts of the contract
-    assert (ce[:, :, 1, 1:4] == np.array([0, 0, 1], np.float32)).all() and (ce[:, :, 1, 6] == 0).all()
-    assert (ce[:, :, 1, 7][sel["ground"]] == r64["cap_env"][:, :, 1, 7][sel["ground"]]).all() and np.isin(ce[:, :, 1, 7], (0, 1)).all()
-    idx = bits(sm[..., 7])
-    assert (idx[sel["group"]] == r64["min_idx"][sel["group"]]).all(), "a group's closest pair differs on a well-conditioned record"
-    rows = np.arange(idx.shape[0])[:, None]
-    assert (hp_pairs_group(idx) == np.arange(NG)[None, :]).all()                # every record names a pair of its own group ...
-    assert (bits(sm[..., 0]) == bits(out["pair_dist"][rows, idx])).all()       # ... and carries that pair's distance, bit for bit
-    for g in range(NG):                                                        # the minimum of the group, ties to the lowest index
-        members = np.nonzero(PAIR_GROUP == g)[0]
-        d = out["pair_dist"][:, members]
-        assert (members[np.argmin(d, 1)] == idx[:, g]).all()
-    for k in ("ground_d", "ground_p", "pair_d", "group_n", "group_p") + (("box_d", "box_n", "box_p", "box_t") if box else ()):
-        assert m[k] <= tol[k], (k, m[k], tol[k])
-    assert m["group_d"] <= tol["pair_d"], ("group_d", m["group_d"], tol["pair_d"])
-    return m
-
-
-PAIR_GROUP = np.array([t[2] for t in pr.pair_table()])
-
-
-def hp_pairs_group(idx):
-    assert ((idx >= 0) & (idx < NP)).all()
-    return PAIR_GROUP[idx]
-
-
 @pytest.fixture(scope="module")
 def rig(hp, poses):
     """A BlindGrasping core of N envs posed at the test poses (hand and box), and its full query, computed once."""

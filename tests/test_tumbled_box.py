@@ -16,122 +16,24 @@ goes as 1 / dist with dist = gap + rest_offset + capsule radius (4-8 mm), so the
 largest err_n dist of the fp32 oracle against the fp64 oracle on the same sample, computed by the test (3.2e-8 m at N = 256).  States:
 the kernels' error against fp64 at the 99.9th percentile and at the maximum is at most c x the fp32 oracle's own error on the same
 envs, plus the floors 1e-7 and 1e-6 of test_hip_error_is_a_small_multiple_of_fp32_roundoff, whose c = 3 this file uses throughout.
+The references and the comparisons that apply these bounds are in tests/physics_rig.py, shared with the suites that follow this method.
 """
-import functools
-
 import numpy as np
 import pytest
 
-from dexrobot_isaac_amd.config import build_sim_config, default_cfg
+from tests import physics_rig as pr
 from tests import tumbled_states as ts
 
-N, SEED = 256, 11
-C_RULE = 3.0                       # test_gpu_parity.py::test_hip_error_is_a_small_multiple_of_fp32_roundoff
-LEFT_OUT = 0.02
-SYNC = ("q", "qd", "box_pos", "box_quat", "box_lin", "box_ang")
-FIELDS = SYNC + ("cforce",)
-BOX_FIELDS = ("box_pos", "box_quat", "box_lin", "box_ang")
+N = pr.N
 
 
-@functools.lru_cache(maxsize=None)
 def _setup(n):
-    cfg = default_cfg("BlindGrasping")
-    cfg["env"]["numEnvs"] = n
-    sc, model = build_sim_config(cfg)
-    return sc, model, model.to_struct()
+    return pr.setup("BlindGrasping", n)
 
 
-def _state(kind, n):
-    """The first n envs of the N-env sample."""
-    return {k: v[:, :n].copy() for k, v in ts.sample(kind, N, SEED).items()}
-
-
-def _load(b, st):
-    for k, v in st.items():
-        b.set(k, v)
-
-
-def _lists(b, n):
-    return [b.contacts(e).copy() for e in range(n)]
-
-
-def _bg_cache(b):
-    """Warm-start cache of the box / ground slots 80-83: impulses (12, n) and the corner each slot holds (4, n), -1 = not valid."""
-    if hasattr(b, "warm_cache"):
-        lam, tag, gen = b.warm_cache()
-    else:
-        lam, tag, gen = b.get("wlam"), b.get("wtag").astype(np.int64), b.get("wgen")[0].astype(np.int64)
-    tag = tag[80:84]
-    return lam[240:252].copy(), np.where((tag >> 3) == gen[None, :], tag & 7, -1)
-
-
-def _snap(b, fields=FIELDS):
-    s = {f: b.get(f) for f in fields}
-    s["ncontact"] = b.get("ncontact")[0].astype(int)
-    s["lam"], s["corner"] = _bg_cache(b)
-    return s
-
-
-# ------------------------------------------------------------------------------------------------- references, computed once
-def teacher_ref(sc, ms, start):
-    """Three teacher-forced sub-steps on the fp64 and the fp32 oracle (fresh instances): after each, q, qd and the box state of both
-    are put to the fp64 oracle's values rounded to float32, so that every sub-step starts from one state.  Per sub-step: the
-    float32 state it started from, both snapshots and (first sub-step) both contact lists."""
-    from oracle.oracle import Oracle
-    n = int(sc.num_envs)
-    o64, o32 = Oracle(sc, ms, f64=True), Oracle(sc, ms)
-    _load(o64, start), _load(o32, start)
-    out = []
-    for sub in range(3):
-        o64.substep(last=True), o32.substep(last=True)
-        rec = dict(start=start, s64=_snap(o64), s32=_snap(o32))
-        if sub == 0:
-            rec["lists64"], rec["lists32"] = _lists(o64, n), _lists(o32, n)
-            rec["wtag64"], rec["wgen64"] = o64.get("wtag").astype(np.int64), o64.get("wgen")[0].astype(np.int64)
-        out.append(rec)
-        start = {k: ts._f32(o64.get(k)) for k in SYNC}
-        _load(o64, start), _load(o32, start)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def _teacher_ref(kind, n):
-    sc, _, ms = _setup(n)
-    return teacher_ref(sc, ms, _state(kind, n))
-
-
-@functools.lru_cache(maxsize=None)
 def _free_ref(n):
     """The box-alone sample free-running for two physics steps (8 sub-steps) on both oracles: snapshots after each step."""
-    from oracle.oracle import Oracle
-    sc, _, ms = _setup(n)
-    o64, o32 = Oracle(sc, ms, f64=True), Oracle(sc, ms)
-    st = _state("box_alone", n)
-    _load(o64, st), _load(o32, st)
-    out = []
-    for _ in range(2):
-        o64.physics_step(), o32.physics_step()
-        out.append(dict(s64=_snap(o64, BOX_FIELDS), s32=_snap(o32, BOX_FIELDS)))
-    return out
-
-
-def _same_lists(a, b):
-    return a.shape == b.shape and bool((a[:, 8] == b[:, 8]).all()) and bool((a[a[:, 8] != 2, 9] == b[a[:, 8] != 2, 9]).all())
-
-
-def _dist(row, sc, ms):
-    """gap + rest_offset + capsule radius of a hand / box entry: the distance of the axis point from the box."""
-    return row[6] + float(sc.rest_offset) + float(ms.cap_r[int(row[9])])
-
-
-def _normal_scale(lists64, lists32, envs, sc, ms):
-    """E: the largest err_n dist of the fp32 oracle's hand / box normals against the fp64 oracle's."""
-    E = 0.0
-    for e in envs:
-        for r64, r32 in zip(lists64[e], lists32[e]):
-            if r64[8] == 1:
-                E = max(E, np.abs(r32[3:6] - r64[3:6]).max() * _dist(r64, sc, ms))
-    return E
+    return pr.tumbled_free_ref("box_alone", n, 2, pr.BOX_FIELDS)
 
 
 # ------------------------------------------------------------------------------------------------- CPU: the sample and the reference
@@ -149,7 +51,7 @@ def test_sample_covers_the_cases():
     """What the fp64 oracle sees in the two samples; every threshold is half of the count observed at N = 256, seed 11."""
     from oracle.oracle import Oracle
     sc, _, ms = _setup(N)
-    on, alone = _teacher_ref("hand_on_box", N)[0], _teacher_ref("box_alone", N)[0]
+    on, alone = pr.tumbled_teacher_ref("hand_on_box", N)[0], pr.tumbled_teacher_ref("box_alone", N)[0]
     seen = {}
     for name, rec in (("hand_on_box", on), ("box_alone", alone)):
         nbg = np.array([(c[:, 8] == 2).sum() for c in rec["lists64"]])
@@ -163,11 +65,11 @@ def test_sample_covers_the_cases():
     min_gap = min(c[:, 6].min() for c in on["lists64"] if len(c))
     # corner turnover of the box alone over 8 free-running sub-steps: a valid slot holds another corner, or none, one sub-step later
     o = Oracle(sc, ms, f64=True)
-    _load(o, _state("box_alone", N))
+    pr.load(o, pr.tumbled_state("box_alone", N))
     prev, turned, kmax = None, np.zeros(N, bool), 0
     for sub in range(8):
         o.substep(last=sub % 4 == 3)
-        _, cur = _bg_cache(o)
+        _, cur = pr.bg_cache(o)
         if prev is not None:
             turned |= ((prev >= 0) & (cur != prev)).any(0)
         prev, kmax = cur, max(kmax, int(o.get("ncontact").max()))
@@ -189,21 +91,21 @@ def test_both_oracles_list_the_same_contacts():
     """The exclusion rule of the GPU tests leaves out nothing for the reference alone: count, type and capsule agree in every env of
     both samples, over the teacher-forced sub-steps and over the free run; box / ground slots hold the same corners."""
     for kind in ("hand_on_box", "box_alone"):
-        recs = _teacher_ref(kind, N)
-        assert all(_same_lists(a, b) for a, b in zip(recs[0]["lists64"], recs[0]["lists32"])), kind
+        recs = pr.tumbled_teacher_ref(kind, N)
+        assert all(pr.same_lists(a, b) for a, b in zip(recs[0]["lists64"], recs[0]["lists32"])), kind
         for rec in recs:
             assert (rec["s64"]["ncontact"] == rec["s32"]["ncontact"]).all() and (rec["s64"]["corner"] == rec["s32"]["corner"]).all(), kind
     for rec in _free_ref(N):
         assert (rec["s64"]["ncontact"] == rec["s32"]["ncontact"]).all() and (rec["s64"]["corner"] == rec["s32"]["corner"]).all()
     # ... and the fp32 oracle is inside the fixed bound on points and gaps, which its normals are not (module docstring)
-    rec = _teacher_ref("hand_on_box", N)[0]
+    rec = pr.tumbled_teacher_ref("hand_on_box", N)[0]
     sc, _, ms = _setup(N)
     worst_p = max(np.abs(a[:, [0, 1, 2, 6]] - b[:, [0, 1, 2, 6]]).max() for a, b in zip(rec["lists64"], rec["lists32"]) if len(a))
     worst_n = max(np.abs(a[:, 3:6] - b[:, 3:6]).max() for a, b in zip(rec["lists64"], rec["lists32"]) if len(a))
-    E = _normal_scale(rec["lists64"], rec["lists32"], range(N), sc, ms)
+    E = pr.normal_scale(rec["lists64"], rec["lists32"], range(N), sc, ms)
     print(f"\nfp32 oracle against fp64: points / gaps {worst_p:.2e}, normals {worst_n:.2e}, E = {E:.2e} m")
     assert worst_p <= 2e-6 / 10 and 0 < E < 1e-7
-    assert min(_dist(r, sc, ms) for c in rec["lists64"] for r in c[c[:, 8] == 1]) > 1e-3      # no axis point inside the box: dist is a distance
+    assert min(pr.dist(r, sc, ms) for c in rec["lists64"] for r in c[c[:, 8] == 1]) > 1e-3      # no axis point inside the box: dist is a distance
 
 
 def test_oracle_gaps_against_independent_capsule_box_distance():
@@ -212,12 +114,11 @@ def test_oracle_gaps_against_independent_capsule_box_distance():
     raw gap D = gap + rest_offset against the exact capsule / box distance Q of that capsule, L its axis length:
     Q <= D + tol and D - Q <= (0.02 + 2^-11) L + tol -- the inequalities and the tol of
     test_proximity.py::test_against_engine_narrowphase, which only meets faces."""
-    from tests import proximity_ref as pr
-    from tests.test_proximity import N as NP_ROWS, SEED as NP_SEED, _reference
+    from tests import proximity_ref as prox
     sc, _, ms = _setup(N)
-    hp = pr.HandProx(ms, sc)
-    tol = _reference(hp, *hp.test_poses(NP_ROWS, NP_SEED))["tol"]["box_d"]
-    rec = _teacher_ref("hand_on_box", N)[0]
+    hp = prox.HandProx(ms, sc)
+    tol = prox.reference(hp, *hp.test_poses(prox.ROWS, prox.SEED))["tol"]["box_d"]
+    rec = pr.tumbled_teacher_ref("hand_on_box", N)[0]
     st = rec["start"]
     a, b, _ = hp.capsules(st["q"].T, np.float64)
     box = np.concatenate([st["box_pos"].T, st["box_quat"].T], 1)
@@ -244,101 +145,18 @@ def test_oracle_gaps_against_independent_capsule_box_distance():
 
 
 # ------------------------------------------------------------------------------------------------- GPU
-def _agree(same, *counts):
-    for a in counts[1:]:
-        same = same & (counts[0] == a)
-    assert 1.0 - same.mean() <= LEFT_OUT, f"{(~same).sum()} of {same.size} envs left out"
-    return same
-
-
-def _check_manifold(b, rec, sc, ms):
-    """3.1 for the backend under test `b`, which has taken the first teacher-forced sub-step of the hand-on-box sample."""
-    n = len(rec["lists64"])
-    lists = _lists(b, n)
-    same = _agree(np.ones(n, bool), rec["s64"]["ncontact"], rec["s32"]["ncontact"], np.array([len(c) for c in lists]))
-    envs = np.nonzero(same)[0]
-    _, corner = _bg_cache(b)
-    assert (corner[:, same] == rec["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
-    E = _normal_scale(rec["lists64"], rec["lists32"], envs, sc, ms)
-    worst, worst_pg, entries = 0.0, 0.0, 0
-    for e in envs:
-        co, ch = rec["lists64"][e], lists[e]
-        assert _same_lists(co, ch), e                                            # type, and capsule of the hand entries
-        if not len(co):
-            continue
-        worst_pg = max(worst_pg, np.abs(ch[:, [0, 1, 2, 6]] - co[:, [0, 1, 2, 6]]).max())
-        np.testing.assert_allclose(ch[:, [0, 1, 2, 6, 7]], co[:, [0, 1, 2, 6, 7]], rtol=0, atol=2e-6)
-        for ro, rh in zip(co, ch):
-            err = np.abs(rh[3:6] - ro[3:6]).max()
-            if ro[8] == 1:
-                dist = _dist(ro, sc, ms)
-                worst = max(worst, err * dist)
-                assert err <= C_RULE * E / dist + 1e-7, (e, int(ro[9]), err, dist, E)
-            else:
-                assert err <= 1e-7, (e, err)                                     # the ground's normal
-        entries += len(co)
-    print(f"\n{entries} entries in {len(envs)} envs; E = {E:.3e} m, worst err_n dist under test {worst:.3e} m, points / gaps {worst_pg:.2e}")
-    assert entries > 3 * n
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("fused", [True, False], ids=["k_substep", "k_dynamics+k_solve"])
 def test_manifold_on_tumbled_boxes(fused):
-    """One sub-step of the hand-on-box sample: the list of every env against the fp64 oracle's (_check_manifold).  Measured on one
+    """One sub-step of the hand-on-box sample: the list of every env against the fp64 oracle's (pr.check_manifold).  Measured on one
     MI355X, both launch forms: 885 entries in 256 envs, none left out; E = 3.24e-8 m, worst HIP err_n dist 3.12e-8 m, points and
     gaps within 4.0e-8 m."""
-    from tests.hip_backend import HipBackend
     sc, _, ms = _setup(N)
-    rec = _teacher_ref("hand_on_box", N)[0]
-    hb = HipBackend(sc, ms, fused=fused)
-    _load(hb, rec["start"])
+    rec = pr.tumbled_teacher_ref("hand_on_box", N)[0]
+    hb = pr.hip(sc, ms, fused)
+    pr.load(hb, rec["start"])
     hb.substep(last=True)
-    _check_manifold(hb, rec, sc, ms)
-
-
-def _accumulate(report, name, ref, a32, ah, mask):
-    e32, eh = np.abs(a32 - ref)[mask].ravel(), np.abs(ah - ref)[mask].ravel()
-    if not e32.size:
-        return
-    r = report.setdefault(name, [0.0, 0.0, 0.0, 0.0])
-    r[0], r[1] = max(r[0], np.percentile(e32, 99.9)), max(r[1], np.percentile(eh, 99.9))
-    r[2], r[3] = max(r[2], e32.max()), max(r[3], eh.max())
-
-
-def _accumulate_snap(report, s64, s32, sh, same, fields):
-    for f in fields:
-        _accumulate(report, f, s64[f], s32[f], sh[f], np.broadcast_to(same, s64[f].shape))
-    # cached impulses of the box / ground slots that hold the same corner in all three
-    ok = (s64["corner"] >= 0) & (s64["corner"] == s32["corner"]) & (s64["corner"] == sh["corner"]) & same
-    _accumulate(report, "wlam 80-83", s64["lam"], s32["lam"], sh["lam"], np.repeat(ok, 3, axis=0))
-
-
-def _assert_c_rule(report, label):
-    print(f"\n{label}\nfield: p99.9 |f32-f64|, p99.9 |under test-f64|, max |f32-f64|, max |under test-f64|, ratios")
-    for f, r in report.items():
-        print(f"  {f:10s} {r[0]:.3e} {r[1]:.3e} {r[2]:.3e} {r[3]:.3e}   {r[1] / max(r[0], 1e-30):.2f} {r[3] / max(r[2], 1e-30):.2f}")
-    for f, r in report.items():
-        assert r[1] <= C_RULE * r[0] + 1e-7, (f, r)
-        assert r[3] <= C_RULE * r[2] + 1e-6, (f, r)
-
-
-def _check_teacher_forced(make, kind, n, recs=None, label=""):
-    """3.2 for the backend that make() returns; recs: the references, those of the default configuration if None."""
-    recs = _teacher_ref(kind, n) if recs is None else recs
-    b = make()
-    same, report = np.ones(n, bool), {}
-    for rec in recs:
-        _load(b, rec["start"])
-        b.substep(last=True)
-        sh = _snap(b)
-        if kind == "box_alone":
-            assert sh["ncontact"].max() <= 4 and rec["s64"]["ncontact"].max() <= 4       # the early box solve really ran
-        same = _agree(same, rec["s64"]["ncontact"], rec["s32"]["ncontact"], sh["ncontact"])   # (an env left out stays out: its cache differs)
-        assert (sh["corner"][:, same] == rec["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
-        _accumulate_snap(report, rec["s64"], rec["s32"], sh, same, FIELDS)
-    _assert_c_rule(report, f"teacher-forced, {label}{kind}, n = {n}")
-    assert "wlam 80-83" in report
-    return report
+    pr.check_manifold(hb, rec, sc, ms)
 
 
 # Measured on one MI355X, ratios |HIP - fp64| / |fp32 oracle - fp64| at the 99.9th percentile / at the maximum (the fp32 oracle's own
@@ -358,23 +176,8 @@ def _check_teacher_forced(make, kind, n, recs=None, label=""):
 @pytest.mark.parametrize("fused", [True, False], ids=["k_substep", "k_dynamics+k_solve"])
 @pytest.mark.parametrize("kind,n", [("hand_on_box", N), ("box_alone", N), ("box_alone", 200)], ids=["hand_on_box", "box_alone", "box_alone-padded"])
 def test_teacher_forced_substeps_on_tumbled_boxes(kind, n, fused):
-    from tests.hip_backend import HipBackend
     sc, _, ms = _setup(n)
-    _check_teacher_forced(lambda: HipBackend(sc, ms, fused=fused), kind, n)
-
-
-def _check_corner_turnover(b, n):
-    """3.3 for the backend under test `b`, loaded with the box-alone sample."""
-    report = {}
-    for step, rec in enumerate(_free_ref(n)):
-        b.physics_step()
-        sh = _snap(b, BOX_FIELDS)
-        for s in (rec["s64"], rec["s32"]):
-            assert (sh["ncontact"] == s["ncontact"]).all(), f"contact count differs in {(sh['ncontact'] != s['ncontact']).sum()} envs after step {step}"
-            assert (sh["corner"] == s["corner"]).all(), f"slots 80-83 differ in {(sh['corner'] != s['corner']).any(0).sum()} envs after step {step}"
-        assert sh["ncontact"].max() <= 4
-        _accumulate_snap(report, rec["s64"], rec["s32"], sh, np.ones(n, bool), BOX_FIELDS)
-    _assert_c_rule(report, f"free-running, box alone, n = {n}")
+    pr.check_teacher_forced(lambda: pr.hip(sc, ms, fused), pr.tumbled_teacher_ref(kind, n), kind)
 
 
 @pytest.mark.gpu
@@ -382,26 +185,31 @@ def _check_corner_turnover(b, n):
 def test_corner_turnover_free_running(n):
     """Two physics steps = 8 sub-steps of the tumbling box alone: corners leave the list and move between slots (43 of 256 envs), so
     a slot that kept a stale corner's impulse, or dropped a valid one, shows in the box state."""
-    from tests.hip_backend import HipBackend
     sc, _, ms = _setup(n)
-    hb = HipBackend(sc, ms)
-    _load(hb, _state("box_alone", n))
-    _check_corner_turnover(hb, n)
+    hb = pr.hip(sc, ms)
+    pr.load(hb, pr.tumbled_state("box_alone", n))
+    report = {}
+    for step, rec in enumerate(_free_ref(n)):
+        hb.physics_step()
+        sh = pr.snap(hb, pr.BOX_FIELDS)
+        pr.check_free_step(sh, rec, f" after step {step}")
+        assert sh["ncontact"].max() <= 4
+        pr.accumulate_snap(report, rec["s64"], rec["s32"], sh, np.ones(n, bool), pr.BOX_FIELDS)
+    pr.assert_c_rule(report, f"free-running, box alone, n = {n}")
 
 
 @pytest.mark.gpu
 def test_hand_on_tumbled_box_is_bitwise_reproducible():
     """test_general_contact_path_is_bitwise_reproducible on the hand-on-box sample: two instances, two physics steps."""
     import torch
-    from tests.hip_backend import HipBackend
     sc, _, ms = _setup(N)
     outs = []
     for _ in range(2):
-        hb = HipBackend(sc, ms)
-        _load(hb, _state("hand_on_box", N))
+        hb = pr.hip(sc, ms)
+        pr.load(hb, pr.tumbled_state("hand_on_box", N))
         hb.physics_step(), hb.physics_step()
         torch.cuda.synchronize()
-        outs.append([hb.core.field(f).clone() for f in SYNC + ("cforce", "wlam", "wgen", "ncontact")])
+        outs.append([hb.core.field(f).clone() for f in pr.SYNC + ("cforce", "wlam", "wgen", "ncontact")])
     assert outs[0][-1].max() > 4
     for a, b in zip(*outs):
         assert torch.equal(a, b)

@@ -11,7 +11,7 @@ from every limit.  Three parts of the step kernels therefore run without anythin
 
 N = 256 envs, seed 11 (four workgroups), and the first 200 envs (last workgroup padded).  Bounds: none of this file's own.  States and
 published quantities: the error against fp64 at the 99.9th percentile and at the maximum is at most c = 3 x the fp32 oracle's own error
-on the same entries, plus the floors 1e-7 and 1e-6 (tests/test_tumbled_box.py::_accumulate / _assert_c_rule).  Contact counts exact.
+on the same entries, plus the floors 1e-7 and 1e-6 (tests/physics_rig.py::accumulate / assert_c_rule).  Contact counts exact.
 
 The clamp.  A third fp64 oracle instance runs a model whose limits are widened by +-10 and is re-synchronised from the clamped fp64
 oracle before every sub-step; its unclamped q classifies every joint-sub-step: beyond a stop by more than 1e-5 rad -- clamped, inside by
@@ -30,13 +30,11 @@ import functools
 import numpy as np
 import pytest
 
-from dexrobot_isaac_amd.config import build_sim_config, default_cfg
-from dexrobot_isaac_amd.hand_model import HandModel
-from tests import test_tumbled_box as tb
+from tests import physics_rig as pr
 from tests import wide_states as ws
-from tests.tumbled_states import _f32
+from tests.tumbled_states import f32
 
-N, SEED, PADDED = tb.N, tb.SEED, 200
+N, SEED, PADDED = pr.N, pr.SEED, 200
 KINDS = ("free", "stops")
 WIDEN = 10.0                            # the third instance's limits: lo - 10, hi + 10
 AMBIGUOUS = 1e-5                        # rad: an unclamped q this close to a stop is decided by roundoff
@@ -47,22 +45,9 @@ PUBLISHED = ("site_pose", "hand_vel")
 
 
 # ------------------------------------------------------------------------------------------------- configurations and states
-@functools.lru_cache(maxsize=None)
 def _setup(task, n, name=None):
-    """(sc, model, ms) for n envs; name: a model of tests/test_model_structure.py::MODELS that lacks the folded structure."""
-    cfg = default_cfg(task)
-    cfg["env"]["numEnvs"] = n
-    model = None
-    if name is not None:
-        from tests.test_model_structure import MODELS
-        edit, rot = MODELS[name]
-        if rot is not None:
-            cfg["env"]["initialHandRot"] = list(rot)
-        model = HandModel(cfg["env"]["initialHandPos"], cfg["env"]["initialHandRot"])
-        if edit is not None:
-            edit(model)
-    sc, model = build_sim_config(cfg, model=model)
-    return sc, model, model.to_struct()
+    """(sc, model, ms) for n envs; name: a model of pr.MODELS that lacks the folded structure."""
+    return pr.setup(task, n, model=name)
 
 
 def _variant(task, n, name=None, widen=0.0, lower=None):
@@ -83,12 +68,12 @@ def _state(kind, n, task="BlindGrasping", name=None):
 
 
 def _sync(task):
-    return tb.SYNC if task == "BlindGrasping" else HAND_FIELDS
+    return pr.SYNC if task == "BlindGrasping" else HAND_FIELDS
 
 
 def _snap(b, task):
     if task == "BlindGrasping":
-        return tb._snap(b)
+        return pr.snap(b)
     s = {f: b.get(f) for f in HAND_FIELDS}
     s["ncontact"] = b.get("ncontact")[0].astype(int)
     return s
@@ -104,7 +89,7 @@ def _classify(qw, lo, hi):
 # ------------------------------------------------------------------------------------------------- references, computed once
 @functools.lru_cache(maxsize=None)
 def _teacher_ref(kind, n, task="BlindGrasping", name=None):
-    """tb.teacher_ref with the widened instance next to the two oracles: three teacher-forced sub-steps, after each q, qd and the box
+    """pr.teacher_ref with the widened instance next to the two oracles: three teacher-forced sub-steps, after each q, qd and the box
     state of all three are put to the (clamped) fp64 oracle's values rounded to float32.  Per sub-step: the float32 state it started
     from, both snapshots, both contact lists, the widened instance's unclamped q and qd and the classification they give; with the
     last one, what both oracles publish from their own final state."""
@@ -116,13 +101,13 @@ def _teacher_ref(kind, n, task="BlindGrasping", name=None):
     out = []
     for sub in range(3):
         for o in (o64, o32, w64):
-            tb._load(o, start)
+            pr.load(o, start)
             o.substep(last=True)
-        rec = dict(start=start, s64=_snap(o64, task), s32=_snap(o32, task), lists64=tb._lists(o64, n), lists32=tb._lists(o32, n),
+        rec = dict(start=start, s64=_snap(o64, task), s32=_snap(o32, task), lists64=pr.lists(o64, n), lists32=pr.lists(o32, n),
                    qw=w64.get("q"), qdw=w64.get("qd"))
         rec["at_lo"], rec["at_hi"], rec["amb"] = _classify(rec["qw"], lo, hi)
         out.append(rec)
-        start = dict(start, **{k: _f32(o64.get(k)) for k in _sync(task)})
+        start = dict(start, **{k: f32(o64.get(k)) for k in _sync(task)})
     o64.publish(), o32.publish()
     out[-1]["pub64"], out[-1]["pub32"] = {f: o64.get(f) for f in PUBLISHED}, {f: o32.get(f) for f in PUBLISHED}
     return out
@@ -138,29 +123,29 @@ def _free_ref(n):
     o64, o32, w64 = Oracle(sc, ms, f64=True), Oracle(sc, ms), Oracle(*_variant("BlindGrasping", n, widen=WIDEN), f64=True)
     st = _state("stops", n)
     for o in (o64, o32, w64):
-        tb._load(o, st)
+        pr.load(o, st)
     left, subs = np.zeros(n, bool), int(sc.substeps)
     for sub in range(subs):
-        tb._load(w64, {k: o64.get(k) for k in tb.SYNC})
+        pr.load(w64, {k: o64.get(k) for k in pr.SYNC})
         for o in (o64, o32, w64):
             o.substep(last=sub == subs - 1)
         at_lo, at_hi, amb = _classify(w64.get("q"), lo, hi)
         left |= amb.any(0)
-    return dict(s64=tb._snap(o64), s32=tb._snap(o32), left=left, at_lo=at_lo, at_hi=at_hi)
+    return dict(s64=pr.snap(o64), s32=pr.snap(o32), left=left, at_lo=at_lo, at_hi=at_hi)
 
 
 # ------------------------------------------------------------------------------------------------- the comparisons (GPU tests and stand-ins)
 def _accumulate_rec(report, s64, s32, sh, amb, left):
-    """tb._accumulate per field over the envs not in `left`; qd without the ambiguous joints."""
+    """pr.accumulate per field over the envs not in `left`; qd without the ambiguous joints."""
     keep = ~left
     for f in s64:
         if f in ("ncontact", "corner", "lam"):
             continue
         mask = np.broadcast_to(keep, s64[f].shape)
-        tb._accumulate(report, f, s64[f], s32[f], sh[f], mask & ~amb if f == "qd" else mask)
+        pr.accumulate(report, f, s64[f], s32[f], sh[f], mask & ~amb if f == "qd" else mask)
     if "lam" in s64:
         ok = (s64["corner"] >= 0) & (s64["corner"] == s32["corner"]) & (s64["corner"] == sh["corner"]) & keep
-        tb._accumulate(report, "wlam 80-83", s64["lam"], s32["lam"], sh["lam"], np.repeat(ok, 3, axis=0))
+        pr.accumulate(report, "wlam 80-83", s64["lam"], s32["lam"], sh["lam"], np.repeat(ok, 3, axis=0))
 
 
 def _assert_no_hand_contact(sh, rec, task):
@@ -188,10 +173,10 @@ def _run_teacher(make, kind, n, task="BlindGrasping", name=None, exact=True):
     lo, hi = ws.limits(_setup(task, n, name)[2])
     b, report, none_left = make(), {}, np.zeros(n, bool)
     for rec in recs:
-        tb._load(b, rec["start"])
+        pr.load(b, rec["start"])
         b.substep(last=True)
         sh = _snap(b, task)
-        assert rec["amb"].any(0).mean() <= tb.LEFT_OUT, f"{rec['amb'].any(0).sum()} of {n} envs hold an ambiguous joint"
+        assert rec["amb"].any(0).mean() <= pr.LEFT_OUT, f"{rec['amb'].any(0).sum()} of {n} envs hold an ambiguous joint"
         if exact:
             _assert_no_hand_contact(sh, rec, task)
             _assert_on_the_stops(sh, rec["at_lo"], rec["at_hi"], lo, hi)
@@ -206,7 +191,7 @@ def _label(what, kind, n, task, name):
 def _check_teacher(make, kind, n, task="BlindGrasping", name=None):
     """Item 5: states after each of three teacher-forced sub-steps by the c rule, contact counts and clamped joints exact."""
     _, report = _run_teacher(make, kind, n, task, name)
-    tb._assert_c_rule(report, _label("teacher-forced", kind, n, task, name))
+    pr.assert_c_rule(report, _label("teacher-forced", kind, n, task, name))
     assert ("wlam 80-83" in report) == (task == "BlindGrasping")
     return report
 
@@ -227,7 +212,7 @@ def _published_report(make, kind, n, task="BlindGrasping", name=None):
     b.publish()
     report, every = {}, np.ones(n, bool)
     for f in PUBLISHED:
-        tb._accumulate(report, f, rec["pub64"][f], rec["pub32"][f], b.get(f), np.broadcast_to(every, rec["pub64"][f].shape))
+        pr.accumulate(report, f, rec["pub64"][f], rec["pub32"][f], b.get(f), np.broadcast_to(every, rec["pub64"][f].shape))
     core = getattr(b, "core", None)
     if core is not None:
         import torch
@@ -238,8 +223,8 @@ def _published_report(make, kind, n, task="BlindGrasping", name=None):
         rbs = core.rigid_body_states[:, :kr.NB].cpu().numpy().astype(np.float64)[envs]
         p64, t64 = _body_states(hk, rec["s64"]["q"], rec["s64"]["qd"], np.float64, envs)
         p32, t32 = _body_states(hk, rec["s32"]["q"], rec["s32"]["qd"], np.float32, envs)
-        tb._accumulate(report, "body pos", p64, p32, rbs[:, :, 0:3], np.ones(p64.shape, bool))
-        tb._accumulate(report, "body twist", t64, t32, rbs[:, :, 7:13], np.ones(t64.shape, bool))
+        pr.accumulate(report, "body pos", p64, p32, rbs[:, :, 0:3], np.ones(p64.shape, bool))
+        pr.accumulate(report, "body twist", t64, t32, rbs[:, :, 7:13], np.ones(t64.shape, bool))
     return report
 
 
@@ -248,7 +233,7 @@ def _check_published(make, kind, n, task="BlindGrasping", name=None):
     against the oracles; on a backend with rigid_body_states also the origins and twists of the 37 hand bodies of every fourth env,
     against tests/kindyn_ref.HandKin in float64 on the fp64 oracle's final state and in float32 on the fp32 oracle's."""
     report = _published_report(make, kind, n, task, name)
-    tb._assert_c_rule(report, _label("published", kind, n, task, name))
+    pr.assert_c_rule(report, _label("published", kind, n, task, name))
     return report
 
 
@@ -257,17 +242,17 @@ def _check_physics_step(make, n, exact=True):
     rule over the envs that held no ambiguous joint in any sub-step, joints clamped in the last sub-step on their stops."""
     ref = _free_ref(n)
     lo, hi = ws.limits(_setup("BlindGrasping", n)[2])
-    assert ref["left"].mean() <= tb.LEFT_OUT, f"{ref['left'].sum()} of {n} envs left out"
+    assert ref["left"].mean() <= pr.LEFT_OUT, f"{ref['left'].sum()} of {n} envs left out"
     b = make()
-    tb._load(b, _state("stops", n))
+    pr.load(b, _state("stops", n))
     b.physics_step()
-    sh = tb._snap(b)
+    sh = pr.snap(b)
     if exact:
         _assert_no_hand_contact(sh, ref, "BlindGrasping")
         _assert_on_the_stops(sh, ref["at_lo"], ref["at_hi"], lo, hi, ~ref["left"])
     report = {}
     _accumulate_rec(report, ref["s64"], ref["s32"], sh, np.zeros((26, n), bool), ref["left"])
-    tb._assert_c_rule(report, f"one physics step, stops, n = {n}")
+    pr.assert_c_rule(report, f"one physics step, stops, n = {n}")
     return report
 
 
@@ -303,11 +288,11 @@ def test_sample_covers_the_cases():
     # the free run takes the same sub-steps as physics_step, and lists no hand contact either
     sc, _, ms = _setup("BlindGrasping", N)
     o = Oracle(sc, ms, f64=True)
-    tb._load(o, _state("stops", N))
+    pr.load(o, _state("stops", N))
     o.physics_step()
     ref = _free_ref(N)
-    assert all(np.array_equal(o.get(f), ref["s64"][f]) for f in tb.FIELDS) and ref["s64"]["ncontact"].max() <= 4
-    assert all((c[:, 8] == 2).all() for c in tb._lists(o, N))
+    assert all(np.array_equal(o.get(f), ref["s64"][f]) for f in pr.FIELDS) and ref["s64"]["ncontact"].max() <= 4
+    assert all((c[:, 8] == 2).all() for c in pr.lists(o, N))
 
 
 @pytest.mark.parametrize("task,name", [("BlindGrasping", None), ("BaseTask", None), ("BlindGrasping", "all")], ids=["default", "basetask", "model-all"])
@@ -385,6 +370,9 @@ class _StandIn:
     def contacts(self, e):
         return self.o.contacts(e)
 
+    def warm_cache(self):
+        return self.o.warm_cache()
+
     def substep(self, last=True):
         self.o.substep(last=last)
 
@@ -422,7 +410,7 @@ class _ClampKeepsSpeed(_StandIn):
 
     def substep(self, last=True):
         self.o.substep(last=last)
-        self.o.set("q", _f32(np.clip(self.o.get("q"), *self.lim)))
+        self.o.set("q", f32(np.clip(self.o.get("q"), *self.lim)))
 
 
 class _WrongQuadrant(_StandIn):
@@ -434,7 +422,7 @@ class _WrongQuadrant(_StandIn):
         if k == "q":
             self.flip = v[THUMB] > 0.5 * np.pi
         if k in ("q", "targets"):
-            v[THUMB] = np.where(self.flip, _f32(np.pi - v[THUMB]), v[THUMB])
+            v[THUMB] = np.where(self.flip, f32(np.pi - v[THUMB]), v[THUMB])
         if k == "qd":
             v[THUMB] = np.where(self.flip, -v[THUMB], v[THUMB])
         self.o.set(k, v)
@@ -450,7 +438,7 @@ class _WrongQuadrant(_StandIn):
 
 def _margin(report):
     """By how many bounds the worst field of a report misses (<= 1: inside)."""
-    return max(max(r[1] / (tb.C_RULE * r[0] + 1e-7), r[3] / (tb.C_RULE * r[2] + 1e-6)) for r in report.values())
+    return max(max(r[1] / (pr.C_RULE * r[0] + 1e-7), r[3] / (pr.C_RULE * r[2] + 1e-6)) for r in report.values())
 
 
 def _refused(check):
@@ -469,7 +457,7 @@ def test_fp32_oracle_in_the_kernels_place_passes():
         sc, _, ms = _setup(task, N, name)
         for kind in KINDS:
             r = _check_teacher(lambda: Oracle(sc, ms), kind, N, task, name)
-            assert _margin(r) <= 1.0 / tb.C_RULE + 1e-12                       # it IS the fp32 reference
+            assert _margin(r) <= 1.0 / pr.C_RULE + 1e-12                       # it IS the fp32 reference
     sc, _, ms = _setup("BlindGrasping", N)
     for kind in KINDS:
         _check_published(lambda: Oracle(sc, ms), kind, N)
@@ -486,7 +474,7 @@ def test_each_new_dimension_bites():
     A kernel with one of these defects would therefore fail; the thresholds below are a tenth of the measured margins."""
     sc, _, ms = _setup("BlindGrasping", N)
     full = _run_teacher(lambda: _NoVelocityTerms(sc, ms, velocity_terms=True), "free", N)[1]
-    tb._assert_c_rule(full, "numpy integrator in float32, b(q, qd)")           # the integrator itself is inside the bound ...
+    pr.assert_c_rule(full, "numpy integrator in float32, b(q, qd)")           # the integrator itself is inside the bound ...
     rec = _teacher_ref("stops", N)[0]
     assert rec["at_hi"][LOWERED].sum() >= 5                                     # (b) lowers a limit that joints of the sample sit on
     low = _variant("BlindGrasping", N, lower=LOWERED)
@@ -514,9 +502,8 @@ def test_each_new_dimension_bites():
 
 # ------------------------------------------------------------------------------------------------- GPU
 def _hip(n, fused=True, task="BlindGrasping", name=None):
-    from tests.hip_backend import HipBackend
     sc, _, ms = _setup(task, n, name)
-    return HipBackend(sc, ms, fused=fused)
+    return pr.hip(sc, ms, fused)
 
 
 FORMS = pytest.mark.parametrize("fused", [True, False], ids=["k_substep", "k_dynamics+k_solve"])
@@ -558,7 +545,7 @@ def test_one_fused_physics_step_from_the_stops(n):
     _check_physics_step(lambda: _hip(n), n)
 
 
-HIP_STATE = tb.SYNC + ("cforce", "site_pose", "hand_vel", "ncontact", "wlam", "wgen")
+HIP_STATE = pr.SYNC + ("cforce", "site_pose", "hand_vel", "ncontact", "wlam", "wgen")
 
 
 @pytest.mark.gpu
@@ -569,7 +556,7 @@ def test_fused_physics_launch_is_four_substep_launches_and_reproducible():
     st = _state("stops", N)
     a, b, c = _hip(N), _hip(N), _hip(N)
     for x in (a, b, c):
-        tb._load(x, st)
+        pr.load(x, st)
     a.core.run_stage(_abi.STAGE["PHYSICS"]), c.core.run_stage(_abi.STAGE["PHYSICS"])
     for _ in range(int(_setup("BlindGrasping", N)[0].substeps)):
         b.core.run_stage(_abi.STAGE["SUBSTEP"])
@@ -590,16 +577,15 @@ def test_specialised_kernels_equal_the_general_ones_at_wide_poses(kind):
     """The model structure folded out of the chains (tests/test_model_structure.py) removes exact zeros and ones: `==` over the three
     teacher-forced sub-steps, where the velocity products and the base rotations are no longer small."""
     import torch
-    from tests.test_model_structure import general_path
     spec = _hip(N)
-    with general_path():
+    with pr.general_path():
         gen = _hip(N)
     for sub, rec in enumerate(_teacher_ref(kind, N)):
         for b in (spec, gen):
-            tb._load(b, rec["start"])
+            pr.load(b, rec["start"])
             b.substep(last=True)
         torch.cuda.synchronize()
-        for f in tb.SYNC + ("cforce", "ncontact", "wlam"):
+        for f in pr.SYNC + ("cforce", "ncontact", "wlam"):
             assert torch.equal(spec.core.field(f), gen.core.field(f)), f"sub-step {sub}: {f} differs"
     for b in (spec, gen):
         b.publish()

@@ -1,6 +1,6 @@
 """Seeded states with a TUMBLED box for the physics parity tests (tests/test_tumbled_box.py, tests/test_gpu_parity.py).  Plain numpy.
 
-test_gpu_parity._random_state only yaws the box, so it always rests on its -z face: the box wave then lists corners 0, 1, 2, 3 or
+physics_rig.random_state only yaws the box, so it always rests on its -z face: the box wave then lists corners 0, 1, 2, 3 or
 nothing, a cache slot 80 + k never changes its corner, and the hand meets faces.  The states here put the box on one or two corners, on
 another face, on an edge and anywhere in between, with the lowest corner within the contact band of the ground, so that the corner list,
 its warm-start tags and the edge / vertex branches of the narrowphase all see more than one input.
@@ -15,7 +15,7 @@ import numpy as np
 CORNERS = np.array([[(1 if i & 1 else -1), (1 if i & 2 else -1), (1 if i & 4 else -1)] for i in range(8)], dtype=np.float64)
 
 
-def _f32(x):
+def f32(x):
     return np.asarray(x, dtype=np.float32).astype(np.float64)
 
 
@@ -76,15 +76,15 @@ def corner_heights(quat, box_size):
 
 def _place_box(rng, st, n, box_size, low_mm):
     """Tumbled orientation; the height puts the lowest corner at U(low_mm) millimetres above the ground."""
-    quat = _f32(box_orientations(rng, n))
-    quat = _f32(quat / np.linalg.norm(quat, axis=1, keepdims=True))        # float32 numbers, unit to float32 roundoff
+    quat = f32(box_orientations(rng, n))
+    quat = f32(quat / np.linalg.norm(quat, axis=1, keepdims=True))        # float32 numbers, unit to float32 roundoff
     st["box_quat"] = quat.T.copy()
     st["box_pos"][2] = 1e-3 * rng.uniform(low_mm[0], low_mm[1], n) - corner_heights(quat, box_size).min(1)
 
 
 def _base_state(rng, model, n, near_box):
-    from tests.test_gpu_parity import _random_state
-    return _random_state(rng, model, n, near_box=near_box)
+    from tests.physics_rig import random_state
+    return random_state(rng, model, n, near_box=near_box)
 
 
 def hand_clear_state(rng, model, n, box_size=0.05):
@@ -92,13 +92,13 @@ def hand_clear_state(rng, model, n, box_size=0.05):
     with its lowest corner at U(-0.5, 1.5) mm."""
     st = _base_state(rng, model, n, False)
     st["q"][2] = rng.uniform(0.0, 0.2, n)
-    st["q"] = _f32(st["q"])
+    st["q"] = f32(st["q"])
     st["qd"] = np.zeros((26, n))
     st["targets"] = st["q"].copy()
     _place_box(rng, st, n, box_size, (-0.5, 1.5))
     st["box_ang"] = rng.normal(0, 1.5, (3, n))
     st["box_lin"] = rng.normal(0, 0.05, (3, n))
-    return {k: _f32(v) for k, v in st.items()}
+    return {k: f32(v) for k, v in st.items()}
 
 
 def hand_on_box_state(rng, model, sc, ms, n, near=False):
@@ -113,9 +113,9 @@ def hand_on_box_state(rng, model, sc, ms, n, near=False):
     st["qd"] *= 0.3
     st["box_ang"] = rng.normal(0, 0.5, (3, n))
     _place_box(rng, st, n, float(sc.box_size), (-0.3, 0.8))
-    st = {k: _f32(v) for k, v in st.items()}
+    st = {k: f32(v) for k, v in st.items()}
     lad = Oracle(sc, ms, f64=True)
-    rungs = _f32(np.arange(0.05, -0.44 - 1e-9, -0.002))
+    rungs = f32(np.arange(0.05, -0.44 - 1e-9, -0.002))
     first = np.full(n, -1)
     nbg = None
     for i, z in enumerate(rungs):
@@ -134,10 +134,10 @@ def hand_on_box_state(rng, model, sc, ms, n, near=False):
             break
     assert (first >= 0).all(), "a hand never reached box or ground"
     past = 1e-3 * rng.uniform(0.0, 2.0, n)
-    st["q"][2] = _f32(rungs[first - 1] + past) if near else _f32(rungs[first] - past)
+    st["q"][2] = f32(rungs[first - 1] + past) if near else f32(rungs[first] - past)
     tg = st["q"] + rng.normal(0, 0.03, (26, n))
     tg[2] = st["q"][2] - 0.01
-    st["targets"] = _f32(tg)
+    st["targets"] = f32(tg)
     return st
 
 
@@ -150,11 +150,11 @@ def _draw(kind, n, seed, sc, model):
 
 
 @functools.lru_cache(maxsize=None)
-def _cached(kind, n, seed):
+def _default_config(n):
     from dexrobot_isaac_amd.config import build_sim_config, default_cfg
     cfg = default_cfg("BlindGrasping")
     cfg["env"]["numEnvs"] = n
-    return _draw(kind, n, seed, *build_sim_config(cfg))
+    return build_sim_config(cfg)
 
 
 _BY_CONFIG = {}
@@ -164,13 +164,9 @@ def sample(kind, n=256, seed=11, config=None):
     """The "box_alone" / "hand_on_box" / "hand_near_box" state of n envs, built once per process; a fresh copy.  `config`: None for
     the default BlindGrasping configuration, or (sc, model) -- a DexSimConfig of n envs and the hand model it goes with; the sample is
     kept per value of the two structs."""
-    if config is None:
-        st = _cached(kind, n, seed)
-    else:
-        sc, model = config
-        assert int(sc.num_envs) == n
-        key = (kind, n, seed, bytes(sc), bytes(model.to_struct()))
-        if key not in _BY_CONFIG:
-            _BY_CONFIG[key] = _draw(kind, n, seed, sc, model)
-        st = _BY_CONFIG[key]
-    return {k: v.copy() for k, v in st.items()}
+    sc, model = _default_config(n) if config is None else config
+    assert int(sc.num_envs) == n
+    key = (kind, n, seed, bytes(sc), bytes(model.to_struct()))
+    if key not in _BY_CONFIG:
+        _BY_CONFIG[key] = _draw(kind, n, seed, sc, model)
+    return {k: v.copy() for k, v in _BY_CONFIG[key].items()}

@@ -1,6 +1,6 @@
 """Seeded contact-free states over the hand's WHOLE joint range for the physics parity tests (tests/test_wide_poses.py).  Plain numpy.
 
-test_gpu_parity._random_state, and tests/tumbled_states.py on top of it, draw finger joints from [0, 0.5] rad, base rotations from
+physics_rig.random_state, and tests/tumbled_states.py on top of it, draw finger joints from [0, 0.5] rad, base rotations from
 +-0.3 rad and joint speeds from N(0, 0.3), clipped to at least 1 mm / 1 mrad inside every limit: the velocity terms of the bias force
 are worth a few bounds there, no half-angle leaves quadrant 0 of sincos_joint, and no joint reaches a stop.  Here (h = dt / substeps):
   fingers        q ~ U(lo, hi) per joint, qd ~ N(0, 3), target q + N(0, 0.05)
@@ -21,7 +21,7 @@ import functools
 
 import numpy as np
 
-from tests.tumbled_states import _f32
+from tests.tumbled_states import f32
 
 P_STOP, STOP_BAND, STOP_SPEED, STOP_TARGET = 0.4, 3.0, (2.0, 6.0), 0.2
 
@@ -43,7 +43,7 @@ def _draw(kind, n, seed, sc, model):
     qd = rng.normal(0, 3.0, (26, n))
     qd[0:3] = rng.normal(0, 0.5, (3, n))
     qd[3:6] = rng.normal(0, 2.0, (3, n))
-    q, qd = _f32(q), _f32(qd)
+    q, qd = f32(q), f32(qd)
     tg = q + rng.normal(0, 0.05, (26, n))
     tg[0:6] = q[0:6] + h * qd[0:6] + rng.normal(0, 0.002, (6, n))
     # the stops: drawn for both kinds, so that "free" and "stops" differ in nothing else
@@ -57,11 +57,11 @@ def _draw(kind, n, seed, sc, model):
         q[6:] = np.where(pick, np.where(upper, fhi - depth, flo + depth), q[6:])
         qd[6:] = np.where(pick, np.where(upper, speed, -speed), qd[6:])
         tg[6:] = np.where(pick, np.where(upper, fhi + STOP_TARGET, flo - STOP_TARGET), tg[6:])
-        q[6:] = np.clip(_f32(q[6:]), flo, fhi)               # rounding to float32 must not put a joint outside its range
+        q[6:] = np.clip(f32(q[6:]), flo, fhi)               # rounding to float32 must not put a joint outside its range
     z = np.zeros(n)
     st = dict(q=q, qd=qd, targets=tg, box_pos=np.stack([z, z, z + 0.5 * float(sc.box_size)]), box_quat=np.stack([z, z, z, z + 1.0]),
               box_lin=np.zeros((3, n)), box_ang=np.zeros((3, n)))
-    return {k: _f32(v) for k, v in st.items()}
+    return {k: f32(v) for k, v in st.items()}
 
 
 @functools.lru_cache(maxsize=None)
