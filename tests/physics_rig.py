@@ -1,4 +1,5 @@
-"""What the physics parity tests share (test_gpu_parity, test_tumbled_box, test_wide_poses, test_physics_configs, test_model_structure):
+"""What the physics parity tests share (test_gpu_parity, test_tumbled_box, test_wide_poses, test_physics_configs, test_model_structure,
+test_contact_rich):
 configurations, the backends loaded with one state, snapshots, the references of the tumbled samples and the comparisons with their
 bounds.  A plain module: no fixtures, no torch at import (the HIP backend is imported where one is built).
 
@@ -6,7 +7,10 @@ Bounds.  Integers (list length, type, capsule, corner per slot) are exact over t
 fp32 oracle and the backend under test; at most LEFT_OUT of the envs may be left out.  Points and gaps: 2e-6 m.  Normals of hand / box
 entries: C_RULE E / dist + 1e-7 with E the largest err_n dist of the fp32 oracle against the fp64 oracle on the same sample.  States: the
 error against fp64 at the 99.9th percentile and at the maximum is at most C_RULE x the fp32 oracle's own error on the same entries, plus
-the floors 1e-7 and 1e-6 (accumulate / assert_c_rule).  A helper that takes a tolerance has no default for it: the tests state them."""
+the floors 1e-7 and 1e-6 (accumulate / assert_c_rule); the cached impulses of the warm-start slots enter as three more fields (box /
+ground slots that hold the same corner, hand slots and joint-limit slots valid in all three), and the set of valid hand and limit
+slots is exact.  An env that the two oracles alone decide differently (oracles_differ) is left out, within the same cap.  A helper
+that takes a tolerance has no default for it: the tests state them."""
 import contextlib
 import functools
 import math
@@ -178,17 +182,47 @@ def bg_cache(b):
 
 
 def snap(b, fields=FIELDS):
+    """The fields, the list lengths and the warm-start cache by groups of slots: box / ground (bg_cache), hand contacts (slots 0-79:
+    three impulses each) and joint-limit rows (slots 88 and above: one impulse each), with whether each slot's tag is valid for the
+    env's generation."""
     s = {f: b.get(f) for f in fields}
     s["ncontact"] = b.get("ncontact")[0].astype(int)
     s["lam"], s["corner"] = bg_cache(b)
+    lam, tag, gen = b.warm_cache()
+    valid = (tag >> 3) == gen[None, :]
+    s["hlam"], s["hvalid"] = lam[:240].copy(), valid[:80]
+    s["llam"], s["lvalid"] = lam[264::3].copy(), valid[88:]
     return s
 
 
+CACHE_GROUPS = (("wlam hand", "hlam", "hvalid", 3), ("wlam limit", "llam", "lvalid", 1))
+SNAP_EXTRAS = ("ncontact", "lam", "corner", "hlam", "hvalid", "llam", "lvalid")          # what snap() adds to the fields
+
+
 # ------------------------------------------------------------------------------------------------- references, computed once
+def oracles_differ(s64, s32, ms):
+    """(n,) the envs that the two oracles alone decide differently, by roundoff: another list length, another set of valid cache
+    slots, or a joint that ends the sub-step clamped on a stop in one and free in the other (its qd then differs by the whole
+    speed, not by roundoff).  Computed from the references only: such an env may be left out of a comparison, LEFT_OUT at the most."""
+    lo = np.array(np.ctypeslib.as_array(ms.lo), dtype=np.float64)[:, None]      # the float32 limits every side clamps at
+    hi = np.array(np.ctypeslib.as_array(ms.hi), dtype=np.float64)[:, None]
+    stop = ((s64["q"] <= lo) != (s32["q"] <= lo)) | ((s64["q"] >= hi) != (s32["q"] >= hi))
+    slots = (s64["hvalid"] != s32["hvalid"]).any(0) | (s64["lvalid"] != s32["lvalid"]).any(0)
+    return (s64["ncontact"] != s32["ncontact"]) | slots | stop.any(0)
+
+
+def left_by_the_references(recs):
+    """(n,) the envs that oracles_differ names in any record; the cap is asserted here, before anything under test is read."""
+    left = np.any([rec["left"] for rec in recs], axis=0)
+    assert left.mean() <= LEFT_OUT, f"the oracles alone leave out {left.sum()} of {left.size} envs"
+    return left
+
+
 def teacher_ref(sc, ms, start):
     """Three teacher-forced sub-steps on the fp64 and the fp32 oracle (fresh instances): after each, q, qd and the box state of both
     are put to the fp64 oracle's values rounded to float32, so that every sub-step starts from one state.  Per sub-step: the
-    float32 state it started from, both snapshots and (first sub-step) both contact lists."""
+    float32 state it started from, both snapshots, the envs the oracles decide differently (oracles_differ) and (first sub-step)
+    both contact lists."""
     from oracle.oracle import Oracle
     n = int(sc.num_envs)
     o64, o32 = Oracle(sc, ms, f64=True), Oracle(sc, ms)
@@ -197,6 +231,7 @@ def teacher_ref(sc, ms, start):
     for sub in range(3):
         o64.substep(last=True), o32.substep(last=True)
         rec = dict(start=start, s64=snap(o64), s32=snap(o32))
+        rec["left"] = oracles_differ(rec["s64"], rec["s32"], ms)
         if sub == 0:
             rec["lists64"], rec["lists32"] = lists(o64, n), lists(o32, n)
             _, rec["wtag64"], rec["wgen64"] = o64.warm_cache()
@@ -226,6 +261,20 @@ def tumbled_free_ref(kind, n, steps, fields=FIELDS, seed=SEED, **cfg):
         o64.physics_step(), o32.physics_step()
         out.append(dict(s64=snap(o64, fields), s32=snap(o32, fields)))
     return out
+
+
+def free_step_ref(sc, ms, start):
+    """One free-running physics step (sim.substeps sub-steps) from `start` on both oracles: the snapshots after it and `left`, the
+    envs that oracles_differ names after any of its sub-steps."""
+    from oracle.oracle import Oracle
+    o64, o32 = Oracle(sc, ms, f64=True), Oracle(sc, ms)
+    load(o64, start), load(o32, start)
+    left, subs = np.zeros(int(sc.num_envs), bool), int(sc.substeps)
+    for sub in range(subs):
+        o64.substep(last=sub == subs - 1), o32.substep(last=sub == subs - 1)
+        s64, s32 = snap(o64), snap(o32)
+        left |= oracles_differ(s64, s32, ms)
+    return dict(start=start, s64=s64, s32=s32, left=left)
 
 
 # ------------------------------------------------------------------------------------------------- comparisons: contact lists
@@ -258,19 +307,19 @@ def normal_scale(lists64, lists32, envs, sc, ms):
     return E
 
 
-def agree(same, *counts):
+def agree(same, *counts, exact=True):
     for a in counts[1:]:
         same = same & (counts[0] == a)
-    assert 1.0 - same.mean() <= LEFT_OUT, f"{(~same).sum()} of {same.size} envs left out"
+    assert not exact or 1.0 - same.mean() <= LEFT_OUT, f"{(~same).sum()} of {same.size} envs left out"
     return same
 
 
-def check_manifold(b, rec, sc, ms):
-    """The backend under test `b` has taken the first teacher-forced sub-step of a hand-on-box sample: its list of every env against
-    the fp64 oracle's."""
+def check_manifold(b, rec, sc, ms, keep=None):
+    """The backend under test `b` has taken the first teacher-forced sub-step of a hand-on-box sample: its list of every env (of the
+    envs `keep`) against the fp64 oracle's."""
     n = len(rec["lists64"])
     got = lists(b, n)
-    same = agree(np.ones(n, bool), rec["s64"]["ncontact"], rec["s32"]["ncontact"], np.array([len(c) for c in got]))
+    same = agree(np.ones(n, bool) if keep is None else keep, rec["s64"]["ncontact"], rec["s32"]["ncontact"], np.array([len(c) for c in got]))
     envs = np.nonzero(same)[0]
     _, corner = bg_cache(b)
     assert (corner[:, same] == rec["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
@@ -312,6 +361,22 @@ def accumulate_snap(report, s64, s32, sh, same, fields):
     # cached impulses of the box / ground slots that hold the same corner in all three
     ok = (s64["corner"] >= 0) & (s64["corner"] == s32["corner"]) & (s64["corner"] == sh["corner"]) & same
     accumulate(report, "wlam 80-83", s64["lam"], s32["lam"], sh["lam"], np.repeat(ok, 3, axis=0))
+    # ... and of the hand slots and the joint-limit slots that are valid in all three
+    for name, lam, valid, rows in CACHE_GROUPS:
+        ok = s64[valid] & s32[valid] & sh[valid] & same
+        accumulate(report, name, s64[lam], s32[lam], sh[lam], np.repeat(ok, rows, axis=0))
+
+
+def assert_same_slots(sh, s64, same):
+    """The snapshot under test holds valid hand and joint-limit cache slots exactly where the fp64 oracle's does, over the envs `same`."""
+    for _, _, valid, _ in CACHE_GROUPS:
+        bad = (sh[valid] != s64[valid]).any(0) & same
+        assert not bad.any(), f"{valid}: the set of valid cache slots differs in {bad.sum()} envs, first {np.nonzero(bad)[0][:8]}"
+
+
+def c_rule_factor(report):
+    """By what factor the report misses (> 1) or meets (<= 1) the rule: the largest error over its bound."""
+    return max(max(r[1] / (C_RULE * r[0] + 1e-7), r[3] / (C_RULE * r[2] + 1e-6)) for r in report.values())
 
 
 def assert_c_rule(report, label):
@@ -323,22 +388,30 @@ def assert_c_rule(report, label):
         assert r[3] <= C_RULE * r[2] + 1e-6, (f, r)
 
 
-def check_teacher_forced(make, recs, kind, label=""):
+def teacher_forced_report(make, recs, kind, exact=True):
     """The backend that make() returns through the teacher-forced sub-steps of the references `recs` (teacher_ref): contact counts
-    over the envs that agree, slot corners exact, states by the c rule."""
-    n = recs[0]["s64"]["ncontact"].size
+    over the envs that agree, slot corners and the sets of valid hand and limit slots exact; the report for the c rule.
+    exact = False skips the exact assertions on the output under test, for the margins of the stand-ins."""
+    same, report = ~left_by_the_references(recs), {}
     b = make()
-    same, report = np.ones(n, bool), {}
     for rec in recs:
         load(b, rec["start"])
         b.substep(last=True)
         sh = snap(b)
         if kind == "box_alone":
             assert sh["ncontact"].max() <= 4 and rec["s64"]["ncontact"].max() <= 4       # the early box solve really ran
-        same = agree(same, rec["s64"]["ncontact"], rec["s32"]["ncontact"], sh["ncontact"])   # (an env left out stays out: its cache differs)
-        assert (sh["corner"][:, same] == rec["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
+        same = agree(same, rec["s64"]["ncontact"], rec["s32"]["ncontact"], sh["ncontact"], exact=exact)   # (an env left out stays out: its cache differs)
+        assert not exact or (sh["corner"][:, same] == rec["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
+        if exact:
+            assert_same_slots(sh, rec["s64"], same)
         accumulate_snap(report, rec["s64"], rec["s32"], sh, same, FIELDS)
-    assert_c_rule(report, f"teacher-forced, {label}{kind}, n = {n}")
+    return report
+
+
+def check_teacher_forced(make, recs, kind, label=""):
+    """teacher_forced_report, then states and cached impulses by the c rule."""
+    report = teacher_forced_report(make, recs, kind)
+    assert_c_rule(report, f"teacher-forced, {label}{kind}, n = {recs[0]['s64']['ncontact'].size}")
     assert "wlam 80-83" in report
     return report
 

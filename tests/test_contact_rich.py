@@ -1,0 +1,321 @@
+"""The contact-rich paths of the contact solver on a MIXED sample (tests/contact_rich_states.py), by the c rule of tests/physics_rig.py.
+
+What the solver's hardest code exists for -- more work items than item lanes (sweeps in rounds), blocks that are pairs of contacts,
+lists cut at DEXSIM_KMAX, hand / box, hand / ground and box / ground rows coupled through one box, joint-limit rows behind a finger's
+contacts -- was held only to the fixed bounds of test_saturated_contact_list_matches_oracle and test_generic_sweep_variants_match_oracle
+(q 2e-4, qd 1e-2 + 5e-3 rel, cforce 0.5 N + 5 %), four to five orders above the fp32 oracle's own error, from a cold cache, on samples
+whose envs are all of one regime in full workgroups.  Here N = 134 (two full workgroups and one with six live lanes), env i of class
+i % 4 (hand clear / single-contact blocks / pairs / truncated lists), for the default configuration and with
+sim.dexsim_joint_limit_rows on, three teacher-forced sub-steps (the first from a cold cache, the next two warm) and one free physics
+step; the cached impulses of the hand slots and the limit slots are compared next to those of the box / ground slots, and the sets of
+valid slots are exact.
+
+Bounds: the rig's, unchanged.  The kernels' error against the fp64 oracle, at the 99.9th percentile and at the maximum, is at most
+C_RULE = 3 times the fp32 oracle's own error on the same entries, plus the floors 1e-7 and 1e-6; list lengths, slot corners and
+valid-slot sets exact over the envs that agree; points, gaps and friction of the lists 2e-6.  An env is left out only by a criterion
+computed from the two oracles alone (pr.oracles_differ: another list length, another valid-slot set, a joint clamped in one and free in
+the other), LEFT_OUT = 2 % at the most, asserted before anything under test is read.
+
+The CPU tests show that the sample covers the cases and that the comparison bites: the fp32 oracle itself passes, the fp32 oracle with
+one sweep fewer, with the hand slots cleared before the warm sub-steps, or with 1 % more hand friction is refused (factors in
+test_mutated_oracles_are_refused), the first two of which pass the former fixed bounds.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+from tests import contact_rich_states as cr
+from tests import physics_rig as pr
+
+N = cr.N
+CONFIGS = {"default": {}, "limit_rows": {"sim.dexsim_joint_limit_rows": True}}
+BOTH = pytest.mark.parametrize("config", list(CONFIGS))
+# both launch forms; the stand-alone k_dynamics + k_solve do not build joint-limit rows (dexsim_run_stage refuses the configuration)
+FORMS = pytest.mark.parametrize("fused,config", [(True, "default"), (False, "default"), (True, "limit_rows")],
+                                ids=["k_substep-default", "k_dynamics+k_solve-default", "k_substep-limit_rows"])
+
+
+def _setup(config, **more):
+    return pr.setup("BlindGrasping", N, **CONFIGS[config], **more)
+
+
+@functools.lru_cache(maxsize=None)
+def _teacher_ref(config):
+    sc, _, ms = _setup(config)
+    return pr.teacher_ref(sc, ms, cr.sample())
+
+
+@functools.lru_cache(maxsize=None)
+def _free_ref(config):
+    sc, _, ms = _setup(config)
+    return pr.free_step_ref(sc, ms, cr.sample())
+
+
+# ------------------------------------------------------------------------------------------------- the comparisons (GPU tests and stand-ins)
+def _teacher_report(make, config, exact=True):
+    return pr.teacher_forced_report(make, _teacher_ref(config), "contact_rich", exact)
+
+
+def _check_teacher(make, config):
+    """Three teacher-forced sub-steps, the first from a cold cache: list lengths, slot corners and valid-slot sets exact, all of
+    pr.FIELDS and the three groups of cached impulses by the c rule."""
+    report = pr.check_teacher_forced(make, _teacher_ref(config), "contact_rich", label=f"{config}, ")
+    assert "wlam hand" in report and ("wlam limit" in report) == (config == "limit_rows")
+    return report
+
+
+def _check_lists(make, config):
+    """The first sub-step's list of every env entry by entry, joint-limit rows included: type and capsule / joint level exact, points,
+    gaps and friction to 2e-6, box / ground slot corners exact; the normals as one more field of the c rule (pr.check_manifold's
+    E / dist bound takes an axis point outside the box: here fingers are pressed into it)."""
+    rec = _teacher_ref(config)[0]
+    keep = ~pr.left_by_the_references([rec])
+    b = make()
+    pr.load(b, rec["start"])
+    b.substep(last=True)
+    got = pr.lists(b, N)
+    keep = pr.agree(keep, rec["s64"]["ncontact"], np.array([len(c) for c in got]))
+    assert (pr.bg_cache(b)[1][:, keep] == rec["s64"]["corner"][:, keep]).all(), "a box / ground slot holds another corner"
+    for e in np.nonzero(keep)[0]:
+        assert pr.same_lists(rec["lists64"][e], got[e]), e
+    l64, l32, lh = (np.concatenate([l[e] for e in np.nonzero(keep)[0]]) for l in (rec["lists64"], rec["lists32"], got))
+    worst = np.abs(lh[:, [0, 1, 2, 6, 7]] - l64[:, [0, 1, 2, 6, 7]]).max()
+    print(f"\n{config}: {len(l64)} entries in {keep.sum()} envs, points / gaps / friction within {worst:.2e}")
+    np.testing.assert_allclose(lh[:, [0, 1, 2, 6, 7]], l64[:, [0, 1, 2, 6, 7]], rtol=0, atol=2e-6)
+    report = {}
+    pr.accumulate(report, "normals", l64[:, 3:6], l32[:, 3:6], lh[:, 3:6], np.ones((len(l64), 3), bool))
+    pr.assert_c_rule(report, f"lists, contact_rich, {config}, n = {N}")
+    assert len(l64) > 10 * N
+
+
+def _free_report(make, config, exact=True):
+    """One free-running physics step from the sample against both oracles: contact counts, slot corners and valid-slot sets where
+    the oracles agree; the report.  exact = False skips the exact assertions on the output under test, for the stand-ins' margins."""
+    ref = _free_ref(config)
+    assert ref["left"].mean() <= pr.LEFT_OUT, f"the oracles alone leave out {ref['left'].sum()} of {N} envs"
+    b = make()
+    pr.load(b, ref["start"])
+    b.physics_step()
+    sh = pr.snap(b)
+    same = pr.agree(~ref["left"], ref["s64"]["ncontact"], ref["s32"]["ncontact"], sh["ncontact"], exact=exact)
+    if exact:
+        assert (sh["corner"][:, same] == ref["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
+        pr.assert_same_slots(sh, ref["s64"], same)
+    report = {}
+    pr.accumulate_snap(report, ref["s64"], ref["s32"], sh, same, pr.FIELDS)
+    return report
+
+
+def _check_free(make, config):
+    report = _free_report(make, config)
+    pr.assert_c_rule(report, f"one physics step, contact_rich, {config}, n = {N}")
+    assert "wlam hand" in report and "wlam 80-83" in report
+    return report
+
+
+# ------------------------------------------------------------------------------------------------- CPU: the sample
+def _blocks(c):
+    """Solver blocks of one env's list: every hand entry (types 0, 1, 3) its own block, pairs beyond 12."""
+    nh = int((c[:, 8] != 2).sum())
+    return (nh + 1) // 2 if nh > 12 else nh
+
+
+@BOTH
+def test_sample_covers_the_cases(config):
+    """What the fp64 oracle makes of the sample (thresholds: the issue's coverage facts); both oracles agree within the cap over the
+    teacher-forced sub-steps and over the free step."""
+    recs = _teacher_ref(config)
+    lists = recs[0]["lists64"]
+    cls = np.arange(N) % 4
+    length = np.array([len(c) for c in lists])
+    hand = np.array([int(((c[:, 8] == 0) | (c[:, 8] == 1)).sum()) for c in lists])
+    blocks = np.array([_blocks(c) for c in lists])
+    per_wg = [int(blocks[w:w + 64].sum()) for w in range(0, N, 64)]
+    types = np.bincount(np.concatenate([c[:, 8] for c in lists]).astype(int), minlength=4)
+    left_t, left_f = pr.left_by_the_references(recs), _free_ref(config)["left"]
+    print(f"\n{config}: list length per class, min / mean / max: " + ", ".join(
+        f"{length[cls == k].min()} / {length[cls == k].mean():.1f} / {length[cls == k].max()}" for k in range(4)) +
+        f"; hand contacts > 12: class 2 {(hand[cls == 2] > 12).mean():.2f}, class 3 {(hand[cls == 3] > 12).mean():.2f}; blocks per workgroup "
+        f"{per_wg}; entries by type {types.tolist()}; left out by the oracles: teacher-forced {left_t.sum()}, free step {left_f.sum()}")
+    assert (hand[cls == 0] == 0).all() and (length[cls == 0] == 4).all()          # hand clear, the box on its four corners
+    assert (hand[cls == 1] <= 12).all() and 8 <= length[cls == 1].mean() <= 12    # single-contact blocks, lists of 8-12 on average
+    assert 13 <= length[cls == 2].min() and length[cls == 2].mean() < 24
+    assert (hand[cls == 2] > 12).mean() > 0.5 and (hand[cls == 3] > 12).all()     # pairs
+    assert (length[cls == 3] == 24).all()                                         # DEXSIM_KMAX: truncated
+    assert max(per_wg[:2]) > 384                                                  # a full workgroup deals its items in rounds
+    assert types[0] > 0 and types[1] > 0 and types[2] > 0 and (types[3] > 0) == (config == "limit_rows")
+    assert set(cls[128:]) == {0, 1, 2, 3} and per_wg[2] > 0                       # the padded workgroup holds every class
+    assert all(pr.same_lists(a, b) for a, b, l in zip(lists, recs[0]["lists32"], left_t) if not l)
+    assert left_t.mean() <= pr.LEFT_OUT and left_f.mean() <= pr.LEFT_OUT
+
+
+# ------------------------------------------------------------------------------------------------- CPU: the comparison bites
+class _Oracle32:
+    """The fp32 oracle in the kernels' place."""
+
+    def __init__(self, sc, ms):
+        from oracle.oracle import Oracle
+        self.o, self.subs, self.taken = Oracle(sc, ms), int(sc.substeps), 0
+
+    def __getattr__(self, name):
+        return getattr(self.o, name)
+
+    def substep(self, last=True):
+        self.o.substep(last=last)
+        self.taken += 1
+
+    def physics_step(self):
+        for sub in range(self.subs):
+            self.substep(last=sub == self.subs - 1)
+
+
+class _HandSlotsCleared(_Oracle32):
+    """... whose hand contacts start sub-steps 2 and 3 from zero impulses: their warm-start slots are cleared."""
+
+    def substep(self, last=True):
+        if self.taken in (1, 2):
+            lam = self.o.get("wlam")
+            lam[:240] = 0.0
+            self.o.set("wlam", lam)
+        super().substep(last)
+
+
+def _stand_ins(config):
+    sc, model, ms = _setup(config)
+    sc15, _, _ = _setup(config, **{"sim.physx.num_position_iterations": int(sc.num_position_iterations) - 1})
+    _, _, ms_mu = _setup(config, hand_friction=1.01 * float(model.hand_friction))
+    assert int(sc.num_position_iterations) == 16 and int(sc15.num_position_iterations) == 15
+    return dict(honest=lambda: _Oracle32(sc, ms), sweep=lambda: _Oracle32(sc15, ms), cleared=lambda: _HandSlotsCleared(sc, ms),
+                friction=lambda: _Oracle32(sc, ms_mu))
+
+
+@BOTH
+def test_fp32_oracle_in_the_kernels_place_passes(config):
+    make = _stand_ins(config)["honest"]
+    _check_teacher(make, config), _check_lists(make, config), _check_free(make, config)
+
+
+def _former_fixed_bounds(b, o):
+    """The bounds of test_saturated_contact_list_matches_oracle and test_generic_sweep_variants_match_oracle, `b` against `o`."""
+    np.testing.assert_allclose(b.get("q"), o.get("q"), atol=2e-4)
+    np.testing.assert_allclose(b.get("qd"), o.get("qd"), atol=1e-2, rtol=5e-3)
+    np.testing.assert_allclose(b.get("box_pos"), o.get("box_pos"), atol=2e-4)
+    np.testing.assert_allclose(b.get("cforce"), o.get("cforce"), atol=0.5, rtol=5e-2)
+
+
+@BOTH
+def test_mutated_oracles_are_refused(config):
+    """The fp32 oracle at 15 of 16 iterations, with the hand slots cleared before sub-steps 2 and 3, and with hand_friction x 1.01,
+    through the functions of the GPU tests.  Factors by which each misses the c rule (largest error over its bound; teacher-forced /
+    free step), N = 134, seed 7:
+                    default            limit_rows
+      sweep         1.05e3 / 1.05e3    5.03e3 / 7.12e3
+      cleared       1.39e4 / 3.91e3    6.94e4 / 1.01e5
+      friction      198 / 228          652 / 843
+    (the honest fp32 oracle: 0.333, as the rule has it).  The first two pass the former fixed bounds, on the state and through the steps of
+    test_saturated_contact_list_matches_oracle (at n = 134); the friction also fails the list comparison (mu is a column of the list)."""
+    from oracle.oracle import Oracle
+    stand = _stand_ins(config)
+    factors = {}
+    for name, make in stand.items():
+        factors[name] = (pr.c_rule_factor(_teacher_report(make, config, exact=False)), pr.c_rule_factor(_free_report(make, config, exact=False)))
+    print(f"\n{config}: factors over the c rule, teacher-forced / free step: " + ", ".join(f"{k} {a:.3g} / {b:.3g}" for k, (a, b) in factors.items()))
+    assert max(factors["honest"]) <= 1.0
+    for name in ("sweep", "cleared", "friction"):
+        assert factors[name][0] > 1.0, name
+        with pytest.raises(AssertionError):
+            _check_teacher(stand[name], config)
+    assert factors["sweep"][1] > 1.0 and factors["friction"][1] > 1.0
+    with pytest.raises(AssertionError):
+        _check_lists(stand["friction"], config)
+    # ... while the former fixed bounds let the first two through: test_saturated_contact_list_matches_oracle, its state and steps
+    sat = pr.lowered_hand_state(np.random.default_rng(2), N, z=-0.42, dz=0.02, rot=0.15)
+    sc, _, ms = _setup(config)
+    for name in ("sweep", "cleared"):
+        o, b = Oracle(sc, ms), stand[name]()
+        pr.load(o, sat), pr.load(b, sat)
+        o.substep(last=True), b.substep(last=True)
+        _former_fixed_bounds(b, o)
+        for _ in range(3):
+            o.physics_step(), b.physics_step()
+        worst = np.abs(b.get("q") - o.get("q")).max()
+        print(f"{name} on the saturated state: |dq| after three free physics steps {worst:.2e} (former bound 5e-3)")
+        assert worst < 5e-3
+
+
+class _OneSlotDropped(_Oracle32):
+    """... that forgets one hand contact of one env of the padded workgroup: its cache slot is not valid after the sub-step."""
+    ENV = 130
+
+    def substep(self, last=True):
+        super().substep(last)
+        _, tag, gen = self.o.warm_cache()
+        slot = int(np.nonzero(tag[:80, self.ENV] == 8 * gen[self.ENV])[0][0])
+        tag[slot, self.ENV] = -8
+        self.o.set("wtag", tag)
+
+
+def test_one_dropped_cache_slot_is_refused():
+    sc, _, ms = _setup("default")
+    with pytest.raises(AssertionError, match="hvalid: the set of valid cache slots differs in 1 envs"):
+        _teacher_report(lambda: _OneSlotDropped(sc, ms), "default")
+    with pytest.raises(AssertionError, match="hvalid: the set of valid cache slots differs in 1 envs"):
+        _free_report(lambda: _OneSlotDropped(sc, ms), "default")
+
+
+# ------------------------------------------------------------------------------------------------- GPU
+# Measured on one MI355X, ratios |HIP - fp64| / |fp32 oracle - fp64| at the 99.9th percentile / at the maximum (the fp32 oracle's own
+# figures: DESIGN.md, section 5); C_RULE allows 3.  No env left out, by the oracles or by the kernels:
+#              teacher-forced, default            teacher-forced, limit_rows   one physics step (k_physics4)
+#              k_substep    k_dynamics+k_solve    k_substep                    default      limit_rows
+#   q          0.45 / 0.69  0.45 / 0.67           0.48 / 0.69                  0.65 / 0.92  0.80 / 0.83
+#   qd         0.46 / 0.68  0.46 / 0.68           0.46 / 0.68                  0.86 / 0.88  0.83 / 0.79
+#   box_pos    0.98 / 0.99  0.97 / 0.97           0.98 / 0.98                  0.75 / 0.84  0.76 / 0.78
+#   box_quat   0.40 / 0.39  0.39 / 0.39           0.39 / 0.38                  0.67 / 0.84  0.81 / 0.78
+#   box_lin    0.98 / 0.99  0.97 / 0.96           0.98 / 0.98                  0.93 / 0.94  0.86 / 0.88
+#   box_ang    0.40 / 0.38  0.39 / 0.38           0.39 / 0.38                  0.83 / 0.84  0.78 / 0.78
+#   cforce     0.55 / 0.61  0.55 / 0.61           0.56 / 0.61                  0.75 / 0.87  0.79 / 0.81
+#   wlam 80-83 0.46 / 0.38  0.44 / 0.38           0.37 / 0.39                  0.88 / 0.85  0.84 / 0.79
+#   wlam hand  0.59 / 0.59  0.59 / 0.59           0.58 / 0.59                  0.88 / 0.86  0.80 / 0.81
+#   wlam limit                                    0.65 / 0.64                               0.50 / 0.46
+#   normals    0.93 / 0.78  0.94 / 0.78           0.82 / 0.78                  (test_contact_lists_of_the_mixed_sample; points, gaps and
+#                                                                              friction within 4.4e-8 of the fp64 oracle's)
+@pytest.mark.gpu
+@FORMS
+def test_teacher_forced_substeps_on_the_mixed_sample(fused, config):
+    sc, _, ms = _setup(config)
+    _check_teacher(lambda: pr.hip(sc, ms, fused), config)
+
+
+@pytest.mark.gpu
+@FORMS
+def test_contact_lists_of_the_mixed_sample(fused, config):
+    sc, _, ms = _setup(config)
+    _check_lists(lambda: pr.hip(sc, ms, fused), config)
+
+
+@pytest.mark.gpu
+@BOTH
+def test_free_physics_step_on_the_mixed_sample(config):
+    """One physics step of four sub-steps by k_physics4 against both oracles; and the step equals four single sub-step launches bit
+    for bit, warm-start cache included."""
+    import torch
+    from dexrobot_isaac_amd import _abi
+    sc, _, ms = _setup(config)
+    made = []
+
+    def make():
+        made.append(pr.hip(sc, ms))
+        return made[-1]
+    _check_free(make, config)
+    a, b = made[0], pr.hip(sc, ms)
+    pr.load(b, cr.sample())
+    for _ in range(4):
+        b.core.run_stage(_abi.STAGE["SUBSTEP"])
+    torch.cuda.synchronize()
+    assert int(a.core.field("ncontact").max()) == _abi.KMAX
+    for f in pr.SYNC + ("cforce", "site_pose", "ncontact"):
+        assert torch.equal(a.core.field(f), b.core.field(f)), f
+    for x, y in zip(a.warm_cache(), b.warm_cache()):                    # impulses, tags and generation of every slot and env
+        assert np.array_equal(x, y)

@@ -150,6 +150,7 @@ def test_sample_conditions(name):
         assert all(pr.same_lists(a, b) for a, b in zip(recs[0]["lists64"], recs[0]["lists32"])), kind
         for rec in recs:
             assert (rec["s64"]["ncontact"] == rec["s32"]["ncontact"]).all() and (rec["s64"]["corner"] == rec["s32"]["corner"]).all(), kind
+            assert not rec["left"].any(), kind                             # (pr.oracles_differ: valid cache slots and joint stops too)
         if kind != "hand_on_box":
             ref = _physics_ref(name, kind, N)
             assert (ref["s64"]["ncontact"] == ref["s32"]["ncontact"]).all() and (ref["s64"]["corner"] == ref["s32"]["corner"]).all(), kind

@@ -95,6 +95,7 @@ def test_both_oracles_list_the_same_contacts():
         assert all(pr.same_lists(a, b) for a, b in zip(recs[0]["lists64"], recs[0]["lists32"])), kind
         for rec in recs:
             assert (rec["s64"]["ncontact"] == rec["s32"]["ncontact"]).all() and (rec["s64"]["corner"] == rec["s32"]["corner"]).all(), kind
+            assert not rec["left"].any(), kind                             # ... nor for valid cache slots or joints on their stops
     for rec in _free_ref(N):
         assert (rec["s64"]["ncontact"] == rec["s32"]["ncontact"]).all() and (rec["s64"]["corner"] == rec["s32"]["corner"]).all()
     # ... and the fp32 oracle is inside the fixed bound on points and gaps, which its normals are not (module docstring)

@@ -139,7 +139,7 @@ def _accumulate_rec(report, s64, s32, sh, amb, left):
     """pr.accumulate per field over the envs not in `left`; qd without the ambiguous joints."""
     keep = ~left
     for f in s64:
-        if f in ("ncontact", "corner", "lam"):
+        if f in pr.SNAP_EXTRAS:
             continue
         mask = np.broadcast_to(keep, s64[f].shape)
         pr.accumulate(report, f, s64[f], s32[f], sh[f], mask & ~amb if f == "qd" else mask)
