@@ -127,6 +127,7 @@ class DexSimCamera(C.Structure):
 IK_MAX_ITERS = 64   # DEXSIM_IK_MAX_ITERS
 NPROX_GROUPS, NPROX_PAIRS = 15, 120   # DEXSIM_NPROX_GROUPS, DEXSIM_NPROX_PAIRS: the pair table of dexsim_query_proximity
 ID_GRAVITY = 1   # DEXSIM_ID_GRAVITY: dexsim_inverse_dynamics includes the gravity force
+FK_HAND_FRAME = 1   # DEXSIM_FK_HAND_FRAME: dexsim_forward_kinematics gives the site poses relative to site 0
 FD_GRAVITY, FD_ARMATURE = 1, 2   # DEXSIM_FD_GRAVITY, DEXSIM_FD_ARMATURE: flags of dexsim_forward_dynamics / dexsim_mass_solve
 MSOLVE_MAX_RHS = 32   # DEXSIM_MSOLVE_MAX_RHS
 
@@ -193,11 +194,17 @@ PROTOTYPES = {
     "dexsim_last_error": [],
 }
 EXPORTED_SYMBOLS = list(PROTOTYPES)
+# the entry point include/dexsim_fk.h declares, the part of the header that dexsim.h includes (tests/test_forward_kinematics.py holds
+# this table against that file and the built library as tests/test_abi.py holds the one above against dexsim.h)
+FK_PROTOTYPES = {
+    "dexsim_forward_kinematics": [vp, vp, i32, vp, vp, P(i32), i32, i32, vp, vp, vp, vp],
+}
+ALL_PROTOTYPES = {**PROTOTYPES, **FK_PROTOTYPES}   # every entry point of the library: what the loader checks and declares
 
 
 def declare_prototypes(lib):
-    """Attach argtypes/restype for every entry point of include/dexsim.h to a loaded CDLL."""
-    for name, argtypes in PROTOTYPES.items():
+    """Attach argtypes/restype for every entry point of include/dexsim.h and include/dexsim_fk.h to a loaded CDLL."""
+    for name, argtypes in ALL_PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, i32
     lib.dexsim_error_string.restype = C.c_char_p

@@ -22,7 +22,7 @@ def load():
                 f"{LIB_PATH} not found. Build it with `python -m dexrobot_isaac_amd.build` "
                 "(hipcc --offload-arch=gfx950); there is no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for sym in _abi.EXPORTED_SYMBOLS:
+        for sym in _abi.ALL_PROTOTYPES:
             if not hasattr(lib, sym):
                 raise DexSimError(f"libdexsim.so does not export {sym}")
         _abi.declare_prototypes(lib)

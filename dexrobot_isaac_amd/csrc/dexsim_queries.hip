@@ -1,6 +1,6 @@
 // dexsim_queries.hip -- libdexsim's query unit: the C-ABI (include/dexsim.h) of the queries on a simulation's state -- camera
-// sensors, Jacobians and mass matrix, inverse kinematics, clearances, inverse and forward dynamics and their derivatives -- over
-// their gfx950 kernels (dexsim_chain, _render, _kindyn, _ik, _proximity, _invdyn, _fwddyn, _dynderiv).
+// sensors, Jacobians and mass matrix, inverse kinematics, clearances, inverse dynamics, forward kinematics, forward dynamics and the
+// dynamics derivatives -- over their gfx950 kernels (dexsim_chain, _render, _kindyn, _ik, _proximity, _invdyn, _fk, _fwddyn, _dynderiv).
 //
 // The library's second translation unit (build: see dexsim.hip).  It includes none of the step unit's .hip.inc files and the step
 // unit none of these; from the step side it takes the declarations of dexsim_device.h and the handle of dexsim_host.h, nothing
@@ -257,6 +257,21 @@ static int kin_rows_qd(const char* who, dexsim_t h, const int64_t* env_ids, int 
   return DEXSIM_OK;
 }
 
+// The `n` requested bodies bodies[first + i] (NULL: body first + i) sorted by the frame they ride on -- -1 (the spawn frame), then
+// the joints in order -- from entry `at` on: body[] and slot[] (i, the position in the request) per entry, one range per frame in
+// jstart[0 .. DEXSIM_NJ + 1], so that a wave visits its own bodies only.  Returns the end of the entries.
+static int kin_sort_by_frame(const int* bodies, int first, int n, int at, unsigned char* body, unsigned char* slot, unsigned char* jstart) {
+  for (int j = -1; j < DEXSIM_NJ; j++) {
+    jstart[j + 1] = (unsigned char)at;
+    for (int i = 0; i < n; i++) {
+      const int b = bodies ? bodies[first + i] : first + i;
+      if (kd_body_joint(b) == j) { body[at] = (unsigned char)b; slot[at] = (unsigned char)i; at++; }
+    }
+  }
+  jstart[DEXSIM_NJ + 1] = (unsigned char)at;
+  return at;
+}
+
 extern "C" int dexsim_inverse_dynamics(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const float* qdd,
                                        int flags, float* tau, void* stream) {
   InvDyn K;
@@ -279,18 +294,40 @@ extern "C" int dexsim_body_bias_accel(dexsim_t h, const int64_t* env_ids, int k,
   if (rc) return rc;
   rc = kin_bodies("dexsim_body_bias_accel", h, bodies, nb, nullptr, "acc", acc, 4);
   if (rc) return rc;
-  int n = 0;   // the request sorted by the frame a body rides on: -1 (the spawn frame), then the joints in order
-  for (int j = -1; j < DEXSIM_NJ; j++) {
-    K.jstart[j + 1] = (unsigned char)n;
-    for (int i = 0; i < nb; i++) {
-      const int b = bodies ? bodies[i] : i;
-      if (kd_body_joint(b) == j) { K.body[n] = (unsigned char)b; K.slot[n] = (unsigned char)i; n++; }
-    }
-  }
-  K.jstart[DEXSIM_NJ + 1] = (unsigned char)n;
+  kin_sort_by_frame(bodies, 0, nb, 0, K.body, K.slot, K.jstart);
   NEED_BOUND(h);
   K.qd = qd; K.acc = acc; K.nb = nb;
   KIN_LAUNCH(k_kin_bias_accel, 1, K);
+  return DEXSIM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- forward kinematics
+// Behind the inverse dynamics: the kernel uses its velocity walk.
+// clang-format off
+#include "dexsim_fk.hip.inc"
+// clang-format on
+
+extern "C" int dexsim_forward_kinematics(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const int* bodies,
+                                         int nb, int flags, float* body_states, float* site_poses, float* centroid, void* stream) {
+  FwdKin K;
+  std::memset(&K, 0, sizeof K);
+  int rc = kin_rows("dexsim_forward_kinematics", h, env_ids, k, q, &K.rows);
+  if (rc) return rc;
+  if (qd && !q) return fail(DEXSIM_ERR_ARG, "dexsim_forward_kinematics: a qd override needs a q override (the state path takes the envs' qd)");
+  if ((flags & ~DEXSIM_FK_HAND_FRAME) != 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_forward_kinematics: unknown flag bits (DEXSIM_FK_HAND_FRAME is the only flag)");
+  if (!body_states && !site_poses && !centroid)
+    return fail(DEXSIM_ERR_ARG, "dexsim_forward_kinematics: at least one of body_states, site_poses and centroid is required");
+  if (body_states && (rc = kin_bodies("dexsim_forward_kinematics", h, bodies, nb, nullptr, "body_states", body_states, 4))) return rc;
+  if (((uintptr_t)site_poses & 3) != 0 || ((uintptr_t)centroid & 15) != 0)
+    return fail(DEXSIM_ERR_ARG, "dexsim_forward_kinematics: site_poses must be 4-byte aligned, centroid 16-byte aligned");
+  NEED_BOUND(h);
+  K.qd = qd; K.body_states = body_states; K.site_poses = site_poses; K.centroid = centroid;
+  K.nb = body_states ? nb : 0; K.nby = (K.nb + FK_CHUNK - 1) / FK_CHUNK;
+  K.vel = !q || qd; K.hand_frame = flags & DEXSIM_FK_HAND_FRAME;
+  for (int c = 0, at = 0; c < K.nby; c++)   // every chunk of the request sorted on its own
+    at = kin_sort_by_frame(bodies, c * FK_CHUNK, std::min(FK_CHUNK, K.nb - c * FK_CHUNK), at, K.body, K.slot, K.jstart[c]);
+  KIN_LAUNCH(k_kin_fk, K.nby + (site_poses || centroid ? 1 : 0), K);
   return DEXSIM_OK;
 }
 

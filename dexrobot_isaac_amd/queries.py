@@ -1,11 +1,12 @@
 """The query surface: everything that reads or copies simulation state outside the control step -- state records (save, load,
-fork), camera sensors, Jacobians and mass matrix, inverse and forward dynamics and their derivatives, fingertip IK, clearances.
+fork), camera sensors, Jacobians and mass matrix, inverse dynamics, forward kinematics, forward dynamics and the dynamics
+derivatives, fingertip IK, clearances.
 
 Two levels, in the same family order.  CoreQueries, a base class of DexSimCore, is the ctypes level: one C-ABI call per method
 on caller-owned device tensors, DexSimError on a bad argument.  EnvQueries, a base class of DexHandEnv, is the user level: it
 accepts lists, names and arrays, allocates the outputs and raises ValueError.  The argument rules that every call repeats are
 written once, at the top of this file and at the top of each class.  A new query adds a method to each class (and its row to
-_abi.PROTOTYPES); nothing else."""
+_abi.PROTOTYPES, or to _abi.FK_PROTOTYPES for include/dexsim_fk.h); nothing else."""
 import ctypes as C
 import hashlib
 
@@ -244,6 +245,30 @@ class CoreQueries:
         op = self._req("body_bias_accel", "out", out, (k, nb, 6))
         self._keep_kin = self._keep_kin + (qd,)
         check(self.lib.dexsim_body_bias_accel(self.h, ids, k, qp, vp, bp, nb, op, self._stream()), "body_bias_accel")
+
+    # ------------------------------------------------------------------ forward kinematics
+    def forward_kinematics(self, body_states=None, site_poses=None, centroid=None, env_ids=None, q=None, qd=None, bodies=None,
+                           hand_frame=False):
+        """The configuration in one launch: `body_states` (k, nb, 13) f32 = rows of rigid_body_states for the hand bodies `bodies`
+        (None = all 37); `site_poses` (k, 11, 7) f32 = position and quaternion xyzw of right_hand_base, the five tips and the five
+        pads, in the world frame or, with hand_frame=True, relative to right_hand_base; `centroid` (k, 8) f32 = centre of mass,
+        potential energy, velocity of the centre of mass, kinetic energy.  Any of the three may be None, not all.  Rows as for
+        body_jacobian; with a `q` override `qd` is an optional (k, 26) override, None = every velocity word is +0.0; without `q`
+        the velocities are the envs' and `qd` must be None.  dexsim_forward_kinematics."""
+        what = "forward_kinematics"
+        if body_states is None and site_poses is None and centroid is None:
+            raise DexSimError(f"{what}: at least one of body_states, site_poses and centroid is required")
+        if qd is not None and q is None:
+            raise DexSimError(f"{what}: a qd override needs a q override (without q the velocities are the envs')")
+        ids, qp, k = self._kin_rows(what, env_ids, q)
+        vp = self._opt(what, "qd", qd, (k, _abi.NJ))
+        nb, bp = (0, None) if body_states is None else self._kin_bodies(what, bodies)
+        op = self._opt(what, "body_states", body_states, (k, nb, 13))
+        sp = self._opt(what, "site_poses", site_poses, (k, _abi.NSITE, 7))
+        cp = self._opt(what, "centroid", centroid, (k, 8))
+        self._keep_kin = self._keep_kin + (qd,)
+        check(self.lib.dexsim_forward_kinematics(self.h, ids, k, qp, vp, bp, nb, _abi.FK_HAND_FRAME if hand_frame else 0, op, sp, cp,
+                                                 self._stream()), what)
 
     # ------------------------------------------------------------------ forward dynamics, mass-matrix solves
     def forward_dynamics(self, out, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False):
@@ -683,6 +708,64 @@ class EnvQueries:
         out = self._kindyn_out("get_body_bias_acceleration", out, (k, nb, 6), core.device)
         core.body_bias_accel(out, env_ids=ids, q=q, qd=qd, bodies=idx)
         return out
+
+    # ------------------------------------------------------------------ forward kinematics
+    SITE_SELECTIONS = {"all": slice(0, _abi.NSITE), "base": slice(0, 1), "tips": slice(1, 1 + _abi.NFINGER),
+                       "pads": slice(1 + _abi.NFINGER, _abi.NSITE)}
+
+    def _fk_rows(self, what, env_ids, q, qd=None):
+        """_kindyn_rows for the forward kinematics: a `qd` override is optional with a `q` override and an error without one."""
+        if qd is not None and q is None:
+            raise ValueError(f"{what}: a qd override needs a q override (without q the velocities are the envs' own)")
+        core, ids, q, k = self._kindyn_rows(what, "forward_kinematics", env_ids, q)
+        return core, ids, q, self._kindyn_vel(what, "qd", qd, k, core.device), k
+
+    def _fk_out(self, what, out, shape, core, ids):
+        given = out
+        out = self._kindyn_out(what, out, shape, core.device)
+        if given is None and ids is not None:   # a row whose id is out of range is left as it is by the kernel: give it a defined value
+            out.fill_(float("nan"))
+        return out
+
+    def get_body_states(self, bodies=None, env_ids=None, q=None, qd=None, out=None):
+        """gym.refresh_rigid_body_state_tensor on a row and body selection: (k, nb, 13) rows of rigid_body_states -- position of
+        the body-frame origin, quaternion xyzw, world linear and angular velocity -- of the hand bodies `bodies` (as for
+        get_jacobian: indices or names, None = all 37 in order).  Rows: the envs `env_ids` (None = all) at their dof_pos / dof_vel,
+        or the rows of a (k, 26) joint-position override `q` (env_ids is then ignored) with the optional (k, 26) velocity override
+        `qd`; without `qd` the velocity words of an override are exactly zero."""
+        what = "get_body_states"
+        core, ids, q, qd, k = self._fk_rows(what, env_ids, q, qd)
+        idx, nb = self._kindyn_bodies(what, bodies)
+        out = self._fk_out(what, out, (k, nb, 13), core, ids)
+        core.forward_kinematics(body_states=out, env_ids=ids, q=q, qd=qd, bodies=idx)
+        return out
+
+    def get_site_poses(self, sites="all", frame="world", env_ids=None, q=None, out=None):
+        """(k, ns, 7) poses (position, quaternion xyzw) of the hand's sites: sites="all" (11: right_hand_base, five tips, five
+        pads), "base" (1), "tips" (5) or "pads" (5), thumb to pinky.  frame="world": the env's world frame, as
+        obs_dict["fingertip_poses_world"]; frame="hand": relative to right_hand_base, as fingertip_poses_hand /
+        fingerpad_poses_hand.  Rows as for get_jacobian.  All 11 are computed into one (k, 11, 7) tensor -- `out`, when given --
+        and the selection is a slice of it."""
+        what = "get_site_poses"
+        if sites not in self.SITE_SELECTIONS:
+            raise ValueError(f"{what}: sites must be one of {sorted(self.SITE_SELECTIONS)}, got {sites!r}")
+        if frame not in ("world", "hand"):
+            raise ValueError(f"{what}: frame must be 'world' or 'hand', got {frame!r}")
+        core, ids, q, _, k = self._fk_rows(what, env_ids, q)
+        out = self._fk_out(what, out, (k, _abi.NSITE, 7), core, ids)
+        core.forward_kinematics(site_poses=out, env_ids=ids, q=q, hand_frame=frame == "hand")
+        return out[:, self.SITE_SELECTIONS[sites]]
+
+    def get_centroid(self, env_ids=None, q=None, qd=None, out=None):
+        """The hand as one body: a dict of views of one (k, 8) tensor (`out`, when given) -- "com" (k, 3) centre of mass in the
+        world frame, "com_vel" (k, 3) its velocity, "kinetic" (k,) = 1/2 qd^T M(q) qd with the M of get_mass_matrix, "potential"
+        (k,) = -M_tot g . com (zero at the env's world origin) -- plus "data", the tensor itself.  Rows and overrides as for
+        get_body_states; without velocities com_vel and kinetic are exactly zero."""
+        what = "get_centroid"
+        core, ids, q, qd, k = self._fk_rows(what, env_ids, q, qd)
+        out = self._fk_out(what, out, (k, 8), core, ids)
+        core.forward_kinematics(centroid=out, env_ids=ids, q=q, qd=qd)
+        return {"com": out[:, 0:3], "potential": out[:, 3], "com_vel": out[:, 4:7], "kinetic": out[:, 7], "data": out}
 
     # ------------------------------------------------------------------ forward dynamics, mass-matrix solves
     def get_forward_dynamics(self, tau=None, env_ids=None, q=None, qd=None, gravity=True, armature=False, out=None):

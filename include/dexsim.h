@@ -769,6 +769,11 @@ int dexsim_inverse_dynamics(dexsim_t h, const int64_t* env_ids, int k, const flo
 int dexsim_body_bias_accel(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* qd, const int* bodies, int nb,
                            float* acc, void* stream);
 
+/* ------------------------------------------------------------------ forward kinematics: body states, site poses, centroid
+ * The configuration the queries above and below describe, for the same rows and overrides: the entry point and DEXSIM_FK_HAND_FRAME
+ * are declared and documented in dexsim_fk.h, which is part of this header. */
+#include "dexsim_fk.h"
+
 /* ------------------------------------------------------------------ forward dynamics and mass-matrix solves
  * The inverse direction of the family: which joint acceleration a generalized force produces at (q, qd), and M(q)^-1 applied to
  * caller vectors without forming M -- what a planner that rolls candidate torques forward, an operational-space controller
