@@ -129,6 +129,12 @@ static int validate_model(const DexHandModel& m) {
     if (m.jtype[j] != (j < 3 ? 0 : 1)) return fail(DEXSIM_ERR_ARG, "model: kernels assume joints 0-2 prismatic, 3-25 revolute");
   for (int j = 0; j < 5; j++)
     if (m.mass[j] != 0.f) return fail(DEXSIM_ERR_ARG, "model: base-chain links 0-4 must be massless (palm rides on joint 5)");
+  for (int j = 0; j < 5; j++) {   // the kernels and the oracle take the base's inertial data from link 5 alone
+    for (int i = 0; i < 6; i++)
+      if (m.inertia[j][i] != 0.f) return fail(DEXSIM_ERR_ARG, "model: base-chain links 0-4 must have zero inertia (palm rides on joint 5)");
+    for (int i = 0; i < 3; i++)
+      if (m.com[j][i] != 0.f) return fail(DEXSIM_ERR_ARG, "model: base-chain links 0-4 must have a zero centre of mass (palm rides on joint 5)");
+  }
   for (int j = 5; j < DEXSIM_NJ; j++)
     if (!(m.mass[j] > 0.f)) return fail(DEXSIM_ERR_ARG, "model: palm and finger links need positive mass");
   for (int c = 0; c < DEXSIM_NCAP; c++) {

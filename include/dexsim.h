@@ -161,7 +161,7 @@ typedef struct DexHandModel {
   float jqoff[DEXSIM_NJ][4];        /* xyzw */
   float jpoff[DEXSIM_NJ][3];
   float jaxis[DEXSIM_NJ][3];        /* unit, in the joint's own frame */
-  float mass[DEXSIM_NJ];            /* body carried by joint j */
+  float mass[DEXSIM_NJ];            /* body carried by joint j; links 0-4 carry none: mass, com and inertia must be 0 there */
   float com[DEXSIM_NJ][3];          /* in joint frame */
   float inertia[DEXSIM_NJ][6];      /* about COM, joint-frame axes: xx yy zz xy xz yz */
   float kp[DEXSIM_NJ], kd[DEXSIM_NJ], armature[DEXSIM_NJ], lo[DEXSIM_NJ], hi[DEXSIM_NJ];

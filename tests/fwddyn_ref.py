@@ -51,9 +51,16 @@ def regular_poses(hk, n, seed, min_cos=0.1):
     Euler angles on massless links, so at q4 = +-pi/2 (joints 3 and 5 coaxial) M is exactly singular and the acceleration is not
     defined; the condition number of the d-scaled M grows like 10 / cos^2 q4 (1.8e9 at |q4 - pi/2| = 2e-4, at most 1.2e3 over 2000
     draws with |cos q4| >= 0.1, about 93 % of them), and with it the roundoff of ANY fp32 solve, so that 4 x the fp32 reference's
-    figure stops being a bound there.  The residual E_res is not affected."""
+    figure stops being a bound there.  The residual E_res is not affected.
+    Stated for any model: M is singular where the world axes of the hinges 3, 4, 5 are linearly dependent, and |det [a3 a4 a5]| is
+    |cos q4| on the default model (axes e_x, e_y, e_z on coincident frames); a model with tilted axes has its lock elsewhere."""
     q = hk.random_poses(2 * n + 20, seed)
-    q = q[np.abs(np.cos(q[:, 4].astype(np.float64))) >= min_cos]
+    g = hk.geom
+    det = np.zeros(len(q))
+    for i, x in enumerate(q.astype(np.float64)):
+        R = g.fk(x)[1]
+        det[i] = abs(np.linalg.det(np.stack([R[j] @ (g.jaxis[j] / np.linalg.norm(g.jaxis[j])) for j in (3, 4, 5)])))
+    q = q[det >= min_cos]
     assert len(q) >= n
     return q[:n]
 
@@ -79,22 +86,6 @@ def err_qdd(x, x64, M64):
 def err_res(x, tau, M64, b64):
     """E_res: the residual M64 x + b64 against tau in invdyn_ref.err_tau's metric."""
     return ir.err_tau(np.einsum("nij,nj->ni", M64, np.asarray(x, dtype=np.float64)) + b64, np.asarray(tau, dtype=np.float64), M64)
-
-
-def scaled_model(ms, seed=8):
-    """test_inverse_dynamics.py::test_different_model's model: per-joint scaled offsets, centres of mass and masses, finger links
-    with off-diagonal inertia.  Changes `ms` in place."""
-    rng = np.random.default_rng(seed)
-    for j in range(NJ):
-        fp, fc, fm = rng.uniform(0.7, 1.4, 3)
-        for i in range(3):
-            ms.jpoff[j][i] *= fp
-            ms.com[j][i] *= fc
-        ms.mass[j] *= fm
-        if j >= 6:
-            a, b, d = ms.inertia[j][0], ms.inertia[j][1], ms.inertia[j][2]
-            ms.inertia[j][3], ms.inertia[j][4], ms.inertia[j][5] = 0.3 * (a * b) ** 0.5, -0.2 * (a * d) ** 0.5, 0.25 * (b * d) ** 0.5
-    return ms
 
 
 def set_armature(ms, orc64, q_mid, seed=9):

@@ -20,6 +20,7 @@ import numpy as np
 
 from dexrobot_isaac_amd.config import build_sim_config, default_cfg
 from dexrobot_isaac_amd.hand_model import HandModel, rot_z
+from tests import generic_model
 from tests import tumbled_states as ts
 from tests.tumbled_states import f32
 
@@ -84,14 +85,31 @@ _ROT = (math.sin(0.05) / math.sqrt(2.0), math.sin(0.05) / math.sqrt(2.0), 0.0, m
 MODELS = {
     "poff4": (_break_poff4, None), "axis": (_break_axis, None), "qoff": (_break_qoff, None), "com": (_break_com, None),
     "hand_rot": (None, _ROT), "all": (_break_all, _ROT), "mixed": (_mixed, None),
+    # none of the default model's zeros, ones and repeated numbers, by tenths of a radian and a centimetre (it turns the spawn frame itself)
+    "generic": (generic_model.generic, None),
 }
+
+
+def _model_edit(name):
+    """(edit, rot) of a name of MODELS, or of "generic:<property>": the generic model with that property of generic_model.RESTORE put
+    back to the default model's value (the bite test of tests/test_generic_model.py)."""
+    if name in MODELS:
+        return MODELS[name]
+    base, prop = name.split(":", 1)
+    assert base == "generic"
+
+    def edit(m):
+        generic_model.generic(m)
+        if generic_model.RESTORE[prop] is not None:
+            generic_model.RESTORE[prop](m)
+    return edit, None
 
 
 # ------------------------------------------------------------------------------------------------- configuration
 @functools.lru_cache(maxsize=None)
 def setup(task, n, model=None, ground_friction=None, hand_friction=None, **over):
     """(sc, model, ms) of n envs, built once per process.  `over`: dotted keys into default_cfg(task), list indices included
-    ("sim.gravity.0"); `model`: a name of MODELS; ground_friction (hard-wired in config.py) and hand_friction (fixed by the MJCF-less
+    ("sim.gravity.0"); `model`: a name of MODELS or "generic:<property>" (_model_edit); ground_friction (hard-wired in config.py) and hand_friction (fixed by the MJCF-less
     model) are set on the built DexSimConfig / HandModel before to_struct()."""
     cfg = default_cfg(task)
     cfg["env"]["numEnvs"] = n
@@ -102,7 +120,7 @@ def setup(task, n, model=None, ground_friction=None, hand_friction=None, **over)
         d[int(parts[-1]) if isinstance(d, list) else parts[-1]] = value
     hand = None
     if model is not None:
-        edit, rot = MODELS[model]
+        edit, rot = _model_edit(model)
         if rot is not None:
             cfg["env"]["initialHandRot"] = list(rot)
         hand = HandModel(cfg["env"]["initialHandPos"], cfg["env"]["initialHandRot"])

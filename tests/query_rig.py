@@ -34,11 +34,49 @@ def stub_core(record, **methods):
     return factory
 
 
-def setup(n, task="BlindGrasping"):
+def setup(n, task="BlindGrasping", model=None, free_bodies=False, restore=None):
+    """(sc, ms) of n envs, the struct a fresh one for the caller to edit.  model: None for the default hand, "scaled" for
+    scaled_model on it, "generic" for the model of tests/generic_model.py, with its free_body_frames if free_bodies and with the
+    property `restore` (a name of generic_properties()) put back to the default model's value."""
+    if model == "generic":
+        from tests import generic_model
+        sc, _, ms = generic_model.build(n, task, free_bodies=free_bodies, restore=restore)
+        return sc, ms
+    assert model in (None, "scaled") and not free_bodies and restore is None
     cfg = default_cfg(task)
     cfg["env"]["numEnvs"] = n
-    sc, model = build_sim_config(cfg)
-    return sc, model.to_struct()
+    sc, hand = build_sim_config(cfg)
+    ms = hand.to_struct()
+    return sc, scaled_model(ms) if model == "scaled" else ms
+
+
+def generic_hand():
+    """The HandModel of tests/generic_model.py, a copy of the caller's own: make_env(..., hand_model=generic_hand())."""
+    from tests import generic_model
+    return generic_model.build(1)[1]
+
+
+def generic_properties():
+    """The names of the structural properties the generic model lacks (tests/generic_model.py::RESTORE)."""
+    from tests import generic_model
+    return list(generic_model.RESTORE)
+
+
+def scaled_model(ms, seed=8):
+    """The suites' second model: per-joint scaled offsets, centres of mass and masses, finger links with off-diagonal inertia --
+    no constant of the default model is baked in, and the diagonal-inertia shortcut of the step path is not taken.  It keeps every
+    zero of the default model a zero; the model without them is tests/generic_model.py.  Changes `ms` in place and returns it."""
+    rng = np.random.default_rng(seed)
+    for j in range(len(ms.mass)):
+        fp, fc, fm = rng.uniform(0.7, 1.4, 3)
+        for i in range(3):
+            ms.jpoff[j][i] *= fp
+            ms.com[j][i] *= fc
+        ms.mass[j] *= fm
+        if j >= 6:                                                             # [[1, .3, -.2], [.3, 1, .25], [-.2, .25, 1]] is positive definite
+            a, b, d = ms.inertia[j][0], ms.inertia[j][1], ms.inertia[j][2]
+            ms.inertia[j][3], ms.inertia[j][4], ms.inertia[j][5] = 0.3 * (a * b) ** 0.5, -0.2 * (a * d) ** 0.5, 0.25 * (b * d) ** 0.5
+    return ms
 
 
 def guarded(k, *tail):

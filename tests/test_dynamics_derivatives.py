@@ -5,7 +5,7 @@ route.
 
 Inputs: poses from fwddyn_ref.regular_poses with |cos q4| >= 0.3 (the full joint range without the 17 degrees around the base's
 gimbal lock, where M is singular and d qdd is unbounded: test_reference_roundoff says why not the default 0.1), qd and qdd from invdyn_ref.random_rates (+-3, +-10), tau from fwddyn_ref.targets, the second
-model from fwddyn_ref.scaled_model / set_armature.
+model from query_rig.scaled_model / fwddyn_ref.set_armature, the third from tests/generic_model.py.
 
 Metrics (dynderiv_ref.err_dtau, err_dqdd), with d_r = sqrt(M64_rr) and D[r, c] = d_r / d_c the Jacobian: E_dtau is per pose
 max_rc |D - D64|_rc / d_r over max_rc |D64|_rc / d_r, E_dqdd the same with |.|_rc d_r; the max over poses.  A pose counts as a whole.
@@ -119,8 +119,17 @@ def test_reference_against_oracle_differences():
     for flags = 0.  Measured on these 6 poses: 1.47e-08 / 1.82e-11 with gravity, 1.10e-08 / 7.4e-12 without; tau itself agrees
     with the oracle's to 6e-15.  (Over HandGeometry.fk, which normalises the model's float32 quaternions where the engine and the
     oracle do not, d/dqd was off by 1.3e-7: dynderiv_ref.frames.)"""
+    _against_oracle_differences(None)
+
+
+def test_reference_against_oracle_differences_generic_model():
+    """The same on the model of tests/generic_model.py."""
+    _against_oracle_differences("generic")
+
+
+def _against_oracle_differences(model):
     from oracle.oracle import Oracle
-    sc, ms = _setup(1)
+    sc, ms = _setup(1, model=model)
     hk, links = kr.HandKin(ms), dd.Links(ms)
     q = poses(hk, 6, seed=3)
     qd, qdd = ir.random_rates(6, seed=4)
@@ -142,9 +151,19 @@ def test_reference_roundoff():
     poses.  With fwddyn_ref.regular_poses' default |cos q4| >= 0.1 the free acceleration's d/dq figure was 2.88e-03, 4 x that above
     the cap: d qdd grows with 1 / cos^2 q4, the inputs were wrong for this quantity, and every draw of this suite asks for
     |cos q4| >= MIN_COS = 0.3."""
-    sc, ms = _setup(1)
+    _reference_roundoff(None)
+
+
+def test_reference_roundoff_generic_model():
+    """The same measurement and cap on the model of tests/generic_model.py, its armatures in the forward route."""
+    _reference_roundoff("generic")
+
+
+def _reference_roundoff(model):
+    sc, ms = _setup(1, model=model)
     q = poses(kr.HandKin(ms), 300, seed=3)
-    r = references(sc, ms, q, ir.random_rates(300, seed=4)[0], seed=5)
+    arm = None if model is None else np.array(np.ctypeslib.as_array(ms.armature), dtype=np.float64)
+    r = references(sc, ms, q, ir.random_rates(300, seed=4)[0], seed=5, arm=arm)
     for name in ID_CASES + ("fd_full", "fd_free"):
         print(f"reference roundoff over 300 poses, {name}: e = {r[name]['e'][0]:.3g} (d/dq), {r[name]['e'][1]:.3g} (d/dqd)")
         assert all(0 < FACTOR * e <= 1e-2 for e in r[name]["e"]), name
@@ -315,8 +334,7 @@ def test_accuracy_against_fp64(posed):
 def test_armature_and_different_model():
     """The scaled model with general finger inertias and armatures of the size of M's diagonal: the inverse derivatives, and the
     forward ones with DEXSIM_FD_ARMATURE against -solve(M64 + diag(a), .) and without it against -solve(M64, .)."""
-    sc, ms = _setup(N)
-    fr.scaled_model(ms)
+    sc, ms = _setup(N, model="scaled")
     hk = kr.HandKin(ms)
     arm = fr.set_armature(ms, kr.oracle_pair(sc, ms)[1], 0.5 * (hk.geom.lo + hk.geom.hi))
     q, qd = poses(hk, N, 22), ir.random_rates(N, 32)[0]
@@ -328,6 +346,19 @@ def test_armature_and_different_model():
     del off["full"], off["noflags"], off["bias"]
     check_all(gpu_all(core, on, N, armature=True), on, "scaled model, armature")
     check_all(gpu_all(core, off, N), off, "scaled model, no armature")
+    core.close()
+
+
+@pytest.mark.gpu
+def test_structure_free_model():
+    """The model of tests/generic_model.py, which has none of the default model's exact zeros, ones and repeated numbers: the
+    inverse derivatives and the forward ones with the model's own armatures, the bounds recomputed on these rows of this model."""
+    sc, ms = _setup(N, model="generic", free_bodies=True)
+    arm = np.array(np.ctypeslib.as_array(ms.armature), dtype=np.float64)
+    q, qd = poses(kr.HandKin(ms), N, 23), ir.random_rates(N, 33)[0]
+    core = _core_at(sc, ms, q, qd)
+    on = references(sc, ms, q, qd, seed=43, arm=arm)
+    check_all(gpu_all(core, on, N, armature=True), on, "generic model, armature")
     core.close()
 
 

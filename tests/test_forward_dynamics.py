@@ -126,9 +126,20 @@ def test_reference_roundoff():
     """The measurement the GPU tolerances rest on, and its cap.  Measured over these 300 poses (E_qdd / E_res): full 4.83e-05 /
     1.43e-05, free 4.18e-05 / 4.94e-06, nograv 4.89e-05 / 8.57e-06, msolve 9.60e-05 / 8.81e-06.  The GPU tests recompute the figures on
     their own 70 poses."""
-    sc, ms = _setup(1)
+    _reference_roundoff(None, None)
+
+
+def test_reference_roundoff_generic_model():
+    """The same measurement and cap on the model of tests/generic_model.py, with its armatures in the solve.  Measured (E_qdd /
+    E_res): full 1.62e-05 / 4.86e-06, free 5.64e-06 / 8.21e-06, nograv 1.08e-05 / 3.73e-06, msolve 1.38e-05 / 4.93e-06."""
+    _reference_roundoff("generic", True)
+
+
+def _reference_roundoff(model, armature):
+    sc, ms = _setup(1, model=model)
     q = fr.regular_poses(kr.HandKin(ms), 300, seed=3)
-    r = references(sc, ms, q, ir.random_rates(300, seed=4)[0], seed=5)
+    arm = np.array(np.ctypeslib.as_array(ms.armature), dtype=np.float64) if armature else None
+    r = references(sc, ms, q, ir.random_rates(300, seed=4)[0], seed=5, arm=arm)
     for name in CASES:
         print(f"reference roundoff over 300 poses, {name}: e_qdd = {r[name]['e_qdd']:.3g}, e_res = {r[name]['e_res']:.3g}")
         assert 0 < FACTOR * r[name]["e_qdd"] <= 1e-3 and 0 < FACTOR * r[name]["e_res"] <= 1e-3, name
@@ -151,13 +162,20 @@ def test_reference_solve_against_numpy():
 
 def _armature_case(seed):
     """test_inverse_dynamics.py::test_different_model's scaled model with armatures of the size of M's own diagonal."""
-    sc, ms = _setup(N)
-    fr.scaled_model(ms)
+    sc, ms = _setup(N, model="scaled")
     hk = kr.HandKin(ms)
     arm = fr.set_armature(ms, kr.oracle_pair(sc, ms)[1], 0.5 * (hk.geom.lo + hk.geom.hi))
     q = fr.regular_poses(hk, N, seed)
     qd = ir.random_rates(N, seed + 10)[0]
     return sc, ms, q, qd, arm
+
+
+def _generic_case(seed):
+    """The model of tests/generic_model.py with its own armatures (0.5-2 e-4 per joint: the size of M's diagonal on the finger joints)."""
+    sc, ms = _setup(N, model="generic", free_bodies=True)
+    hk = kr.HandKin(ms)
+    arm = np.array(np.ctypeslib.as_array(ms.armature), dtype=np.float64)
+    return sc, ms, fr.regular_poses(hk, N, seed), ir.random_rates(N, seed + 10)[0], arm
 
 
 def test_missing_terms_are_discriminated():
@@ -360,6 +378,18 @@ def test_armature_and_different_model():
     on, off = references(sc, ms, q, qd, seed=42, arm=arm), references(sc, ms, q, qd, seed=42)
     check_all(gpu_all(core, on, N, armature=True), on, "scaled model, armature")
     check_all(gpu_all(core, off, N), off, "scaled model, no armature")
+    core.close()
+
+
+@pytest.mark.gpu
+def test_structure_free_model():
+    """The model of tests/generic_model.py, which has none of the default model's exact zeros, ones and repeated numbers: every
+    case with and without its armatures, the bounds recomputed from the float32 reference on these rows of this model."""
+    sc, ms, q, qd, arm = _generic_case(23)
+    core = _core_at(sc, ms, q, qd)
+    on, off = references(sc, ms, q, qd, seed=43, arm=arm), references(sc, ms, q, qd, seed=43)
+    check_all(gpu_all(core, on, N, armature=True), on, "generic model, armature")
+    check_all(gpu_all(core, off, N), off, "generic model, no armature")
     core.close()
 
 

@@ -75,7 +75,16 @@ def test_reference_quaternions():
 def test_reference_identities_and_roundoff():
     """The centroid reference against the fp64 oracle -- 1/2 qd^T M qd and g(q) . qd = -M_tot g . v_C -- and the reference's own
     float32 roundoff, the figures the GPU bounds are read against."""
-    sc, ms = setup(1)
+    _identities_and_roundoff(None)
+
+
+def test_reference_identities_and_roundoff_generic_model():
+    """The same identities and roundoff bars on the model of tests/generic_model.py, every body on a frame of its own."""
+    _identities_and_roundoff("generic")
+
+
+def _identities_and_roundoff(model):
+    sc, ms = setup(1, model=model, free_bodies=model is not None)
     fk = fr.HandFK(ms, sc)
     q, qd = fk.test_rows(N, seed=21)
     qd = np.random.default_rng(1021).uniform(-1, 1, (N, NJ)).astype(np.float32)        # every rate uniform in +-1 for these figures
@@ -206,8 +215,9 @@ def check_all(c, body, site, hand, cen, what, ref=None, qd="case"):
     fr.check(fr.site_errors(hand, r["H64"], "hand-frame site"), what)
     fr.check(fr.centroid_errors(cen, r["C64"], qd, fk.total_mass, fk.gravity), what)
     assert (bits(body[:, 0, 7:13]) == 0).all()                                 # hand_mount: a twist of exact +0.0f
-    spawn = np.array(list(c["core"].model.spawn_pos), dtype=np.float32)
-    assert (body[:, 0, 0:3] == spawn + np.array(np.ctypeslib.as_array(c["core"].model.body_p), dtype=np.float32)[0]).all()
+    if tuple(c["core"].model.spawn_quat) == (0.0, 0.0, 0.0, 1.0):              # hand_mount under an identity spawn frame: one exact sum
+        spawn = np.array(list(c["core"].model.spawn_pos), dtype=np.float32)      # (a turned spawn frame: the body position bound above)
+        assert (body[:, 0, 0:3] == spawn + np.array(np.ctypeslib.as_array(c["core"].model.body_p), dtype=np.float32)[0]).all()
 
 
 @pytest.fixture(scope="module")
@@ -231,17 +241,7 @@ def test_against_float64_reference(posed):
 def test_different_model():
     """The scaled model of test_kindyn.test_different_model: per-joint scaled offsets, centres of mass and masses, finger links with
     off-diagonal inertia -- no constant of the default model is baked in."""
-    sc, ms = setup(N)
-    rng = np.random.default_rng(8)
-    for j in range(NJ):
-        fp, fc, fm = rng.uniform(0.7, 1.4, 3)
-        for i in range(3):
-            ms.jpoff[j][i] *= fp
-            ms.com[j][i] *= fc
-        ms.mass[j] *= fm
-        if j >= 6:                                                             # [[1, .3, -.2], [.3, 1, .25], [-.2, .25, 1]] is positive definite
-            a, b, d = ms.inertia[j][0], ms.inertia[j][1], ms.inertia[j][2]
-            ms.inertia[j][3], ms.inertia[j][4], ms.inertia[j][5] = 0.3 * (a * b) ** 0.5, -0.2 * (a * d) ** 0.5, 0.25 * (b * d) ** 0.5
+    sc, ms = setup(N, model="scaled")
     c = _case(ms, sc, seed=22)
     body, site, cen = gpu_fk(c["core"], N)
     _, hand, _ = gpu_fk(c["core"], N, hand_frame=True, want=("site",))
@@ -250,11 +250,29 @@ def test_different_model():
 
 
 @pytest.mark.gpu
+def test_structure_free_model():
+    """The model of tests/generic_model.py, which has none of the default model's exact zeros, ones and repeated numbers, every body
+    on a frame of its own: bodies, world- and hand-frame sites and the centroid against the float64 reference, and the contract
+    with what the engine publishes (publish_body) and with the Jacobian, the mass matrix and the gravity force on this model."""
+    sc, ms = setup(N, model="generic", free_bodies=True)
+    c = _case(ms, sc, seed=23)
+    c["body"], c["site"], c["cen"] = gpu_fk(c["core"], N)
+    _, c["hand"], _ = gpu_fk(c["core"], N, hand_frame=True, want=("site",))
+    check_all(c, c["body"], c["site"], c["hand"], c["cen"], "generic model")
+    assert np.abs(c["hand"][:, 0] - [0, 0, 0, 0, 0, 0, 1]).max() <= 1e-6       # site 0 in its own frame
+    _contract_with_published_state(c)
+    c["core"].close()
+
+
+@pytest.mark.gpu
 def test_contract_with_published_state(posed):
     """What the engine publishes for the same state -- rigid_body_states, the arena's site_pose and hand_vel -- and what the other
     queries say about it: J qd, 1/2 qd^T M qd, g . qd."""
+    _contract_with_published_state(posed)
+
+
+def _contract_with_published_state(c):
     import torch
-    c = posed
     core, q, qd, fk = c["core"], c["q"], c["qd"], c["fk"]
     pose_core(core, q, qd=qd)
     core.refresh_body_states()

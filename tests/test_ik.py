@@ -139,6 +139,17 @@ def hk():
     return ir.HandIK(ms, sc)
 
 
+@pytest.fixture(scope="module")
+def hk_generic():
+    """The reference on the model of tests/generic_model.py: no identity site frame, no offset on the x axis, no axis along e_y."""
+    sc, ms = _setup(N, model="generic")
+    return ir.HandIK(ms, sc)
+
+
+def test_reference_jacobian_is_the_derivative_of_fk_generic_model(hk_generic):
+    test_reference_jacobian_is_the_derivative_of_fk(hk_generic)
+
+
 def test_batched_fk_is_render_refs_fk(hk):
     """ik_ref evaluates all rows at once; its joint-by-joint formula is HandGeometry.fk's, held here to the last bits."""
     _, q0, _ = hk.test_poses(6, seed=2)
@@ -191,6 +202,13 @@ def test_reference_converges(hk, name):
     assert left <= 1.4e-6
 
 
+@pytest.mark.parametrize("name", list(CONV))
+def test_reference_converges_generic_model(hk_generic, name):
+    """The condition for running the convergence test on the model of tests/generic_model.py: the float64 reference itself
+    converges there within the suite's 32 iterations, on at least 90 % of the rows, and its float32 evaluation stays on the floor."""
+    test_reference_converges(hk_generic, name)
+
+
 # ------------------------------------------------------------------------------------------------- GPU helpers
 def gpu_ik(core, k, targets, env_ids=None, q=None, want=("q", "residual"), **prm):
     """core.solve_ik into guarded outputs: dict of numpy arrays controls (k, 18), q (k, 26), residual (k, 5)."""
@@ -218,6 +236,18 @@ def rig(hk):
     u0, q0, _ = hk.test_poses(N, SEED)
     pose_core(core, q0)
     return dict(core=core, hk=hk, u0=u0, q0=q0, conv={})
+
+
+@pytest.fixture(scope="module")
+def rig_generic(hk_generic):
+    """The same on the model of tests/generic_model.py."""
+    from dexrobot_isaac_amd.core import DexSimCore
+    sc, ms = _setup(N, model="generic")
+    core = DexSimCore(sc, ms, "cuda:0")
+    core.reset()
+    u0, q0, _ = hk_generic.test_poses(N, SEED)
+    pose_core(core, q0)
+    return dict(core=core, hk=hk_generic, u0=u0, q0=q0, conv={})
 
 
 def _conv_gpu(rig, name):
@@ -251,6 +281,21 @@ def test_one_iteration_against_reference(rig, name, free, pert):
     # residual and q_out of that result
     assert np.abs(out["residual"] - hk.residual64(u0, out["controls"], tg)).max() <= 1e-5
     assert (out["q"] == hk.q_of_u(out["controls"], np.float32)).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,free,pert", [("fingers", ir.FINGERS_FREE, 0.3), ("all", ir.ALL_FREE, 0.1)])
+def test_structure_free_model_one_iteration(rig_generic, name, free, pert):
+    """The one-iteration comparison on the model of tests/generic_model.py, the bound recomputed on its rows."""
+    test_one_iteration_against_reference(rig_generic, name, free, pert)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CONV))
+def test_structure_free_model_convergence(rig_generic, name):
+    """The convergence test under its rule on the model of tests/generic_model.py (test_reference_converges_generic_model holds
+    the condition: the float64 reference converges there)."""
+    test_convergence(rig_generic, name)
 
 
 @pytest.mark.gpu
@@ -318,9 +363,21 @@ def test_fixed_point_and_hand_frame(hk):
     q off the coupling manifold by the PD tracking error (the two DOFs of a DIP control differ by ~1e-2 rad while they move), which
     the start-value projection turns into millimetres of residual.  The check therefore uses the state q = C u: the stepped state
     projected onto the manifold, written back, published and observed again (obs-only post block)."""
+    _fixed_point_and_hand_frame(hk, None)
+
+
+@pytest.mark.gpu
+def test_structure_free_model_fixed_point_and_hand_frame(hk_generic):
+    """The same on the model of tests/generic_model.py: the observation stage's tips and pads, in the world and in the turned hand
+    frame of that model, are fixed points of the solve on it."""
+    from tests.query_rig import generic_hand
+    _fixed_point_and_hand_frame(hk_generic, generic_hand())
+
+
+def _fixed_point_and_hand_frame(hk, hand_model):
     import torch
     from dexrobot_isaac_amd import make_env
-    env = make_env("BlindGrasping", N, "cuda:0", "cuda:0", 0)
+    env = make_env("BlindGrasping", N, "cuda:0", "cuda:0", 0, hand_model=hand_model)
     env.reset()
     g = torch.Generator().manual_seed(9)
     for _ in range(10):

@@ -79,7 +79,16 @@ def references(sc, ms, q, qd, qdd):
 def test_reference_roundoff():
     """The measurement the GPU tolerances rest on, and its cap.  Measured over these 300 poses: e_full = 2.33e-5, e_bias = 8.7e-7,
     e_c = 5.5e-6, e_lin = 4.1e-6, e_ang = 3.5e-7.  The GPU tests recompute the figures on their own 70 poses."""
-    sc, ms = _setup(1)
+    _reference_roundoff(None)
+
+
+def test_reference_roundoff_generic_model():
+    """The same measurement and cap on the model of tests/generic_model.py, every body on a frame of its own."""
+    _reference_roundoff("generic")
+
+
+def _reference_roundoff(model):
+    sc, ms = _setup(1, model=model, free_bodies=model is not None)
     q = kr.HandKin(ms).random_poses(300, seed=3)
     qd, qdd = ir.random_rates(300, seed=4)
     r = references(sc, ms, q, qd, qdd)
@@ -287,20 +296,21 @@ def test_bias_accel_against_float64_recursion(posed):
 def test_different_model():
     """Per-joint scaled offsets, centres of mass and masses, finger links with off-diagonal inertia (test_kindyn's model): no
     constant of the default model is baked in."""
-    sc, ms = _setup(N)
-    rng = np.random.default_rng(8)
-    for j in range(NJ):
-        fp, fc, fm = rng.uniform(0.7, 1.4, 3)
-        for i in range(3):
-            ms.jpoff[j][i] *= fp
-            ms.com[j][i] *= fc
-        ms.mass[j] *= fm
-        if j >= 6:                                                             # [[1, .3, -.2], [.3, 1, .25], [-.2, .25, 1]] is positive definite
-            a, b, d = ms.inertia[j][0], ms.inertia[j][1], ms.inertia[j][2]
-            ms.inertia[j][3], ms.inertia[j][4], ms.inertia[j][5] = 0.3 * (a * b) ** 0.5, -0.2 * (a * d) ** 0.5, 0.25 * (b * d) ** 0.5
+    sc, ms = _setup(N, model="scaled")
     c = _case(ms, sc, seed=22)
     core = c["core"]
     check_all(c, gpu_tau(core, N, qdd=c["qdd"]), gpu_tau(core, N), gpu_tau(core, N, gravity=False), gpu_acc(core, N), "scaled model")
+    core.close()
+
+
+@pytest.mark.gpu
+def test_structure_free_model():
+    """The model of tests/generic_model.py, which has none of the default model's exact zeros, ones and repeated numbers, every
+    body on a frame of its own: tau with and without qdd and gravity, the bias acceleration of all 37 bodies."""
+    sc, ms = _setup(N, model="generic", free_bodies=True)
+    c = _case(ms, sc, seed=23)
+    core = c["core"]
+    check_all(c, gpu_tau(core, N, qdd=c["qdd"]), gpu_tau(core, N), gpu_tau(core, N, gravity=False), gpu_acc(core, N), "generic model")
     core.close()
 
 

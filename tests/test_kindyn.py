@@ -42,7 +42,16 @@ def test_abi_exports_and_null_handle(lib):
 
 
 def test_reference_jacobian_is_the_derivative_of_fk():
-    _, ms = _setup(1)
+    _jacobian_is_the_derivative_of_fk(None)
+
+
+def test_reference_jacobian_is_the_derivative_of_fk_generic_model():
+    """On the model of tests/generic_model.py, every body on a frame of its own."""
+    _jacobian_is_the_derivative_of_fk("generic")
+
+
+def _jacobian_is_the_derivative_of_fk(model):
+    _, ms = _setup(1, model=model, free_bodies=model is not None)
     hk = kr.HandKin(ms)
     h = 1e-4
     worst = 0.0
@@ -67,7 +76,17 @@ def test_reference_roundoff():
     e_M is the maximum of a long-tailed distribution (per pose: median 6e-6, 95 % below 1.5e-5; the momentum-form CRBA of the
     oracle takes moments about the world origin, and the worst poses have the slides near +-1 m): over six other seeds of 300 poses
     it came out between 1.9e-5 and 3.5e-5.  The GPU tests recompute it on their own 70 poses."""
-    sc, ms = _setup(1)
+    g64 = _reference_roundoff(None)
+    assert abs(g64[:, 2] - 5.17).max() < 0.01                                  # the z slide carries the hand's weight
+
+
+def test_reference_roundoff_generic_model():
+    """The same measurement and caps on the model of tests/generic_model.py."""
+    _reference_roundoff("generic")
+
+
+def _reference_roundoff(model):
+    sc, ms = _setup(1, model=model, free_bodies=model is not None)
     hk = kr.HandKin(ms)
     o32, o64 = kr.oracle_pair(sc, ms)
     q = hk.random_poses(300, seed=3)
@@ -77,7 +96,7 @@ def test_reference_roundoff():
     e_J = max(float(np.abs(hk.jacobian(x, np.float32).astype(np.float64) - hk.jacobian(x.astype(np.float64))).max()) for x in q)
     print(f"reference roundoff over {len(q)} poses: e_M = {e_M:.3g}, e_g = {e_g:.3g}, e_J = {e_J:.3g}")
     assert 4 * e_M <= 1e-4 and 4 * e_g <= 1e-5
-    assert abs(g64[:, 2] - 5.17).max() < 0.01                                  # the z slide carries the hand's weight
+    return g64
 
 
 _stub_core = stub_core(dict(
@@ -171,7 +190,10 @@ def check_mass(c, M, g, what):
             if fa != fb:
                 assert (bits(M[:, 6 + 4 * fa: 10 + 4 * fa, 6 + 4 * fb: 10 + 4 * fb]) == 0).all()
     assert (np.linalg.eigvalsh(M.astype(np.float64)) > 0).all()
-    assert (np.abs(g[:, 0:2]) <= 1e-6 * np.abs(g[:, 2:3])).all()               # gravity along z: no force on the x and y slides
+    geom = c["hk"].geom                                                         # gravity along z: no force on a slide whose axis is level
+    R = geom.fk(np.zeros(NJ))[1]                                               # (both of the default model's; the slides turn nothing)
+    level = [j for j in (0, 1) if abs((R[j] @ geom.jaxis[j])[2]) <= 1e-7]
+    assert (np.abs(g[:, level]) <= 1e-6 * np.abs(g[:, 2:3])).all()
 
 
 # ------------------------------------------------------------------------------------------------- GPU
@@ -239,20 +261,21 @@ def test_mass_matrix_and_gravity_against_fp64_oracle(posed):
 def test_different_model():
     """Per-joint scaled offsets, centres of mass and masses, finger links with off-diagonal inertia: no constant of the default
     model is baked in, and the diagonal-inertia shortcut of the step path is not taken."""
-    sc, ms = _setup(N)
-    rng = np.random.default_rng(8)
-    for j in range(NJ):
-        fp, fc, fm = rng.uniform(0.7, 1.4, 3)
-        for i in range(3):
-            ms.jpoff[j][i] *= fp
-            ms.com[j][i] *= fc
-        ms.mass[j] *= fm
-        if j >= 6:                                                             # [[1, .3, -.2], [.3, 1, .25], [-.2, .25, 1]] is positive definite
-            a, b, d = ms.inertia[j][0], ms.inertia[j][1], ms.inertia[j][2]
-            ms.inertia[j][3], ms.inertia[j][4], ms.inertia[j][5] = 0.3 * (a * b) ** 0.5, -0.2 * (a * d) ** 0.5, 0.25 * (b * d) ** 0.5
+    sc, ms = _setup(N, model="scaled")
     c = _case(ms, sc, seed=22)
     check_jacobian(c, gpu_jac(c["core"], N), "scaled model")
     check_mass(c, *gpu_mass(c["core"], N), "scaled model")
+    c["core"].close()
+
+
+@pytest.mark.gpu
+def test_structure_free_model():
+    """The model of tests/generic_model.py, which has none of the default model's exact zeros, ones and repeated numbers: the
+    Jacobian of all 37 bodies, each on a frame of its own, and M and the gravity force, e_M and e_g recomputed on these rows."""
+    sc, ms = _setup(N, model="generic", free_bodies=True)
+    c = _case(ms, sc, seed=23)
+    check_jacobian(c, gpu_jac(c["core"], N), "generic model")
+    check_mass(c, *gpu_mass(c["core"], N), "generic model")
     c["core"].close()
 
 

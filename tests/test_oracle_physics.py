@@ -76,6 +76,22 @@ def test_mass_matrix_gravity_coriolis_match_numerical_derivation():
         _check_derivation(o, model, q, qd)
 
 
+def test_mass_matrix_gravity_coriolis_match_numerical_derivation_on_the_generic_model():
+    """The same derivation on the hand model without exact zeros, ones and repeated numbers (tests/generic_model.py, through
+    tests/physics_rig.py): the original pose, rows of the wide sample drawn for this model's limits, and four poses over the full
+    joint range -- the oracle is the reference of every GPU test that runs on this model."""
+    from tests import physics_rig, wide_states
+    sc, model, ms = physics_rig.setup("BlindGrasping", 4, model="generic")
+    o = Oracle(sc, ms, f64=True)
+    scN, modelN, _ = physics_rig.setup("BlindGrasping", physics_rig.N, model="generic")
+    st = wide_states.sample("free", physics_rig.N, physics_rig.SEED, config=(scN, modelN))
+    rng = np.random.default_rng(0)
+    poses = [(rng.uniform(-0.3, 0.6, 26), rng.uniform(-1, 1, 26))] + [(st["q"][:, e].copy(), st["qd"][:, e].copy()) for e in (0, 1, 2, 3)]
+    poses += [(rng.uniform(model.lo, model.hi), rng.uniform(-1, 1, 26)) for _ in range(4)]
+    for q, qd in poses:
+        _check_derivation(o, model, q, qd)
+
+
 def _check_derivation(o, model, q, qd):
     M, b0 = o.mass_matrix(q, np.zeros(26))
     Mn, gn = _numeric_mass_and_gravity(model, q)

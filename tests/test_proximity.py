@@ -228,6 +228,23 @@ def poses(hp):
     return dict(q=q, box=box, **ref)
 
 
+@pytest.fixture(scope="module")
+def hp_generic():
+    """The reference on the model of tests/generic_model.py: every capsule starts off its joint origin and ends off the x axis."""
+    sc, ms = _setup(N, model="generic")
+    return pr.HandProx(ms, sc)
+
+
+@pytest.fixture(scope="module")
+def poses_generic(hp_generic):
+    q, box = hp_generic.test_poses(N, SEED)
+    return dict(q=q, box=box, **_reference(hp_generic, q, box))
+
+
+def test_reference_roundoff_and_selection_generic_model(hp_generic, poses_generic):
+    test_reference_roundoff_and_selection(hp_generic, poses_generic)
+
+
 def test_reference_roundoff_and_selection(hp, poses):
     """The measurement the GPU bars rest on: the reference's own float32-vs-float64 differences on the 70 rows, and how many
     records are well-conditioned."""
@@ -273,6 +290,18 @@ def test_against_reference(rig, hp, poses):
     inside = r64["box"]["meets"] & sel["box_d"]
     assert (out["cap_env"][:, :, 0, 0][inside] <= -r[None, :].repeat(N, 0)[inside].astype(np.float32)).all()
     assert m["box_d"] < 6.5e-3 and m["pair_d"] < 6.5e-3
+
+
+@pytest.mark.gpu
+def test_structure_free_model(hp_generic, poses_generic):
+    """test_against_reference on the model of tests/generic_model.py, the bounds recomputed on its rows."""
+    from dexrobot_isaac_amd.core import DexSimCore
+    sc, ms = _setup(N, model="generic")
+    core = DexSimCore(sc, ms, "cuda:0")
+    core.reset()
+    pose_core(core, poses_generic["q"], poses_generic["box"])
+    test_against_reference(dict(core=core, full=gpu_query(core, N)), hp_generic, poses_generic)
+    core.close()
 
 
 @pytest.mark.gpu
@@ -381,7 +410,7 @@ def _narrowphase_states(hp, co, rng):
     geom, hb = hp.geom, 0.5 * hp.box_size
     q_all, _ = hp.test_poses(4 * N, SEED + 1)
     zj = int(np.argmax([abs(geom.fk(np.eye(NJ)[j])[0][5][2] - geom.fk(np.zeros(NJ))[0][5][2]) for j in range(3)]))   # the z slide
-    zs = np.sign(geom.fk(np.eye(NJ)[zj])[0][5][2] - geom.fk(np.zeros(NJ))[0][5][2])
+    zs = 1.0 / (geom.fk(np.eye(NJ)[zj])[0][5][2] - geom.fk(np.zeros(NJ))[0][5][2])   # slide per metre of height: +-1 where its axis is vertical
     qs, boxes, caps, kinds = [], [], [], []
     tries = iter(range(len(q_all)))
     while len(qs) < N:
@@ -429,8 +458,19 @@ def test_against_engine_narrowphase(hp, poses):
     raw gap of a sample-0 hand / box entry, Q the queried distance of the same capsule, L its axis length, tol the distance bound
     of test_against_reference.  The engine's t is a 2^-10 bisection snapped to an end within 2 %, and distance is 1-Lipschitz in
     the axis point: Q <= D + tol and D - Q <= (0.02 + 2^-11) L + tol."""
+    _engine_narrowphase(hp, poses, None)
+
+
+@pytest.mark.gpu
+def test_structure_free_model_engine_narrowphase(hp_generic, poses_generic):
+    """The same on the model of tests/generic_model.py: the step path's narrowphase sees capsules that start off the joint origin
+    and end off the x axis, on tilted frames."""
+    _engine_narrowphase(hp_generic, poses_generic, "generic")
+
+
+def _engine_narrowphase(hp, poses, model):
     from tests.hip_backend import HipBackend
-    sc, ms = _setup(N)
+    sc, ms = _setup(N, model=model)
     co, rest = float(sc.contact_offset), float(sc.rest_offset)
     rng = np.random.default_rng(SEED + 2)
     q, box, chosen, kinds = _narrowphase_states(hp, co, rng)

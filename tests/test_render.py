@@ -275,6 +275,30 @@ def test_scene_and_images_padded_lanes(posed):
 
 
 @pytest.mark.gpu
+def test_structure_free_model():
+    """The 64 x 48 images and the scene records on the model of tests/generic_model.py: capsules that start off their joint origin and
+    end off the x axis, on tilted joint frames under a turned spawn frame.  The same recipe, masks, share of unstable pixels and
+    tolerances (derived from this model's own reference images)."""
+    from dexrobot_isaac_amd.core import DexSimCore
+    from tests.query_rig import setup
+    sc, ms = setup(N, model="generic")
+    geom = rr.HandGeometry(ms)
+    core = DexSimCore(sc, ms, "cuda:0")
+    core.reset()
+    q, bp, bq, eye, target = make_poses(geom, N, float(sc.box_size), seed=12)
+    pose_core(core, q, bp, bq)
+    boxes = [(bp[e].astype(np.float64), bq[e].astype(np.float64), float(sc.box_size)) for e in range(N)]
+    cams = [rr.look_at(eye[e].astype(np.float64), target[e].astype(np.float64)) for e in range(N)]
+    refs, tol_abs, tol_rel = reference_images(geom, q, boxes, cams, W1, H1, 60.0, 0.01, 10.0)
+    ids = np.unique(np.concatenate([r["seg"].ravel() for r in refs]))
+    assert len(ids) >= 20 and {_abi.SEG_NONE, _abi.SEG_GROUND, _abi.SEG_BOX} <= set(ids.tolist())   # the recipe covers the ids
+    scene, depth, rgba, seg = gpu_render(core, make_camera(W1, H1), eye=eye, target=target)
+    compare_scene(core, scene, geom, q, boxes, cams)
+    compare_images(refs, tol_abs, tol_rel, depth, rgba, seg, "generic model, 64x48")
+    core.close()
+
+
+@pytest.mark.gpu
 def test_partial_waves_and_subsets(posed):
     p = posed
     core = p["core"]

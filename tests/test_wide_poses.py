@@ -295,7 +295,37 @@ def test_sample_covers_the_cases():
     assert all((c[:, 8] == 2).all() for c in pr.lists(o, N))
 
 
-@pytest.mark.parametrize("task,name", [("BlindGrasping", None), ("BaseTask", None), ("BlindGrasping", "all")], ids=["default", "basetask", "model-all"])
+def test_sample_covers_the_cases_generic_model():
+    """The conditions the GPU tests on the `generic` model (tests/generic_model.py) rely on, from the references alone: the sample
+    drawn for its limits covers the quadrants and the stops as the default one does, no env lists a hand contact (the hand_reach of
+    this model under its turned spawn frame included), every clamped joint stands still, at most LEFT_OUT of the envs hold a joint
+    that roundoff decides, and the two oracles alone decide at most LEFT_OUT of the envs differently (physics_rig.oracles_differ)."""
+    name = "generic"
+    free, stops = _teacher_ref("free", N, name=name), _teacher_ref("stops", N, name=name)
+    ms = _setup("BlindGrasping", N, name)[2]
+    q = free[0]["start"]["q"]
+    base_k, thumb_k = int((_quadrant(q[3:6]) != 0).sum()), int((_quadrant(q[THUMB]) != 0).sum())
+    clamped = [int((r["at_lo"] | r["at_hi"]).sum()) for r in stops]
+    at_lo, at_hi = [int(r["at_lo"].sum()) for r in stops], [int(r["at_hi"].sum()) for r in stops]
+    amb = [float(r["amb"].any(0).mean()) for recs in (free, stops) for r in recs]
+    left = [float(pr.oracles_differ(r["s64"], r["s32"], ms).mean()) for recs in (free, stops) for r in recs]
+    print(f"\ngeneric model: base rotations outside quadrant 0: {base_k} of {q[3:6].size}; first thumb joints: {thumb_k} of {N}; joint-sub-steps "
+          f"that end clamped, stops: {clamped} (lo {at_lo}, hi {at_hi}); share of envs with an ambiguous joint per sub-step {amb}; "
+          f"share the oracles decide differently {left}")
+    assert base_k >= 188 and thumb_k >= 9                                       # the thresholds of test_sample_covers_the_cases
+    assert all(c >= 517 for c in clamped) and all(c >= 248 for c in at_lo) and all(c >= 268 for c in at_hi)
+    assert max(amb) <= pr.LEFT_OUT and max(left) <= pr.LEFT_OUT
+    for kind, recs in (("free", free), ("stops", stops)):
+        pr.left_by_the_references([dict(left=pr.oracles_differ(r["s64"], r["s32"], ms)) for r in recs])
+        for rec in recs:
+            on = rec["at_lo"] | rec["at_hi"]
+            assert (rec["s64"]["qd"][on] == 0).all(), kind
+            for s, lists in ((rec["s64"], rec["lists64"]), (rec["s32"], rec["lists32"])):
+                assert s["ncontact"].max() <= 4 and all((c[:, 8] == 2).all() for c in lists), kind
+
+
+@pytest.mark.parametrize("task,name", [("BlindGrasping", None), ("BaseTask", None), ("BlindGrasping", "all"), ("BlindGrasping", "generic")],
+                         ids=["default", "basetask", "model-all", "generic"])
 def test_joints_decided_by_roundoff_and_the_clamp_rule(task, name):
     """Item 2.  No env of either kind holds an ambiguous joint in any sub-step (the GPU tests allow 2 %), in the free run neither; and
     the oracle's clamp is the stated rule, to the bit: its q is clip(q_unclamped, lo, hi) and its qd the one-sided max / min of the
@@ -313,7 +343,8 @@ def test_joints_decided_by_roundoff_and_the_clamp_rule(task, name):
             assert np.array_equal(rec["s64"]["q"], q) and np.array_equal(rec["s64"]["qd"], qd), (kind, sub)
             worst = max(worst, np.abs(rec["s64"]["q"] - np.clip(qw, model.lo[:, None], model.hi[:, None])).max())
     print(f"\n{task}, {name}: clamp against the struct's float32 limits: exact; against the Python model's doubles: {worst:.2e}")
-    assert 0 < worst < 1e-7
+    assert worst < 1e-7
+    assert (worst > 0) == bool((f32(model.lo) != model.lo).any() or (f32(model.hi) != model.hi).any())   # (the generic model's limits are float32 numbers)
     if task == "BlindGrasping" and name is None:
         assert _free_ref(N)["left"].sum() == 0
 
@@ -453,7 +484,7 @@ def test_fp32_oracle_in_the_kernels_place_passes():
     """The fp32 oracle itself, through the functions the GPU tests call: teacher-forced sub-steps of both kinds, both tasks and the
     `all` model, the published quantities, the free-running physics step."""
     from oracle.oracle import Oracle
-    for task, name in (("BlindGrasping", None), ("BaseTask", None), ("BlindGrasping", "all")):
+    for task, name in (("BlindGrasping", None), ("BaseTask", None), ("BlindGrasping", "all"), ("BlindGrasping", "generic")):
         sc, _, ms = _setup(task, N, name)
         for kind in KINDS:
             r = _check_teacher(lambda: Oracle(sc, ms), kind, N, task, name)
@@ -602,3 +633,13 @@ def test_general_kernels_on_the_model_without_structure_at_wide_poses(kind):
     oracles of that model."""
     _check_teacher(lambda: _hip(N, name="all"), kind, N, name="all")
     _check_published(lambda: _hip(N, name="all"), kind, N, name="all")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_general_kernels_on_the_generic_model_at_wide_poses(kind):
+    """The same on the `generic` model (tests/generic_model.py), which lacks every zero, one and repeated number of the default model by
+    tenths of a radian and a centimetre, not by the 1e-2 rad and millimetres that flip the classification: every term of the
+    general chains carries weight.  test_sample_covers_the_cases_generic_model holds the conditions of the sample."""
+    _check_teacher(lambda: _hip(N, name="generic"), kind, N, name="generic")
+    _check_published(lambda: _hip(N, name="generic"), kind, N, name="generic")
