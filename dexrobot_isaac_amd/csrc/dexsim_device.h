@@ -206,6 +206,18 @@ struct M3 { float m[9]; };
 
 #define DI __device__ __forceinline__
 
+// LDS tokens: the words through which the waves of a step-kernel workgroup hand over to one another between barriers (who posts,
+// who waits: dexsim_physics.hip.inc).  `sh` is the kernel's `extern __shared__` base, `word` an index in floats.  The accesses are
+// volatile AND typed as LDS: a volatile access through a generic pointer is left alone by the address-space inference and becomes
+// a FLAT instruction (sc0 sc1, waited for with vmcnt(0) lgkmcnt(0)), which is neither ordered with the DS instructions around it
+// nor cheap; these compile to one ds_read_b32 / ds_write_b32.  DS instructions of a wave execute in order, so "data, then
+// token" on the posting side and "token, then data" on the waiting side need compiler barriers only.
+typedef volatile __attribute__((address_space(3))) float lds_tok_f;
+typedef volatile __attribute__((address_space(3))) int lds_tok_i;
+DI int lds_tok_load(const float* sh, int word) { return __float_as_int(((const lds_tok_f*)sh)[word]); }
+DI void lds_tok_store(float* sh, int word, int v) { ((lds_tok_f*)sh)[word] = __int_as_float(v); }
+DI int lds_cnt_load(const float* sh, int word) { return ((const lds_tok_i*)sh)[word]; }   // a counter kept by LDS atomics
+
 DI V3 v3(float x, float y, float z) { return {x, y, z}; }
 DI V3 v3p(const float* p) { return {p[0], p[1], p[2]}; }
 DI V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }

@@ -781,7 +781,7 @@ DI void schur_row(float* sh, const int dlb, int lane) {
 DI void schur_precompute(float* sh, const int dlb, int lane, const BaseChain& B, int seq, int* dbg_cnt) {
   {
     SPIN_GUARD_INIT();
-    while (*(volatile int*)(sh + FS_COMPCNT * 64) < 5 * seq) { __builtin_amdgcn_s_sleep(2); SPIN_GUARD(dbg_cnt, 4, seq); }
+    while (lds_cnt_load(sh, FS_COMPCNT * 64) < 5 * seq) { __builtin_amdgcn_s_sleep(2); SPIN_GUARD(dbg_cnt, 4, seq); }
   }
   asm volatile("" ::: "memory");
   const Comp comp5 = schur_comp(sh, dlb, lane, B.o5);
@@ -869,16 +869,33 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
     }
   }
   st.mark<SG_SCHUR>(A, N, 0, e, SCHUR_OWN_ROWS);   // own rows done
-  float tauB[6];
+  // The PD terms of the base joints need none of the finger sums: they stand in front of the wait for the helpers' tokens, so that
+  // the scalar loads of kp / kd / armature and the reads of the staged targets are in flight while the helpers finish (behind the
+  // wait they were issued only once the tokens had arrived).  Same expressions and association as when they stood at "S, tau_B".
+  float dgn[6];    // armature + h kdh: what the PD controller adds to the diagonal of S
+  float tauB[6];   // here the PD part kp (tgt - q) - kdh qd; "- bias - gsum" follows below
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const float kp = P->jc[i].kp, kdh = P->jc[i].kd + h * kp;
+    dgn[i] = P->jc[i].armature + h * kdh;
+    // fused sub-step: the base targets were staged in LDS by wave 5 (a global load here would first have to wait for
+    // this wave's own factor stores of phase 1 to drain)
+    const float tgt = tgt_lds >= 0 ? SH(tgt_lds + i) : FLD(targets, i);
+    tauB[i] = kp * (tgt - B.qb[i]) - kdh * B.qdb[i];
+  }
   float bias[6];
   if (split_seq > 0) {
-    // pick up the helpers' sums (LDS operations of a wave execute in order: data stores, then the token store; here the token
-    // loads, then the data loads -- only the compiler has to be kept from reordering them)
+    // (the values above exist before the first poll: the optimiser may not sink them behind the loop)
+    asm volatile("" :: "v"(dgn[0]), "v"(dgn[1]), "v"(dgn[2]), "v"(dgn[3]), "v"(dgn[4]), "v"(dgn[5]),
+                 "v"(tauB[0]), "v"(tauB[1]), "v"(tauB[2]), "v"(tauB[3]), "v"(tauB[4]), "v"(tauB[5]));
+    // pick up the helpers' sums (DS instructions of a wave execute in order: data stores, then the token store; here the token
+    // load, then the data loads -- only the compiler has to be kept from reordering them).  One read per poll: lane l < 3 reads
+    // the token of helper wave 1 + l, the other lanes read wave 1's again, and the vote passes once all three are posted.
     const int want = (split_seq << 1) | 1 | SCHUR_SPLIT_BIT;
-#pragma unroll 1
-    for (int w = 1; w <= 3; w++) {
+    const int tw = (FS_FLAG + 1 + (lane < 3 ? lane : 0)) * 64;
+    {
       SPIN_GUARD_INIT();
-      while (__float_as_int(*(volatile float*)(sh + (FS_FLAG + w) * 64)) != want) { __builtin_amdgcn_s_sleep(1); SPIN_GUARD(dbg_cnt, 1, split_seq); }
+      while (!__all(lds_tok_load(sh, tw) == want)) { __builtin_amdgcn_s_sleep(1); SPIN_GUARD(dbg_cnt, 1, split_seq); }
     }
     asm volatile("" ::: "memory");
     st.mark<SG_SCHUR>(A, N, 0, e, SCHUR_TOKENS);   // tokens seen
@@ -903,16 +920,10 @@ DI void schur_base(const Arena& A, const DevParams* __restrict__ P, const BaseCh
       bias[j] = j < 3 ? dot(B.ab[j], ff) : dot(B.ab[j], nn);
     }
   }
-  {
 #pragma unroll
-    for (int i = 0; i < 6; i++) {
-      const float kp = P->jc[i].kp, kdh = P->jc[i].kd + h * kp;
-      S[i * 6 + i] += P->jc[i].armature + h * kdh;
-      // fused sub-step: the base targets were staged in LDS by wave 5 (a global load here would first have to wait for
-      // this wave's own factor stores of phase 1 to drain)
-      const float tgt = tgt_lds >= 0 ? SH(tgt_lds + i) : FLD(targets, i);
-      tauB[i] = kp * (tgt - B.qb[i]) - kdh * B.qdb[i] - bias[i] - gsum[i];
-    }
+  for (int i = 0; i < 6; i++) {
+    S[i * 6 + i] += dgn[i];
+    tauB[i] = tauB[i] - bias[i] - gsum[i];
   }
   st.mark<SG_SCHUR>(A, N, 0, e, SCHUR_S_TAUB);   // S, tau_B complete
   if (solve_only) {
@@ -2544,6 +2555,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
     bool box_conv = false;   // (wave-uniform) a whole pass changed no impulse in any lane: the remaining passes are no-ops
     f2 sv01 = {bv[0], bv[1]}, sv23 = {bv[2], bv[3]}, sv45 = {bv[4], bv[5]};
     const int it_split = (C.num_position_iterations * SPEC_SPLIT_NUM) >> 4;   // sweeps next to the finger dynamics of phase 1
+    const int tokw = (FS_FLAG + (lane < 6 ? lane : 0)) * 64;   // one token per lane: lane w < 6 reads wave w's, the others wave 0's again
     if (has_box) {
       int km = nc;
 #pragma unroll
@@ -2554,7 +2566,8 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
       // box wave the last to reach the phase-1 barrier by ~2.7k cycles)
 #pragma unroll 1
       for (int it = 0; it < it_split && !box_conv; it++) {
-        const int tokv = __float_as_int(*(volatile float*)(sh + (FS_FLAG + (lane < 6 ? lane : 0)) * 64));
+        // (the read is issued here and looked at behind the sweep, which works in VGPRs: the LDS round trip is off the sweep's path)
+        const int tokv = lds_tok_load(sh, tokw);
         box_conv = !__any(sb.sweep(sv01, sv23, sv45));
         if (__any((tokv >> 1) == seq && !(tokv & 1))) break;
       }
@@ -2563,17 +2576,12 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
         // The spin is safe because the seven waves of a workgroup are always co-resident: a workgroup is placed on a CU as
         // a whole (448 threads = 7 waves, __launch_bounds__(448); FS_LDS_BYTES = 160 KiB of LDS => one workgroup per CU), and
         // the waves being waited for never wait for this one before they post their token.
-      hand_free = true;
-#pragma unroll 1
-      for (int w = 0; w < 6; w++) {
-        int tok;
-        SPIN_GUARD_INIT();
-        do {
-          tok = __float_as_int(*(volatile float*)(sh + (FS_FLAG + w) * 64));
-          if ((tok >> 1) != seq) { __builtin_amdgcn_s_sleep(2); SPIN_GUARD(cnt, 2, seq); }
-        } while ((tok >> 1) != seq);
-        hand_free = hand_free && (tok & 1) != 0;
-      }
+        // One LDS read per poll: the six tokens in six lanes (tokw), a vote on "all posted", and the verdict is the AND of the
+        // six clear bits of that same read.
+      int tok;
+      SPIN_GUARD_INIT();
+      while (tok = lds_tok_load(sh, tokw), !__all((tok >> 1) == seq)) { __builtin_amdgcn_s_sleep(2); SPIN_GUARD(cnt, 2, seq); }
+      hand_free = __all((tok & 1) != 0);
     }
     if (LAST && hand_free) FLD(ncontact, 0) = nc;
     SH(DL_NC) = __int_as_float(nc | (nbg << 8));
@@ -2601,9 +2609,8 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   // Hand clear of box and ground in the whole workgroup and at most 4 box/ground contacts per env: the box and the
   // hand are dynamically decoupled in this sub-step, so wave 5 solves the box/ground contacts (rows it built itself in
   // phase 1) WHILE wave 0 reduces the Schur complement; phases 3 and 4 and their barriers disappear.
-  int clear_mask = 0;   // bit w: wave w's part of the hand cannot touch anything in this sub-step
-#pragma unroll
-  for (int w = 0; w < 6; w++) clear_mask |= (__float_as_int(sh[(FS_FLAG + w) * 64]) & 1) << w;
+  // bit w: wave w's part of the hand cannot touch anything in this sub-step (one read, lane w < 6 of token w, and a ballot of bit 0)
+  const int clear_mask = (int)(__ballot(lds_tok_load(sh, (FS_FLAG + (lane < 6 ? lane : 0)) * 64) & 1) & 63);
   hand_free = clear_mask == 63;
   const bool early = hand_free;
 
@@ -2612,7 +2619,7 @@ DI void substep_body(const Arena& A, const ApiPtrs& T, const DevParams* __restri
   if (early && wv >= 1 && wv <= 3) {   // SCHUR_SPLIT: shares of the Schur phase on three of the waves that would wait at the barrier
     schur_helper(sh, dlb, wv - 1, lane);
     asm volatile("" ::: "memory");
-    if (lane == 0) *(volatile float*)(sh + (FS_FLAG + wv) * 64) = __int_as_float((seq << 1) | 1 | SCHUR_SPLIT_BIT);
+    if (lane == 0) lds_tok_store(sh, (FS_FLAG + wv) * 64, (seq << 1) | 1 | SCHUR_SPLIT_BIT);   // a ds_write behind the data's ds_writes
   }
   if (wv == 0) {
     schur_base(A, P, B, sh, dlb, uB, lane, N, e, FS_TGTB, early, early ? seq : 0, st, cnt);
