@@ -373,4 +373,15 @@ def build_sim_config(cfg, model=None, dr=None):
         c.dr_mass_lo, c.dr_mass_hi = [float(x) for x in dr["mass"]]
         c.dr_mu_lo, c.dr_mu_hi = [float(x) for x in dr["friction"]]
         c.dr_seed = int(dr.get("seed", 4242)) & 0xFFFFFFFF
+        # what dexsim_create refuses (the draw reaches 1 / box_mass and the friction cones), on the float32 values it will see
+        for name in ("mass", "mu"):
+            lo, hi = getattr(c, f"dr_{name}_lo"), getattr(c, f"dr_{name}_hi")
+            if not (math.isfinite(lo) and math.isfinite(hi)):
+                raise ValueError(f"dr_{name}_lo / dr_{name}_hi must be finite, got {lo}, {hi}")
+            if lo > hi:
+                raise ValueError(f"dr_{name}_lo = {lo} exceeds dr_{name}_hi = {hi}")
+        if not c.dr_mass_lo > 0.0:
+            raise ValueError(f"dr_mass_lo must be positive, got {c.dr_mass_lo}")
+        if c.dr_mu_lo < 0.0:
+            raise ValueError(f"dr_mu_lo must not be negative, got {c.dr_mu_lo}")
     return c, model

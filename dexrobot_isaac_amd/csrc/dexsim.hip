@@ -159,6 +159,16 @@ int dexsim_create(const DexSimConfig* cfg, const DexHandModel* model, int device
     return fail(DEXSIM_ERR_ARG, "dexsim_create: num_actions inconsistent with policy_controls_*");
   if (cfg->has_box && !(cfg->box_size > 0.f && (cfg->box_mass > 0.f || cfg->box_fixed))) return fail(DEXSIM_ERR_ARG, "dexsim_create: bad box");
   if (cfg->box_fixed && !cfg->has_box) return fail(DEXSIM_ERR_ARG, "dexsim_create: box_fixed needs has_box");
+  if (cfg->dr_enabled) {   // the per-env draw reaches 1 / box_mass and the friction cones unchecked
+    if (!std::isfinite(cfg->dr_mass_lo) || !std::isfinite(cfg->dr_mass_hi))
+      return fail(DEXSIM_ERR_ARG, "dexsim_create: dr_mass_lo / dr_mass_hi must be finite");
+    if (!std::isfinite(cfg->dr_mu_lo) || !std::isfinite(cfg->dr_mu_hi))
+      return fail(DEXSIM_ERR_ARG, "dexsim_create: dr_mu_lo / dr_mu_hi must be finite");
+    if (!(cfg->dr_mass_lo > 0.f)) return fail(DEXSIM_ERR_ARG, "dexsim_create: dr_mass_lo must be positive");
+    if (cfg->dr_mass_lo > cfg->dr_mass_hi) return fail(DEXSIM_ERR_ARG, "dexsim_create: dr_mass_lo exceeds dr_mass_hi");
+    if (cfg->dr_mu_lo < 0.f) return fail(DEXSIM_ERR_ARG, "dexsim_create: dr_mu_lo must not be negative");
+    if (cfg->dr_mu_lo > cfg->dr_mu_hi) return fail(DEXSIM_ERR_ARG, "dexsim_create: dr_mu_lo exceeds dr_mu_hi");
+  }
   {
     int tot = 0;
     for (int s = 0; s < cfg->n_obs_seg; s++) {

@@ -233,7 +233,9 @@ typedef struct DexSimConfig {
   float first_three_height_consistency_decay, fingerpad_proximity_decay, base_stability_decay;
   float geometric_penetration_factor, proximity_min_distance_factor, penetration_depth_scale;
   float height_tolerance, centroid_tolerance, position_drift_tolerance, velocity_tolerance;
-  /* per-env domain randomisation of the box (BASELINE config #5; new capability) */
+  /* per-env domain randomisation of the box (BASELINE config #5; new capability).  With dr_enabled every env draws its mass from
+   * [dr_mass_lo, dr_mass_hi] and its friction from [dr_mu_lo, dr_mu_hi] once, at create; dexsim_create refuses (DEXSIM_ERR_ARG)
+   * dr_mass_lo <= 0, dr_mu_lo < 0, lo > hi and non-finite bounds. */
   int   dr_enabled;
   float dr_mass_lo, dr_mass_hi, dr_mu_lo, dr_mu_hi;
   uint32_t dr_seed;

@@ -1159,7 +1159,20 @@ static void reset_observer_env(OrcEnv* e) { /* observation_encoder.py:363-383 */
 #define PAR_FOR
 #endif
 
+/* What dexsim_create refuses of the randomisation ranges, in its words: NULL for a configuration both sides accept. */
+const char* orc_config_error(const DexSimConfig* cfg) {
+  if (!cfg->dr_enabled) return NULL;
+  if (!isfinite(cfg->dr_mass_lo) || !isfinite(cfg->dr_mass_hi)) return "dr_mass_lo / dr_mass_hi must be finite";
+  if (!isfinite(cfg->dr_mu_lo) || !isfinite(cfg->dr_mu_hi)) return "dr_mu_lo / dr_mu_hi must be finite";
+  if (!(cfg->dr_mass_lo > 0.f)) return "dr_mass_lo must be positive";
+  if (cfg->dr_mass_lo > cfg->dr_mass_hi) return "dr_mass_lo exceeds dr_mass_hi";
+  if (cfg->dr_mu_lo < 0.f) return "dr_mu_lo must not be negative";
+  if (cfg->dr_mu_lo > cfg->dr_mu_hi) return "dr_mu_lo exceeds dr_mu_hi";
+  return NULL;
+}
+
 void* orc_create(const DexSimConfig* cfg, const DexHandModel* model) {
+  if (orc_config_error(cfg)) return NULL;
   Oracle* o = (Oracle*)calloc(1, sizeof(Oracle));
   o->cfg = *cfg; o->model = *model; o->n = cfg->num_envs;
   o->env = (OrcEnv*)calloc((size_t)o->n, sizeof(OrcEnv));

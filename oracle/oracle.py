@@ -47,6 +47,8 @@ def _load(f64=False):
     lib.orc_field_rows.argtypes = [C.c_char_p]
     lib.orc_get_contacts.argtypes = [vp, C.c_int, vp]
     lib.orc_any_reset.argtypes = [vp]
+    lib.orc_config_error.restype = C.c_char_p
+    lib.orc_config_error.argtypes = [vp]
     lib.orc_field_name.restype = C.c_char_p
     lib.orc_field_name.argtypes = [C.c_int]
     return lib
@@ -62,13 +64,16 @@ class Oracle:
         self.num_obs = sim_cfg.num_obs
         self.num_actions = sim_cfg.num_actions
         self.h = self.lib.orc_create(C.byref(sim_cfg), C.byref(model_struct))
+        if not self.h:                               # what dexsim_create refuses, the oracle refuses
+            raise ValueError("orc_create: " + (self.lib.orc_config_error(C.byref(sim_cfg)) or b"failed").decode())
         if threads:
             self.lib.orc_set_threads(self.h, threads)
         self.lib.orc_init_state(self.h)
 
     def __del__(self):
         try:
-            self.lib.orc_destroy(self.h)
+            if self.h:
+                self.lib.orc_destroy(self.h)
         except Exception:
             pass
 

@@ -1,5 +1,5 @@
 """What the physics parity tests share (test_gpu_parity, test_tumbled_box, test_wide_poses, test_physics_configs, test_model_structure,
-test_contact_rich):
+test_contact_rich, test_per_env_box):
 configurations, the backends loaded with one state, snapshots, the references of the tumbled samples and the comparisons with their
 bounds.  A plain module: no fixtures, no torch at import (the HIP backend is imported where one is built).
 
@@ -9,7 +9,8 @@ entries: C_RULE E / dist + 1e-7 with E the largest err_n dist of the fp32 oracle
 error against fp64 at the 99.9th percentile and at the maximum is at most C_RULE x the fp32 oracle's own error on the same entries, plus
 the floors 1e-7 and 1e-6 (accumulate / assert_c_rule); the cached impulses of the warm-start slots enter as three more fields (box /
 ground slots that hold the same corner, hand slots and joint-limit slots valid in all three), and the set of valid hand and limit
-slots is exact.  An env that the two oracles alone decide differently (oracles_differ) is left out, within the same cap.  A helper
+slots is exact.  An env that the two oracles alone decide differently (oracles_differ), or whose free step the fp64 oracle alone shows
+to be decided by float32 roundoff (roundoff_decided), is left out, within the same cap.  A helper
 that takes a tolerance has no default for it: the tests state them."""
 import contextlib
 import functools
@@ -187,6 +188,37 @@ def tumbled_state(kind, n, seed=SEED, **cfg):
     return {k: v[:, :n].copy() for k, v in ts.sample(kind, N, seed, config=(sc, model)).items()}
 
 
+def per_env_box(state, seed=23):
+    """A copy of a sample's state with a box mass and a box friction of its own in every env: two more (1, n) rows, drawn in this
+    order from default_rng(seed) -- box_mass U(0.05, 0.2) kg, box_mu U(0.5, 1.5), the ranges of the config-5 tests -- and rounded to
+    float32 numbers, so that the fp64 oracle, the fp32 oracle and the kernels hold the same values.  load() sets them like any other
+    key; teacher_ref puts only SYNC back between sub-steps, so they stay."""
+    n = state["q"].shape[1]
+    rng = np.random.default_rng(seed)
+    box_mass = rng.uniform(0.05, 0.2, (1, n))
+    box_mu = rng.uniform(0.5, 1.5, (1, n))
+    return {**{k: v.copy() for k, v in state.items()}, "box_mass": f32(box_mass), "box_mu": f32(box_mu)}
+
+
+class Oracle32:
+    """The fp32 oracle in the kernels' place (the stand-ins of the CPU tests that show a comparison bites are its subclasses)."""
+
+    def __init__(self, sc, ms):
+        from oracle.oracle import Oracle
+        self.o, self.subs, self.taken = Oracle(sc, ms), int(sc.substeps), 0
+
+    def __getattr__(self, name):
+        return getattr(self.o, name)
+
+    def substep(self, last=True):
+        self.o.substep(last=last)
+        self.taken += 1
+
+    def physics_step(self):
+        for sub in range(self.subs):
+            self.substep(last=sub == self.subs - 1)
+
+
 # ------------------------------------------------------------------------------------------------- snapshots
 def lists(b, n):
     return [b.contacts(e).copy() for e in range(n)]
@@ -269,11 +301,15 @@ def tumbled_teacher_ref(kind, n, seed=SEED, **cfg):
 @functools.lru_cache(maxsize=None)
 def tumbled_free_ref(kind, n, steps, fields=FIELDS, seed=SEED, **cfg):
     """The tumbled sample free-running for `steps` physics steps (sim.substeps sub-steps each) on both oracles: snapshots after each."""
-    from oracle.oracle import Oracle
     sc, _, ms = setup("BlindGrasping", n, **cfg)
+    return free_run_ref(sc, ms, tumbled_state(kind, n, seed, **cfg), steps, fields)
+
+
+def free_run_ref(sc, ms, start, steps, fields=FIELDS):
+    """`start` free-running for `steps` physics steps (sim.substeps sub-steps each) on both oracles: snapshots after each."""
+    from oracle.oracle import Oracle
     o64, o32 = Oracle(sc, ms, f64=True), Oracle(sc, ms)
-    st = tumbled_state(kind, n, seed, **cfg)
-    load(o64, st), load(o32, st)
+    load(o64, start), load(o32, start)
     out = []
     for _ in range(steps):
         o64.physics_step(), o32.physics_step()
@@ -363,6 +399,52 @@ def check_manifold(b, rec, sc, ms, keep=None):
     assert entries > 3 * n
 
 
+def check_pressed_lists(make, rec, label):
+    """The backend that make() returns takes the first teacher-forced sub-step of a sample whose fingers are pressed into the box
+    (check_manifold's E / dist bound takes an axis point outside it): the list of every env entry by entry, joint-limit rows
+    included -- type and capsule / joint level exact, points, gaps and friction to 2e-6, box / ground slot corners exact; the normals
+    as one more field of the c rule.  Returns the kept envs and the lists under test."""
+    n = len(rec["lists64"])
+    keep = ~left_by_the_references([rec])
+    b = make()
+    load(b, rec["start"])
+    b.substep(last=True)
+    got = lists(b, n)
+    keep = agree(keep, rec["s64"]["ncontact"], np.array([len(c) for c in got]))
+    assert (bg_cache(b)[1][:, keep] == rec["s64"]["corner"][:, keep]).all(), "a box / ground slot holds another corner"
+    for e in np.nonzero(keep)[0]:
+        assert same_lists(rec["lists64"][e], got[e]), e
+    l64, l32, lh = (np.concatenate([l[e] for e in np.nonzero(keep)[0]]) for l in (rec["lists64"], rec["lists32"], got))
+    worst = np.abs(lh[:, [0, 1, 2, 6, 7]] - l64[:, [0, 1, 2, 6, 7]]).max()
+    print(f"\n{label}: {len(l64)} entries in {keep.sum()} envs, points / gaps / friction within {worst:.2e}")
+    np.testing.assert_allclose(lh[:, [0, 1, 2, 6, 7]], l64[:, [0, 1, 2, 6, 7]], rtol=0, atol=2e-6)
+    report = {}
+    accumulate(report, "normals", l64[:, 3:6], l32[:, 3:6], lh[:, 3:6], np.ones((len(l64), 3), bool))
+    assert_c_rule(report, f"lists, {label}, n = {n}")
+    assert len(l64) > 10 * n
+    return keep, got
+
+
+def expected_friction(c, e, start, sc, ms):
+    """The friction column of env e's list `c` as the specification has it, from the state's own box_mu row (the configuration's
+    box_friction without one): the mean of the two surfaces' coefficients -- hand / ground (type 0), hand / box (1), box / ground (2)."""
+    bmu = float(start["box_mu"][0, e]) if "box_mu" in start else float(sc.box_friction)
+    hand, ground = float(ms.hand_friction), float(sc.ground_friction)
+    return np.select([c[:, 8] == 0, c[:, 8] == 1, c[:, 8] == 2], [0.5 * (hand + ground), 0.5 * (hand + bmu), 0.5 * (bmu + ground)], np.nan)
+
+
+def check_friction_column(got, rec, keep, atol, types=(1, 2)):
+    """The friction of every hand / box (type 1) and box / ground (type 2) entry of the lists `got` against the fp64 oracle's, per
+    entry, over the envs `keep` whose lists agree entry for entry: within atol; each of `types` must occur."""
+    for typ, name in ((1, "hand / box"), (2, "box / ground")):
+        if typ not in types:
+            continue
+        err = np.concatenate([np.abs(got[e][:, 7] - rec["lists64"][e][:, 7])[rec["lists64"][e][:, 8] == typ] for e in np.nonzero(keep)[0]])
+        assert err.size > 0, name
+        print(f"friction of {err.size} {name} entries within {err.max():.2e}")
+        assert err.max() <= atol, (name, float(err.max()))
+
+
 # ------------------------------------------------------------------------------------------------- comparisons: states by the c rule
 def accumulate(report, name, ref, a32, ah, mask):
     e32, eh = np.abs(a32 - ref)[mask].ravel(), np.abs(ah - ref)[mask].ravel()
@@ -440,6 +522,47 @@ def check_free_step(sh, ref, where=""):
     for s in (ref["s64"], ref["s32"]):
         assert (sh["ncontact"] == s["ncontact"]).all(), f"contact count differs in {(sh['ncontact'] != s['ncontact']).sum()} envs{where}"
         assert (sh["corner"] == s["corner"]).all(), f"slots 80-83 differ in {(sh['corner'] != s['corner']).any(0).sum()} envs{where}"
+
+
+def roundoff_decided(sc, ms, ref, draws=8):
+    """(n,) the envs of a free_step_ref record in which float32 roundoff decides the step's result, by the two oracles alone.  The c
+    rule takes the fp32 oracle's error on an entry for what float32 roundoff does to it.  Here the fp64 oracle repeats the physics step
+    `draws` times from the start with every number of SYNC moved by a relative U(-2^-24, 2^-24), half a float32 ulp; an env is named
+    when a state field of its then spreads, at the maximum over the draws, beyond the rule's own bound for that field, C_RULE x the
+    fp32 oracle's largest error + 1e-6: there one realisation of roundoff (the fp32 oracle's) says nothing about another (a branch of
+    the solver -- a cone, a clamp, an opening contact -- is taken or not by the last bit), and no implementation in float32 can be
+    held to it.  Such an env may be left out of a comparison like one of oracles_differ, within the same cap."""
+    from oracle.oracle import Oracle
+    named = np.zeros(int(sc.num_envs), bool)
+    spread = {f: np.zeros(int(sc.num_envs)) for f in SYNC}
+    for draw in range(draws):
+        rng = np.random.default_rng(draw)
+        o = Oracle(sc, ms, f64=True)
+        load(o, {k: v * (1.0 + 2.0 ** -24 * rng.uniform(-1.0, 1.0, v.shape)) if k in SYNC else v for k, v in ref["start"].items()})
+        o.physics_step()
+        for f in SYNC:
+            spread[f] = np.maximum(spread[f], np.abs(o.get(f) - ref["s64"][f]).max(0))
+    for f in SYNC:
+        named |= spread[f] > C_RULE * np.abs(ref["s32"][f] - ref["s64"][f]).max() + 1e-6
+    return named
+
+
+def free_step_report(make, ref, exact=True):
+    """One free-running physics step of the backend that make() returns from the start of `ref` (free_step_ref) against both
+    oracles: contact counts, slot corners and valid-slot sets where the oracles agree; the report.  exact = False skips the exact
+    assertions on the output under test, for the stand-ins' margins."""
+    assert ref["left"].mean() <= LEFT_OUT, f"the oracles alone leave out {ref['left'].sum()} of {ref['left'].size} envs"
+    b = make()
+    load(b, ref["start"])
+    b.physics_step()
+    sh = snap(b)
+    same = agree(~ref["left"], ref["s64"]["ncontact"], ref["s32"]["ncontact"], sh["ncontact"], exact=exact)
+    if exact:
+        assert (sh["corner"][:, same] == ref["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
+        assert_same_slots(sh, ref["s64"], same)
+    report = {}
+    accumulate_snap(report, ref["s64"], ref["s32"], sh, same, FIELDS)
+    return report
 
 
 # ------------------------------------------------------------------------------------------------- comparisons: whole control steps

@@ -66,45 +66,13 @@ def _check_teacher(make, config):
 
 
 def _check_lists(make, config):
-    """The first sub-step's list of every env entry by entry, joint-limit rows included: type and capsule / joint level exact, points,
-    gaps and friction to 2e-6, box / ground slot corners exact; the normals as one more field of the c rule (pr.check_manifold's
-    E / dist bound takes an axis point outside the box: here fingers are pressed into it)."""
-    rec = _teacher_ref(config)[0]
-    keep = ~pr.left_by_the_references([rec])
-    b = make()
-    pr.load(b, rec["start"])
-    b.substep(last=True)
-    got = pr.lists(b, N)
-    keep = pr.agree(keep, rec["s64"]["ncontact"], np.array([len(c) for c in got]))
-    assert (pr.bg_cache(b)[1][:, keep] == rec["s64"]["corner"][:, keep]).all(), "a box / ground slot holds another corner"
-    for e in np.nonzero(keep)[0]:
-        assert pr.same_lists(rec["lists64"][e], got[e]), e
-    l64, l32, lh = (np.concatenate([l[e] for e in np.nonzero(keep)[0]]) for l in (rec["lists64"], rec["lists32"], got))
-    worst = np.abs(lh[:, [0, 1, 2, 6, 7]] - l64[:, [0, 1, 2, 6, 7]]).max()
-    print(f"\n{config}: {len(l64)} entries in {keep.sum()} envs, points / gaps / friction within {worst:.2e}")
-    np.testing.assert_allclose(lh[:, [0, 1, 2, 6, 7]], l64[:, [0, 1, 2, 6, 7]], rtol=0, atol=2e-6)
-    report = {}
-    pr.accumulate(report, "normals", l64[:, 3:6], l32[:, 3:6], lh[:, 3:6], np.ones((len(l64), 3), bool))
-    pr.assert_c_rule(report, f"lists, contact_rich, {config}, n = {N}")
-    assert len(l64) > 10 * N
+    """The first sub-step's list of every env entry by entry, joint-limit rows included (pr.check_pressed_lists)."""
+    pr.check_pressed_lists(make, _teacher_ref(config)[0], f"contact_rich, {config}")
 
 
 def _free_report(make, config, exact=True):
-    """One free-running physics step from the sample against both oracles: contact counts, slot corners and valid-slot sets where
-    the oracles agree; the report.  exact = False skips the exact assertions on the output under test, for the stand-ins' margins."""
-    ref = _free_ref(config)
-    assert ref["left"].mean() <= pr.LEFT_OUT, f"the oracles alone leave out {ref['left'].sum()} of {N} envs"
-    b = make()
-    pr.load(b, ref["start"])
-    b.physics_step()
-    sh = pr.snap(b)
-    same = pr.agree(~ref["left"], ref["s64"]["ncontact"], ref["s32"]["ncontact"], sh["ncontact"], exact=exact)
-    if exact:
-        assert (sh["corner"][:, same] == ref["s64"]["corner"][:, same]).all(), "a box / ground slot holds another corner"
-        pr.assert_same_slots(sh, ref["s64"], same)
-    report = {}
-    pr.accumulate_snap(report, ref["s64"], ref["s32"], sh, same, pr.FIELDS)
-    return report
+    """One free-running physics step from the sample against both oracles (pr.free_step_report)."""
+    return pr.free_step_report(make, _free_ref(config), exact)
 
 
 def _check_free(make, config):
@@ -151,23 +119,7 @@ def test_sample_covers_the_cases(config):
 
 
 # ------------------------------------------------------------------------------------------------- CPU: the comparison bites
-class _Oracle32:
-    """The fp32 oracle in the kernels' place."""
-
-    def __init__(self, sc, ms):
-        from oracle.oracle import Oracle
-        self.o, self.subs, self.taken = Oracle(sc, ms), int(sc.substeps), 0
-
-    def __getattr__(self, name):
-        return getattr(self.o, name)
-
-    def substep(self, last=True):
-        self.o.substep(last=last)
-        self.taken += 1
-
-    def physics_step(self):
-        for sub in range(self.subs):
-            self.substep(last=sub == self.subs - 1)
+_Oracle32 = pr.Oracle32        # the fp32 oracle in the kernels' place
 
 
 class _HandSlotsCleared(_Oracle32):

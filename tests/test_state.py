@@ -89,6 +89,45 @@ def test_state_calls_reject_null_handle_and_bad_k(lib):
     assert lib.dexsim_set_step_stamp(None, 5) == ERR_ARG and b"null handle" in lib.dexsim_last_error()
 
 
+BAD_RANGES = [        # (field: value, ...) on top of the valid ranges, and the field the refusal must name
+    ({"dr_mass_lo": 0.0}, "dr_mass_lo"), ({"dr_mass_lo": -0.05}, "dr_mass_lo"), ({"dr_mass_lo": 0.3}, "dr_mass_lo"),
+    ({"dr_mu_lo": 2.0}, "dr_mu_lo"), ({"dr_mu_lo": -0.1}, "dr_mu_lo"),
+    ({"dr_mass_lo": float("nan")}, "dr_mass_lo"), ({"dr_mass_hi": float("inf")}, "dr_mass_hi"),
+    ({"dr_mu_lo": float("nan")}, "dr_mu_lo"), ({"dr_mu_hi": float("inf")}, "dr_mu_hi"), ({"dr_mu_hi": float("nan")}, "dr_mu_hi"),
+]
+
+
+def test_bad_randomisation_ranges_are_refused(lib):
+    """With dr_enabled the draw of k_init reaches 1 / box_mass and the friction cones: dexsim_create (before any device work),
+    build_sim_config and the oracle's create refuse a mass bound <= 0, a negative friction bound, lo > hi and non-finite bounds, each
+    naming the field; a valid range, and a bad one with dr_enabled = 0, pass the argument checks (up to the missing device here)."""
+    from oracle.oracle import Oracle
+    cfg = default_cfg("BlindGrasping")
+    cfg["env"]["numEnvs"] = 4
+    good = {"mass": (0.05, 0.2), "friction": (0.5, 1.5), "seed": 4242}
+    sc, model = build_sim_config(cfg, dr=good)
+    ms = model.to_struct()
+    ERR_ARG, ERR_NO_DEVICE = 1, lib.dexsim_create(C.byref(sc), C.byref(ms), 1 << 20, C.byref(C.c_void_p()))
+    assert ERR_NO_DEVICE != ERR_ARG and b"dr_" not in lib.dexsim_last_error()      # no such device: past every argument check
+    for edit, field in BAD_RANGES:
+        bad, _ = build_sim_config(cfg, dr=good)
+        for k, v in edit.items():
+            setattr(bad, k, v)
+        h = C.c_void_p()
+        assert lib.dexsim_create(C.byref(bad), C.byref(ms), 1 << 20, C.byref(h)) == ERR_ARG and not h.value, edit
+        assert field.encode() in lib.dexsim_last_error(), (edit, lib.dexsim_last_error())
+        with pytest.raises(ValueError, match=field):
+            Oracle(bad, ms)
+        dr = {"mass": (bad.dr_mass_lo, bad.dr_mass_hi), "friction": (bad.dr_mu_lo, bad.dr_mu_hi)}
+        with pytest.raises(ValueError, match=field):
+            build_sim_config(cfg, dr=dr)
+        bad.dr_enabled = 0                                    # the bounds are not read then
+        assert lib.dexsim_create(C.byref(bad), C.byref(ms), 1 << 20, C.byref(h)) == ERR_NO_DEVICE
+    degenerate, _ = build_sim_config(cfg, dr={"mass": (0.1, 0.1), "friction": (0.0, 0.0)})       # lo == hi, mu = 0: a configuration
+    assert lib.dexsim_create(C.byref(degenerate), C.byref(ms), 1 << 20, C.byref(C.c_void_p())) == ERR_NO_DEVICE
+    assert Oracle(degenerate, ms).get("box_mass").min() > 0
+
+
 def _hand_built_state(**kw):
     g = torch.Generator().manual_seed(1)
     d = dict(version=_abi.STATE_VERSION, record_words=7, num_envs=3, config_hash="ab" * 32, capacity=64, stamp=41,
@@ -189,12 +228,15 @@ def _set_clocks(core, k):
     core.field("time_in_stage")[0, : len(k)] = kt.to(torch.float32) * float(core.cfg.control_dt)
 
 
-def _proto_core(n, seed):
+DR = {"mass": (0.05, 0.2), "friction": (0.5, 1.5), "seed": 4242}      # a box mass and friction of its own per env (config 5)
+
+
+def _proto_core(n, seed, dr=None):
     """Protocol P on a bare DexSimCore; returns (core, rng)."""
     from dexrobot_isaac_amd.core import DexSimCore
     cfg = _proto_cfg()
     cfg["env"]["numEnvs"] = n
-    sc, model = build_sim_config(cfg)
+    sc, model = build_sim_config(cfg, dr=dr)
     core = DexSimCore(sc, model.to_struct(), DEV)
     rng = np.random.default_rng(seed)
     core.set_reset_samples(_proto_samples(rng, n))
@@ -203,8 +245,8 @@ def _proto_core(n, seed):
     return core, rng
 
 
-def _proto_env(n, seed, obs_dict="all"):
-    env = make_env("BlindGrasping", n, DEV, DEV, 0, cfg=_proto_cfg(obs_dict))
+def _proto_env(n, seed, obs_dict="all", dr=None):
+    env = make_env("BlindGrasping", n, DEV, DEV, 0, cfg=_proto_cfg(obs_dict), domain_randomisation=dr)
     rng = np.random.default_rng(seed)
     env._core.set_reset_samples(_proto_samples(rng, n))
     env.reset()
@@ -367,15 +409,12 @@ def test_indexed_save_load_touch_exactly_their_envs():
     assert rc == 1 and b"bank is NULL" in core.lib.dexsim_last_error()
 
 
-@pytest.mark.gpu
-def test_fork_of_a_whole_workgroup_continues_bitwise():
-    """C1: workgroup 0 copied onto workgroup 1 in lane order, then driven by the same actions and the same injected reset
-    samples: env i + 64 equals env i on every record word and API row for 16 steps."""
+def _fork_of_a_whole_workgroup(dr):
     n = 128
     from dexrobot_isaac_amd.core import DexSimCore
     cfg = _proto_cfg()
     cfg["env"]["numEnvs"] = n
-    sc, model = build_sim_config(cfg)
+    sc, model = build_sim_config(cfg, dr=dr)
     core = DexSimCore(sc, model.to_struct(), DEV)
     rng = np.random.default_rng(5)
     u = _proto_samples(rng, 64)
@@ -383,6 +422,9 @@ def test_fork_of_a_whole_workgroup_continues_bitwise():
     core.reset()
     _set_clocks(core, rng.integers(0, 199, 64))
     src, dst = torch.arange(64), torch.arange(64, 128)
+    if dr:                                                   # every lane's destination holds another box before the fork
+        for f in ("box_mass", "box_mu"):
+            assert bool((core.field(f)[0, :64] != core.field(f)[0, 64:128]).all()), f
     core.copy_envs(src, dst)
     hand, resets = [], 0
     for t in range(16):
@@ -395,6 +437,13 @@ def test_fork_of_a_whole_workgroup_continues_bitwise():
         resets += int(core.reset_buf[:64].sum())
     print("C1: hand contacts/env per step", hand, "resets of the sources", resets)
     assert min(hand) >= 0.2 and resets >= 2
+
+
+@pytest.mark.gpu
+def test_fork_of_a_whole_workgroup_continues_bitwise():
+    """C1: workgroup 0 copied onto workgroup 1 in lane order, then driven by the same actions and the same injected reset
+    samples: env i + 64 equals env i on every record word and API row for 16 steps."""
+    _fork_of_a_whole_workgroup(None)
 
 
 @pytest.mark.gpu
@@ -423,6 +472,112 @@ def test_scattered_fork_and_its_precondition():
     env.fork_envs([5], [6], check=False)
     assert torch.equal(core.obs_buf[5], core.obs_buf[6])
     _assert_only_envs_changed(core, after, _snapshot(core), [6])
+
+
+# ------------------------------------------------------------------------------------- the record carries the env's box (include/dexsim.h)
+def _box_rows(core, envs=slice(None)):
+    torch.cuda.synchronize()
+    return torch.stack([core.field("box_mass")[0, envs], core.field("box_mu")[0, envs]]).clone()
+
+
+@pytest.mark.gpu
+def test_fork_of_a_whole_workgroup_takes_the_sources_boxes():
+    """C1 with a box mass and friction of its own per env: a copy_envs that left the two rows behind would let every destination
+    step on with its own box, and env i + 64 would leave env i in the first sub-step with a contact."""
+    _fork_of_a_whole_workgroup(DR)
+
+
+@pytest.mark.gpu
+def test_scattered_fork_takes_the_sources_boxes():
+    """C2's scattered fork_envs across workgroups, per-env boxes: the destinations hold their sources' mass and friction (other
+    numbers than before), every record word of the source, and nothing else changes."""
+    n = 200
+    env, rng = _proto_env(n, 3, dr=DR)
+    core = env._core
+    for _ in range(2):
+        env.step(_actions(rng, n))
+    src, dst = [5, 69, 5], [100, 1, 130]
+    before = _snapshot(core)
+    box = _box_rows(core)
+    assert bool((box[:, src] != box[:, dst]).all())
+    env.fork_envs(src, dst)
+    after = _snapshot(core)
+    assert torch.equal(_box_rows(core, dst), box[:, src])
+    for x, y in zip(_env_words(core, before, src), _env_words(core, after, dst)):
+        assert torch.equal(x, y)
+    _assert_only_envs_changed(core, before, after, dst)
+
+
+@pytest.mark.gpu
+def test_restore_into_an_instance_with_another_draw_continues_bit_for_bit():
+    """A with per-env boxes, n = 130: a full snapshot restored into a fresh instance created with another dr_seed -- whose own boxes
+    differ in every env -- replays 12 steps of protocol P like the source, on every statistic and every word of every record."""
+    from dexrobot_isaac_amd.core import DexSimCore
+    n = 130
+    core, rng = _proto_core(n, 3, dr=DR)
+    core.set_reset_samples(None)
+    for _ in range(5):
+        core.step(_actions(rng, n))
+    bank = core.state_bank(core.NS)
+    core.save_state(bank)
+    stats, counters, stamp = core.stats.clone(), core.counters.clone(), core.get_step_stamp()
+    box = _box_rows(core)
+    acts = [_actions(rng, n) for _ in range(12)]
+
+    def run(c):
+        out = []
+        for a in acts:
+            c.step(a)
+            torch.cuda.synchronize()
+            out.append([c.stats.clone()] + _record_of(c, _snapshot(c)))
+        return out
+
+    ref = run(core)
+    assert torch.equal(_box_rows(core), box)                 # (the steps and their resets leave the boxes alone)
+    cfg = _proto_cfg()
+    cfg["env"]["numEnvs"] = n
+    sc, model = build_sim_config(cfg, dr={**DR, "seed": 99})
+    fresh = DexSimCore(sc, model.to_struct(), DEV)
+    fresh.reset()
+    assert bool((_box_rows(fresh) != box).all())
+    fresh.load_state(bank)
+    fresh.stats.copy_(stats)
+    fresh.counters.copy_(counters)
+    fresh.set_step_stamp(stamp)
+    assert torch.equal(_box_rows(fresh), box)
+    for t, (r, g) in enumerate(zip(ref, run(fresh))):
+        for i, (x, y) in enumerate(zip(r, g)):
+            assert x.dtype == y.dtype and torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x,
+                                                      y.view(torch.int32) if y.dtype == torch.float32 else y), (t, i)
+    hand = [float(r[0][_abi.STAT["MEAN_HAND_CONTACTS"]]) for r in ref]
+    print("per-env boxes: hand contacts/env per step", hand)
+    assert min(hand) > 0.0                                   # hands on boxes in every step: mass and friction entered the contact rows
+
+
+@pytest.mark.gpu
+def test_indexed_load_into_other_lanes_brings_the_boxes():
+    """B with per-env boxes: four records saved from envs a, loaded into other lanes b (both workgroups, the padded one's first and
+    last live lane among them): env b then holds env a's mass and friction and every other record word of a at the save, and nothing
+    else changes."""
+    n = 70
+    core, rng = _proto_core(n, 3, dr=DR)
+    for _ in range(3):
+        core.step(_actions(rng, n))
+    a, slots, b = [69, 3, 64, 0], [5, 0, 2, 7], [1, 68, 65, 40]
+    bank = core.state_bank(8)
+    core.save_state(bank, env_ids=torch.tensor(a), slots=torch.tensor(slots))
+    first, box = _snapshot(core), _box_rows(core)
+    assert bool((box[:, a] != box[:, b]).all())
+    assert torch.equal(bank.section("box_mass")[0, slots], box[0, a]) and torch.equal(bank.section("box_mu")[0, slots], box[1, a])
+    for _ in range(3):
+        core.step(_actions(rng, n))
+    before = _snapshot(core)
+    core.load_state(bank, env_ids=torch.tensor(b), slots=torch.tensor(slots))
+    after = _snapshot(core)
+    assert torch.equal(_box_rows(core, b), box[:, a])
+    for x, y in zip(_env_words(core, first, a), _env_words(core, after, b)):
+        assert torch.equal(x, y)
+    _assert_only_envs_changed(core, before, after, b)
 
 
 def _same(a, b, path="extras"):
