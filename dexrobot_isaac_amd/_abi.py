@@ -44,6 +44,8 @@ RENDER_MAX_DIM = 4096
 RCAP = dict(A=0, R=3, B=4, LEN=7, U=8, UO=11, O=12, INVR=15, N=16, CA=19, CB=20, LO=21, LU=22, R2=23)
 RCAP_WORDS = 24
 SCENE_WORDS = 52 + NCAP * RCAP_WORDS
+RAY_MAX = 4096        # DEXSIM_RAY_MAX: rays per dexsim_raycast call
+RAY_SKIP_PARENT = 1   # DEXSIM_RAY_SKIP_PARENT: a ray mounted on joint frame j does not test the capsules with cap_parent == j
 
 f32, i32, u32 = C.c_float, C.c_int, C.c_uint32
 
@@ -199,11 +201,16 @@ EXPORTED_SYMBOLS = list(PROTOTYPES)
 FK_PROTOTYPES = {
     "dexsim_forward_kinematics": [vp, vp, i32, vp, vp, P(i32), i32, i32, vp, vp, vp, vp],
 }
-ALL_PROTOTYPES = {**PROTOTYPES, **FK_PROTOTYPES}   # every entry point of the library: what the loader checks and declares
+# the entry point include/dexsim_ray.h declares, a part of the header like dexsim_fk.h (tests/test_raycast.py holds this table against
+# that file and the built library)
+RAY_PROTOTYPES = {
+    "dexsim_raycast": [vp, vp, i32, vp, vp, f32, vp, P(i32), i32, f32, f32, i32, vp, vp, vp],
+}
+ALL_PROTOTYPES = {**PROTOTYPES, **FK_PROTOTYPES, **RAY_PROTOTYPES}   # every entry point of the library: what the loader checks and declares
 
 
 def declare_prototypes(lib):
-    """Attach argtypes/restype for every entry point of include/dexsim.h and include/dexsim_fk.h to a loaded CDLL."""
+    """Attach argtypes/restype for every entry point of include/dexsim.h and its parts dexsim_fk.h and dexsim_ray.h to a loaded CDLL."""
     for name, argtypes in ALL_PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, i32

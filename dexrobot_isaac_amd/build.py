@@ -9,15 +9,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdexsim.so")
 ABI_HEADER = os.path.join(HERE, "..", "include", "dexsim.h")
-ABI_PARTS = ["dexsim_fk.h"]   # the files next to ABI_HEADER that it includes
+ABI_PARTS = ["dexsim_fk.h", "dexsim_ray.h"]   # the files next to ABI_HEADER that it includes
 _SHARED = ["dexsim_device.h", "dexsim_host.h"]
 # The library's two translation units, in link order: name -> (source, the files of csrc/ that its compile reads besides).  Neither
 # includes a .hip.inc of the other: the step kernels' code cannot depend on a query file, and a query edit does not recompile them.
 SOURCES = {
     "step": ("dexsim.hip", [*_SHARED, "dexsim_stamps.h", "dexsim_physics.hip.inc", "dexsim_l2.hip.inc", "dexsim_state.hip.inc"]),
     "queries": ("dexsim_queries.hip", [*_SHARED, "dexsim_chain.hip.inc", "dexsim_render.hip.inc", "dexsim_kindyn.hip.inc",
-                                       "dexsim_ik.hip.inc", "dexsim_proximity.hip.inc", "dexsim_invdyn.hip.inc",
-                                       "dexsim_fk.hip.inc", "dexsim_fwddyn.hip.inc", "dexsim_dynderiv.hip.inc"]),
+                                       "dexsim_ik.hip.inc", "dexsim_proximity.hip.inc", "dexsim_raycast.hip.inc",
+                                       "dexsim_invdyn.hip.inc", "dexsim_fk.hip.inc", "dexsim_fwddyn.hip.inc",
+                                       "dexsim_dynderiv.hip.inc"]),
 }
 
 

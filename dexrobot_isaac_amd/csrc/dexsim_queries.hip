@@ -1,6 +1,7 @@
 // dexsim_queries.hip -- libdexsim's query unit: the C-ABI (include/dexsim.h) of the queries on a simulation's state -- camera
-// sensors, Jacobians and mass matrix, inverse kinematics, clearances, inverse dynamics, forward kinematics, forward dynamics and the
-// dynamics derivatives -- over their gfx950 kernels (dexsim_chain, _render, _kindyn, _ik, _proximity, _invdyn, _fk, _fwddyn, _dynderiv).
+// sensors, Jacobians and mass matrix, inverse kinematics, clearances, range sensors, inverse dynamics, forward kinematics, forward
+// dynamics and the dynamics derivatives -- over their gfx950 kernels (dexsim_chain, _render, _kindyn, _ik, _proximity, _raycast, _invdyn,
+// _fk, _fwddyn, _dynderiv).
 //
 // The library's second translation unit (build: see dexsim.hip).  It includes none of the step unit's .hip.inc files and the step
 // unit none of these; from the step side it takes the declarations of dexsim_device.h and the handle of dexsim_host.h, nothing
@@ -241,6 +242,55 @@ extern "C" int dexsim_query_proximity(dexsim_t h, const int64_t* env_ids, int k,
   K.hb = 0.5f * size;
   K.cap_env = cap_env; K.self_min = self_min; K.pair_dist = pair_dist;
   KIN_LAUNCH(k_proximity, 1, K);
+  return DEXSIM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- range sensors
+// Behind the clearances: the rows and the box of a call are theirs.
+// clang-format off
+#include "dexsim_raycast.hip.inc"
+// clang-format on
+
+extern "C" int dexsim_raycast(dexsim_t h, const int64_t* env_ids, int k, const float* q, const float* box_pose, float box_size,
+                              const float* rays, const int* parent, int nrays, float min_range, float max_range, int flags,
+                              float* dist, float* hits, void* stream) {
+  // the checks of the ray list, the window, the flags, the outputs, of box_size and of k need neither a handle nor a device
+  if (nrays < 1 || nrays > DEXSIM_RAY_MAX) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: nrays must be in [1, DEXSIM_RAY_MAX]");
+  if (!rays || !parent) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: rays and parent are required");
+  RayArgs K;
+  std::memset(&K, 0, sizeof K);
+  for (int i = 0, j = -1; i <= nrays; i++) {   // the prefix offsets of the parent groups
+    const int p = i < nrays ? parent[i] : DEXSIM_NJ;
+    if (i < nrays && (p < -1 || p >= DEXSIM_NJ)) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: a parent is outside [-1, DEXSIM_NJ)");
+    if (p < j) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: parent must be non-decreasing (sort the rays by parent)");
+    if (i == 0) K.jstart[0] = 0;
+    for (; j < p; j++) K.jstart[j + 2] = (unsigned short)i;   // group j ends, group j + 1 begins at ray i
+  }
+  if (!std::isfinite(min_range) || !std::isfinite(max_range) || min_range < 0.f || !(min_range < max_range))
+    return fail(DEXSIM_ERR_ARG, "dexsim_raycast: the ranges must be finite with 0 <= min_range < max_range");
+  if ((flags & ~DEXSIM_RAY_SKIP_PARENT) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: unknown flag bits (DEXSIM_RAY_SKIP_PARENT is the only flag)");
+  if (!dist && !hits) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: at least one of dist and hits is required");
+  if (((uintptr_t)dist & 15) != 0 || ((uintptr_t)hits & 15) != 0) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: the outputs must be 16-byte aligned");
+  if (!std::isfinite(box_size)) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: box_size is not finite");
+  if (k <= 0) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: k must be positive");
+  int rc = kin_rows("dexsim_raycast", h, env_ids, k, q, &K.rows);
+  if (rc) return rc;
+  if (flags & DEXSIM_RAY_SKIP_PARENT)
+    for (int c = 0; c < DEXSIM_NCAP; c++) {
+      const int p = h->model.cap_parent[c];
+      if (p < 0 || p >= DEXSIM_NJ) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: DEXSIM_RAY_SKIP_PARENT needs every model.cap_parent in [0, DEXSIM_NJ)");
+      K.skip[p] |= 1u << c;
+    }
+  const float size = box_size > 0.f ? box_size : h->cfg.box_size;
+  K.box_pose = box_pose;
+  K.box_env = !box_pose && !q && h->cfg.has_box;
+  if ((K.box_pose || K.box_env) && !(size > 0.f)) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: a box needs a positive box_size or cfg.box_size");
+  NEED_BOUND(h);
+  K.hb = 0.5f * size;
+  K.rays = rays; K.nrays = nrays;
+  K.tmin = min_range; K.tmax = max_range;
+  K.dist = dist; K.hits = hits;
+  KIN_LAUNCH(k_raycast, (nrays + RC_CHUNK - 1) / RC_CHUNK, K);
   return DEXSIM_OK;
 }
 

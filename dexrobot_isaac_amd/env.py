@@ -410,6 +410,7 @@ class DexHandEnv(EnvQueries):
         # creates the reference's fixed "video" camera, placed as VideoManager._position_camera places it
         # (video_manager.py:100-147): 75 deg, behind env 0, looking at the hand.
         self._cameras = {}
+        self._ray_sensors = {}     # range sensors (create_ray_sensor)
         if video_config and video_config.get("resolution") is not None:
             w, h = (int(v) for v in video_config["resolution"])
             back = max(1.5, 0.75 * float(self.env_cfg["envSpacing"]))

@@ -1,15 +1,17 @@
 """The query surface: everything that reads or copies simulation state outside the control step -- state records (save, load,
 fork), camera sensors, Jacobians and mass matrix, inverse dynamics, forward kinematics, forward dynamics and the dynamics
-derivatives, fingertip IK, clearances.
+derivatives, fingertip IK, clearances, range sensors.
 
 Two levels, in the same family order.  CoreQueries, a base class of DexSimCore, is the ctypes level: one C-ABI call per method
 on caller-owned device tensors, DexSimError on a bad argument.  EnvQueries, a base class of DexHandEnv, is the user level: it
 accepts lists, names and arrays, allocates the outputs and raises ValueError.  The argument rules that every call repeats are
 written once, at the top of this file and at the top of each class.  A new query adds a method to each class (and its row to
-_abi.PROTOTYPES, or to _abi.FK_PROTOTYPES for include/dexsim_fk.h); nothing else."""
+_abi.PROTOTYPES, or to the table of the header part that declares it: _abi.FK_PROTOTYPES for include/dexsim_fk.h, _abi.RAY_PROTOTYPES
+for include/dexsim_ray.h); nothing else."""
 import ctypes as C
 import hashlib
 
+import numpy as np
 import torch
 
 from . import _abi
@@ -379,6 +381,33 @@ class CoreQueries:
         self._keep_prox = box_pose                  # alive until the kernel ran
         check(self.lib.dexsim_query_proximity(self.h, ids, k, qp, bp, float(box_size), cp, sp, pp, self._stream()), "query_proximity")
 
+    # ------------------------------------------------------------------ range sensors (dexsim_raycast)
+    def raycast(self, dist=None, hits=None, rays=None, parent=None, env_ids=None, q=None, box_pose=None, box_size=0.0, min_range=0.0,
+                max_range=1.0, skip_parent=False):
+        """Cast the rays `rays` (R, 6) f32 on this device -- origin and direction in the parent frame, shared by all rows -- against
+        the ground, the box and the hand's capsules in one launch: `dist` (k, R) f32 = metres along the unit direction, +inf without
+        a hit; `hits` (k, R, 8) f32 = t, hit point (3), outward unit normal (3), segment id as int32 bits.  Either may be None, not
+        both.  parent: a host sequence of R ints, -1 = the env's world frame or a joint index, non-decreasing.  A hit counts inside
+        [min_range, max_range]; skip_parent: a ray on joint frame j does not test the capsules that ride on j.  Rows and the box as
+        for proximity.  dexsim_raycast."""
+        what = "raycast"
+        if dist is None and hits is None:
+            raise DexSimError(f"{what}: at least one of dist and hits is required")
+        if rays is None or parent is None:
+            raise DexSimError(f"{what}: rays and parent are required")
+        pl = [int(p) for p in parent]
+        R = len(pl)
+        if not 1 <= R <= _abi.RAY_MAX:
+            raise DexSimError(f"{what}: between 1 and {_abi.RAY_MAX} rays, got {R}")
+        ids, qp, k = self._kin_rows(what, env_ids, q)
+        rp = self._req(what, "rays", rays, (R, 6))
+        bp = self._opt(what, "box_pose", box_pose, (k, 7))
+        dp = self._opt(what, "dist", dist, (k, R))
+        hp = self._opt(what, "hits", hits, (k, R, 8))
+        self._keep_ray = (rays, box_pose)            # alive until the kernel ran
+        check(self.lib.dexsim_raycast(self.h, ids, k, qp, bp, float(box_size), rp, (C.c_int * R)(*pl), R, float(min_range), float(max_range),
+                                      _abi.RAY_SKIP_PARENT if skip_parent else 0, dp, hp, self._stream()), what)
+
 
 class ProximityResult:
     """What DexHandEnv.query_proximity returns: the three device tensors (None where not requested), the pair table and the names
@@ -414,9 +443,40 @@ class ProximityResult:
         return self.self_min[..., 7].contiguous().view(torch.int32).to(torch.int64)
 
 
+class RayHits:
+    """What DexHandEnv.read_ray_sensor returns: `dist` (k, R) and `hits` (k, R, 8) device tensors (None where not requested) and views
+    of the hit records."""
+
+    def __init__(self, model, dist=None, hits=None):
+        self.dist, self.hits = dist, hits
+        self._model = model
+
+    @property
+    def seg(self):
+        """(k, R) int32 segment ids: SEG_NONE, SEG_GROUND, SEG_BOX or SEG_CAPSULE0 + c (word 7 of hits)."""
+        return self.hits[..., 7].contiguous().view(torch.int32)
+
+    @property
+    def points(self):
+        """(k, R, 3) hit points in the env's world frame (zeros without a hit)."""
+        return self.hits[..., 1:4]
+
+    @property
+    def normals(self):
+        """(k, R, 3) outward unit normals at the hit, world frame (zeros without a hit)."""
+        return self.hits[..., 4:7]
+
+    def segment_name(self, seg_id):
+        """"none", "ground", "box", or the name of the rigid body the hit capsule belongs to (a row name of rigid_body_states)."""
+        i = int(seg_id)
+        if i in (_abi.SEG_NONE, _abi.SEG_GROUND, _abi.SEG_BOX):
+            return ("none", "ground", "box")[i]
+        return ProximityResult.capsule_body(self, i - _abi.SEG_CAPSULE0)
+
+
 class EnvQueries:
     """The user level of the queries.  DexHandEnv supplies _core, _sim_cfg, _model_struct, model, num_envs, actions,
-    action_processor and the _cameras dict."""
+    action_processor and the _cameras and _ray_sensors dicts."""
 
     # ------------------------------------------------------------------ the argument rules
     def _query_core(self, what, methods, error=NotImplementedError):
@@ -962,3 +1022,113 @@ class EnvQueries:
         if getattr(self, "_proximity_pairs", None) is None:
             self._proximity_pairs = core.proximity_pairs()                     # a host table: read once
         return ProximityResult(self.model, self._proximity_pairs, **bufs)
+
+    # ------------------------------------------------------------------ range sensors (dexsim_raycast)
+    def _ray_parent(self, what, p):
+        """(joint index or -1, body index or None) of one `parent` entry: None = the world frame, a joint index, a DOF name or a body
+        name of hand_model.BODY_NAMES."""
+        if p is None:
+            return -1, None
+        if isinstance(p, str):
+            if p in self.model.dof_names:
+                return self.model.dof_names.index(p), None
+            if p in self.model.body_names:
+                b = self.model.body_names.index(p)
+                return int(self.model.body_parent[b]), b
+            raise ValueError(f"{what}: unknown parent '{p}' (a joint of {self.model.dof_names} or a body of {self.model.body_names})")
+        j = int(p)
+        if not 0 <= j < _abi.NJ:
+            raise ValueError(f"{what}: a parent joint index must be in [0, {_abi.NJ}), got {p}")
+        return j, None
+
+    def create_ray_sensor(self, name, origins, directions, parent=None, min_range=0.0, max_range=1.0, skip_parent=False):
+        """A range sensor of R rays for every env: origins and directions (R, 3) in each ray's parent frame.  parent: one value
+        or R of them -- None = the env's world frame, a joint index or DOF name = that joint's frame (as create_camera), or a body
+        name from hand_model.BODY_NAMES such as "r_f_link2_pad": the ray is then given in the body's frame and folded, on the host and
+        in float64, through the body's fixed offset into the joint frame the body rides on (a body on the spawn frame folds to the
+        world frame).  A reading counts inside [min_range, max_range] metres; skip_parent: a ray does not see the capsules of the
+        joint frame it is mounted on (a sensor under its own link's skin).  The device call wants the rays sorted by parent: they are
+        sorted here, stably.  If the given order was already sorted, read_ray_sensor returns the kernel's tensors as they are;
+        otherwise every read puts the columns back into the caller's order by one index_select (a copy)."""
+        what = "create_ray_sensor"
+        core = self._query_core(what, ("raycast",))
+        sensors = self._ray_sensors
+        if name in sensors:
+            raise ValueError(f"{what}: ray sensor '{name}' already exists")
+        o, d = np.asarray(origins, dtype=np.float64), np.asarray(directions, dtype=np.float64)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError(f"{what}: origins and directions must both have shape (R, 3), got {o.shape} and {d.shape}")
+        R = o.shape[0]
+        if not 1 <= R <= _abi.RAY_MAX:
+            raise ValueError(f"{what}: between 1 and {_abi.RAY_MAX} rays, got {R}")
+        if not (np.isfinite(o).all() and np.isfinite(d).all()) or ((d * d).sum(1) < 1e-24).any():
+            raise ValueError(f"{what}: origins and directions must be finite and no direction may be zero")
+        lo, hi = float(min_range), float(max_range)
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo < hi):
+            raise ValueError(f"{what}: the ranges must be finite with 0 <= min_range < max_range, got {min_range} and {max_range}")
+        plist = list(parent) if isinstance(parent, (list, tuple, np.ndarray)) else [parent] * R
+        if len(plist) != R:
+            raise ValueError(f"{what}: parent must be one value or {R} of them, got {len(plist)}")
+        o, d = o.copy(), d.copy()                                              # directions as given: the device call normalises them
+        joints = np.zeros(R, dtype=np.int64)
+        for i, p in enumerate(plist):
+            joints[i], b = self._ray_parent(what, p)
+            if b is not None:                                                   # body frame -> the frame the body rides on
+                Rb, pb = np.asarray(self.model.body_R[b], dtype=np.float64), np.asarray(self.model.body_p[b], dtype=np.float64)
+                o[i], d[i] = pb + Rb @ o[i], Rb @ d[i]
+                if joints[i] < 0:                                               # a body on the spawn frame: the world frame, through the spawn pose
+                    Rs = np.asarray(self.model.spawn_rot, dtype=np.float64)
+                    o[i], d[i] = np.asarray(self.model.spawn_pos, dtype=np.float64) + Rs @ o[i], Rs @ d[i]
+        order = np.argsort(joints, kind="stable")
+        rays = torch.as_tensor(np.concatenate([o, d], axis=1)[order], dtype=torch.float32).to(core.device).contiguous()
+        unsort = None
+        if (order != np.arange(R)).any():
+            unsort = torch.as_tensor(np.argsort(order, kind="stable"), dtype=torch.int64).to(core.device)
+        sensors[name] = {"rays": rays, "parent": [int(j) for j in joints[order]], "unsort": unsort, "min_range": lo, "max_range": hi,
+                         "skip_parent": bool(skip_parent), "R": R}
+        return name
+
+    def read_ray_sensor(self, name, env_ids=None, q=None, box_pose=None, box_size=None, outputs=("dist",), out=None):
+        """Read the ray sensor `name`, one kernel launch: a RayHits with `dist` (k, R) -- metres along the ray, +inf without a hit
+        -- and / or `hits` (k, R, 8) -- t, hit point (3), outward unit normal (3), segment id as int32 bits; its views seg, points
+        and normals, and segment_name(id).  Point and normal are in the env's world frame.  Rows as for get_jacobian: the envs
+        `env_ids` (None = all), or the rows of a (k, 26) joint-position override `q`.  The box: `box_pose` (k, 7) = centre xyz +
+        quaternion xyzw when given; None = the envs' own box without `q`, no box with it.  box_size: edge length, None = the
+        configured one.  out: a dict of preallocated tensors by output name; with a sensor whose rays were given out of parent order
+        the reordered copy is what is returned, and `out` receives the kernel's own order."""
+        what = "read_ray_sensor"
+        core, ids, q, k = self._kindyn_rows(what, "raycast", env_ids, q)
+        sensors = self._ray_sensors
+        if name not in sensors:
+            raise KeyError(f"no ray sensor named '{name}' (ray sensors: {sorted(sensors)})")
+        s = sensors[name]
+        names = ("dist", "hits")
+        if isinstance(outputs, str):
+            outputs = (outputs,)
+        outputs = tuple(outputs)
+        if not outputs or any(o not in names for o in outputs):
+            raise ValueError(f"{what}: outputs must be a non-empty subset of {names}, got {outputs}")
+        if box_pose is not None:
+            box_pose = torch.as_tensor(box_pose, dtype=torch.float32, device=core.device)
+            if tuple(box_pose.shape) != (k, 7):
+                raise ValueError(f"{what}: box_pose must have shape ({k}, 7), got {tuple(box_pose.shape)}")
+            box_pose = box_pose.contiguous()
+        size = 0.0
+        if box_size is not None:
+            size = float(box_size)
+            if not (size > 0.0 and size != float("inf")):
+                raise ValueError(f"{what}: box_size must be a positive finite edge length, got {box_size}")
+        shapes = {"dist": (k, s["R"]), "hits": (k, s["R"], 8)}
+        if out is not None and (not isinstance(out, dict) or any(o not in outputs for o in out)):
+            raise ValueError(f"{what}: out must be a dict of tensors keyed by the names in outputs, got {out if not isinstance(out, dict) else sorted(out)}")
+        bufs = {}
+        for o in outputs:
+            given = None if out is None else out.get(o)
+            bufs[o] = self._kindyn_out(what, given, shapes[o], core.device)
+            if given is None and ids is not None:   # a row whose id is out of range is left as it is by the kernel: give it a defined value
+                bufs[o].fill_(float("nan"))
+        core.raycast(rays=s["rays"], parent=s["parent"], env_ids=ids, q=q, box_pose=box_pose, box_size=size, min_range=s["min_range"],
+                     max_range=s["max_range"], skip_parent=s["skip_parent"], **bufs)
+        if s["unsort"] is not None:
+            bufs = {o: t.index_select(1, s["unsort"]) for o, t in bufs.items()}
+        return RayHits(self.model, **bufs)

@@ -579,6 +579,12 @@ int dexsim_render_layout(DexSimField* fields, int max_fields, int* n_fields, siz
 int dexsim_render(dexsim_t h, const DexSimCamera* cam, const float* eye, const float* target, const int64_t* env_ids, int k,
                   float* scene, float* depth, uint8_t* rgba, int32_t* seg, void* stream);
 
+/* ------------------------------------------------------------------ range sensors: batched ray casts with distance, hit and normal
+ * A few dozen arbitrary rays, each mounted on a joint frame of the hand or on the env's world frame, cast against the ground, the box
+ * and the hand's capsules by the intersection rule of the camera sensors above: the entry point, DEXSIM_RAY_MAX and
+ * DEXSIM_RAY_SKIP_PARENT are declared and documented in dexsim_ray.h, which is part of this header. */
+#include "dexsim_ray.h"
+
 /* ------------------------------------------------------------------ body Jacobians, mass matrix and gravity force
  * The counterparts of gym.acquire_jacobian_tensor / refresh_jacobian_tensors and gym.acquire_mass_matrix_tensor /
  * refresh_mass_matrix_tensors for the hand actor, for Cartesian fingertip control and inverse kinematics, operational-space and
