@@ -1,6 +1,7 @@
 // dexsim_chain.hip.inc -- the frame the query kernels share (k_render_scene, k_kin_jacobian, k_kin_mass, k_ik_solve, k_proximity,
-// k_kin_invdyn, k_kin_bias_accel, k_kin_fwddyn, k_kin_id_deriv): pure functions of q (the last four of q and qd), off the step path, writing
-// caller-owned memory only.  Force-inlined functions and macros only: this file emits no code of its own.
+// k_raycast, k_kin_fk, k_kin_invdyn, k_kin_bias_accel, k_kin_fwddyn, k_kin_id_deriv): pure functions of q (the last five of q and
+// qd), off the step path, writing caller-owned memory only.  Force-inlined functions and macros only: this file emits no code of its
+// own.
 //
 //   joint_frame      THE joint-frame rule: parent frame -> a joint's offset, world axis and frame.  Every walk of the family is
 //                    written through it; publish_body (dexsim_physics.hip.inc) spells the same rule out for the step kernels.
@@ -11,6 +12,10 @@
 //                    two together for an override or an arena field (kd_load_q, kd_load_qd).  A `valid` flag per row only gates
 //                    stores: every lane reads legal addresses.  kd_flush writes rows that leave as they were staged, whole or as
 //                    a range of columns of longer rows.
+//   the scene stage  what the geometric queries (k_proximity, k_raycast) see of a row: KD_PLACE_HAND walks the hand and leaves the
+//                    axis ends of the DEXSIM_NCAP collision capsules (capsule order: kd_finger_cap) and o5 (world) in LDS, running
+//                    the kernel's ON_FRAME on every joint frame it stands on; KD_LOAD_BOX gives the row's box (KinBox) as a centre
+//                    and a unit quaternion.
 //   KD_TRI           the packed lower triangle every symmetric block of the family is kept in.
 
 #define KD_LD 65          /* LDS row stride in words: [word][row], padded by one */
@@ -115,6 +120,89 @@ DI void kd_finger_link(const JC& c, float qj, V3& of, Q4& qf, V3& aw, V3& rc, S6
 
 #define KD_TRI(i, j) ((i) * ((i) + 1) / 2 + (j))   /* packed lower triangle */
 #define KD_PUT3(w, v) { s_w[((w) + 0) * KD_LD + lane] = (v).x; s_w[((w) + 1) * KD_LD + lane] = (v).y; s_w[((w) + 2) * KD_LD + lane] = (v).z; }
+
+// ---- the scene stage of the geometric queries
+// capsule of finger f's link l (cap_fslot == 3 f + l), behind the three palm capsules: the capsule order validate_model and
+// dexsim_query_proximity insist on
+__host__ DI int kd_finger_cap(int f, int l) { return 3 + 3 * f + l; }
+
+// The box of a call (the host side is kin_box, dexsim_queries.hip); pose or env says that there is one
+struct KinBox {
+  const float* pose;   // (k, 7) centre xyz, quaternion xyzw, or NULL
+  int env;             // no pose: the box of the row's env (state path, cfg.has_box)
+  float hb;            // half edge of the box
+};
+
+// The two pieces below are macros, not functions, and stand in the kernel's own scope (P, A, M, K, N, NR, f, lane, s_w, s_valid, as
+// KD_PUT3 does): the library is built with FMA contraction, which product of a sum of products is fused follows the order the
+// optimiser hands the back end, and that order moved when these lines were reached through a call -- some of both kernels' words
+// changed in their last bit.  As text in the kernel they compile to the instructions they compiled to when each kernel spelled them.
+//
+// KD_PLACE_HAND: lanes along the rows, wave f walks the chain of finger f (kd_load_q / kd_base_walk / kd_finger_joint) and leaves the
+// axis ends p0.xyz p1.xyz of its three capsules, relative to o5, in the LDS words [cap0 + 6 c, cap0 + 6 c + 6); waves 0-2 also place
+// one palm capsule each, wave 0 leaves o5 (world) in [o5w, o5w + 3) and the rows' `valid` in s_valid.  The wave that stands on a
+// frame runs ON_WORLD(o) (wave 0, the env's world frame, o = -o5) or ON_FRAME(j, o, q) (wave 0 for the base joints 0..5, wave f for
+// the joints 6 + 4 f + l of its finger; origin relative to o5, orientation), in front of the capsule that rides on j.  Sets `valid`;
+// the caller's __syncthreads() publishes the words.
+#define KD_PLACE_HAND(valid, cap0, o5w, ON_WORLD, ON_FRAME)                                                                   \
+  {                                                                                                                           \
+    float qb[6], qf[4];                                                                                                       \
+    valid = kd_load_q(A, K.rows, N, NR, f, qb, qf);                                                                           \
+    KinBase B;                                                                                                                \
+    kd_base_walk(P, qb, B);                                                                                                   \
+    const M3 R5 = q2mat(B.q[5]);                                                                                              \
+    if (f == 0) {                                                                                                             \
+      s_valid[lane] = valid;                                                                                                  \
+      /* o5 = spawn + (o_0 - spawn) + (o_5 - o_0): the first increment of the walk, then its own suffix sum */                \
+      const V3 inc0 = mul(q2mat(q4p(M.spawn_quat)), v3p(P->jc[0].poff)) + qb[0] * B.a[0];                                     \
+      const V3 o5 = (v3p(M.spawn_pos) + inc0) - B.orel[0];                                                                    \
+      KD_PUT3(o5w, o5);                                                                                                       \
+      ON_WORLD(v3(0, 0, 0) - o5);                                                                                             \
+      _Pragma("unroll") for (int j = 0; j < 6; j++) ON_FRAME(j, B.orel[j], B.q[j]);                                           \
+    }                                                                                                                         \
+    if (f < 3) { /* palm capsule f rides on joint 5 (validate_model) */                                                       \
+      const V3 p0 = mul(R5, v3p(M.cap_p0[f])), p1 = mul(R5, v3p(M.cap_p1[f]));                                                \
+      KD_PUT3(cap0 + 6 * f, p0); KD_PUT3(cap0 + 6 * f + 3, p1);                                                               \
+    }                                                                                                                         \
+    V3 of = v3(0, 0, 0);                                                                                                      \
+    Q4 qc = B.q[5];                                                                                                           \
+    _Pragma("unroll") for (int l = 0; l < DEXSIM_NFJ; l++) {                                                                  \
+      V3 aw;                                                                                                                  \
+      kd_finger_joint(P->jc[6 + 4 * f + l], qf[l], of, qc, aw);                                                               \
+      ON_FRAME(6 + 4 * f + l, of, qc);                                                                                        \
+      if (l >= 1) { /* link l - 1 of the finger rides on its joint l (validate_model) */                                      \
+        const int c = kd_finger_cap(f, l - 1);                                                                                \
+        const M3 Rj = q2mat(qc);                                                                                              \
+        const V3 p0 = of + mul(Rj, v3p(M.cap_p0[c])), p1 = of + mul(Rj, v3p(M.cap_p1[c]));                                    \
+        KD_PUT3(cap0 + 6 * c, p0); KD_PUT3(cap0 + 6 * c + 3, p1);                                                             \
+      }                                                                                                                       \
+    }                                                                                                                         \
+  }
+
+// KD_LOAD_BOX: the box of row `row` (valid as KD_PLACE_HAND set it) into V3 bc and Q4 bq -- its row of K.box.pose, else, if ENV
+// (K.box.env, or true where the caller stands under "the call has a box"), the arena fields of the row's env, else the identity
+// at the origin.  The quaternion is normalised here (a zero quaternion is the identity): callers hand in rounded
+// or integrated values.
+#define KD_LOAD_BOX(bc, bq, row, valid, ENV)                                                                                  \
+  V3 bc = v3(0, 0, 0);                                                                                                        \
+  Q4 bq = {0.f, 0.f, 0.f, 1.f};                                                                                               \
+  if (K.box.pose) {                                                                                                           \
+    const float* const b = K.box.pose + (size_t)min((int)row, K.rows.k - 1) * 7;                                              \
+    bc = v3(GPTR(b)[0], GPTR(b)[1], GPTR(b)[2]);                                                                              \
+    bq = Q4{GPTR(b)[3], GPTR(b)[4], GPTR(b)[5], GPTR(b)[6]};                                                                  \
+  } else if (ENV) {                                                                                                           \
+    long long id = (long long)row;                                                                                            \
+    if (K.rows.env_ids) id = GPTR(K.rows.env_ids)[min((int)row, K.rows.k - 1)];                                               \
+    const int e = valid ? (int)id : 0;                                                                                        \
+    bc = v3(FLD(box_pos, 0), FLD(box_pos, 1), FLD(box_pos, 2));                                                               \
+    bq = Q4{FLD(box_quat, 0), FLD(box_quat, 1), FLD(box_quat, 2), FLD(box_quat, 3)};                                          \
+  }                                                                                                                           \
+  {                                                                                                                           \
+    const float n2 = bq.x * bq.x + bq.y * bq.y + bq.z * bq.z + bq.w * bq.w;                                                   \
+    const bool ok = n2 > 1e-30f;                                                                                              \
+    const float in = 1.f / sqrtf(ok ? n2 : 1.f);                                                                              \
+    bq = Q4{ok ? bq.x * in : 0.f, ok ? bq.y * in : 0.f, ok ? bq.z * in : 0.f, ok ? bq.w * in : 1.f};                          \
+  }
 
 // Words [w0, w0 + n) of the workgroup's 64 staged rows -> dst[(row0 + r) * rowlen + col0 + c], all five waves along the contiguous
 // output index; a row leaves only if s_valid[r].  QUAD: 16 bytes per lane (n a multiple of 4, dst 16-byte aligned), else one word.

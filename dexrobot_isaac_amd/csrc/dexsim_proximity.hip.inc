@@ -4,10 +4,9 @@
 // override) and the box pose (arena rows or the caller's) and writes caller-owned memory only.
 //
 // One workgroup in the shape of dexsim_chain.hip.inc (64 rows x 5 waves, [word][row] LDS, o5-relative positions):
-//   phase A  lanes along the rows; wave f walks the chain of finger f (kd_load_q / kd_base_walk / kd_finger_joint) and leaves the
-//            axis ends of its three capsules in LDS; waves 0-2 also place one palm capsule each, wave 0 leaves o5 (world) once.
-//            Every hand-internal difference of phase B is therefore a difference of numbers of hand size (< 0.4 m), not of world
-//            coordinates, and the box enters through (o5 - centre) alone.
+//   phase A  the scene stage of dexsim_chain.hip.inc (KD_PLACE_HAND): the axis ends of the capsules relative to o5, and o5 (world),
+//            in LDS.  Every hand-internal difference of phase B is therefore a difference of numbers of hand size (< 0.4 m), not of
+//            world coordinates, and the box (KD_LOAD_BOX) enters through (o5 - centre) alone.
 //   phase B  lanes stay on the rows.  Wave w takes the finger groups 2 w and 2 w + 1 and the palm group 10 + w (9 + 9 + 6 = 24
 //            segment pairs) and the environment records of the capsules w, w + 5, w + 10, w + 15.  The loops are fully unrolled and
 //            the pairs of a group do not depend on each other (only the strict-less minimum chains them), so the scheduler
@@ -39,15 +38,10 @@ static_assert(PX_WORDS * KD_LD * 4 + 256 <= 65536, "k_proximity: static LDS abov
 // finger pair (fa < fb) of group g = 0..9, lexicographic: (0,1) (0,2) (0,3) (0,4) (1,2) (1,3) (1,4) (2,3) (2,4) (3,4)
 __host__ DI int px_group_fa(int g) { return (int)((0x3221110000ull >> (4 * g)) & 15); }
 __host__ DI int px_group_fb(int g) { return (int)((0x4434324321ull >> (4 * g)) & 15); }
-// capsule of finger f's link l (cap_fslot == 3 f + l) and of palm slot i: the capsule order validate_model and
-// dexsim_query_proximity insist on
-__host__ DI int px_finger_cap(int f, int l) { return 3 + 3 * f + l; }
 
 struct ProxArgs {
   KinRows rows;
-  const float* box_pose;   // (k, 7) centre xyz, quaternion xyzw, or NULL
-  int box_env;             // no box_pose: the box of the row's env (state path, cfg.has_box)
-  float hb;                // half edge of the box
+  KinBox box;
   float* cap_env;          // (k, DEXSIM_NCAP, 2, 8) or NULL
   float* self_min;         // (k, DEXSIM_NPROX_GROUPS, 8) or NULL
   float* pair_dist;        // (k, DEXSIM_NPROX_PAIRS) or NULL
@@ -158,45 +152,17 @@ DI void px_group(float* s_w, int lane, const DexHandModel& M, const int (&capA)[
   rec[4] = pw.x; rec[5] = pw.y; rec[6] = pw.z; rec[7] = __int_as_float(bi);
 }
 
+#define PX_NO_RAYS(...) /* nothing rides on the frames of KD_PLACE_HAND here */
+
 __global__ __launch_bounds__(KD_THREADS) void k_proximity(const DevParams* __restrict__ P, ProxArgs K, int N, int NR) {
   __shared__ float s_w[PX_WORDS * KD_LD];
   __shared__ int s_valid[64];
   const int lane = threadIdx.x & 63, f = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const Arena& A = P->arena;
   const DexHandModel& M = P->model;
-  bool valid;
 
-  {   // ---- phase A
-    float qb[6], qf[4];
-    valid = kd_load_q(A, K.rows, N, NR, f, qb, qf);
-    KinBase B;
-    kd_base_walk(P, qb, B);
-    const M3 R5 = q2mat(B.q[5]);
-    if (f == 0) {
-      s_valid[lane] = valid;
-      // o5 = spawn + (o_0 - spawn) + (o_5 - o_0): the first increment of the walk, then its own suffix sum
-      const V3 inc0 = mul(q2mat(q4p(M.spawn_quat)), v3p(P->jc[0].poff)) + qb[0] * B.a[0];
-      const V3 o5 = (v3p(M.spawn_pos) + inc0) - B.orel[0];
-      KD_PUT3(PX_O5, o5);
-    }
-    if (f < 3) {   // palm capsule f rides on joint 5 (validate_model)
-      const V3 p0 = mul(R5, v3p(M.cap_p0[f])), p1 = mul(R5, v3p(M.cap_p1[f]));
-      KD_PUT3(PX_CAP + 6 * f, p0); KD_PUT3(PX_CAP + 6 * f + 3, p1);
-    }
-    V3 of = v3(0, 0, 0);
-    Q4 qc = B.q[5];
-#pragma unroll
-    for (int l = 0; l < DEXSIM_NFJ; l++) {
-      V3 aw;
-      kd_finger_joint(P->jc[6 + 4 * f + l], qf[l], of, qc, aw);
-      if (l >= 1) {   // link l - 1 of the finger rides on its joint l (validate_model)
-        const int c = px_finger_cap(f, l - 1);
-        const M3 Rj = q2mat(qc);
-        const V3 p0 = of + mul(Rj, v3p(M.cap_p0[c])), p1 = of + mul(Rj, v3p(M.cap_p1[c]));
-        KD_PUT3(PX_CAP + 6 * c, p0); KD_PUT3(PX_CAP + 6 * c + 3, p1);
-      }
-    }
-  }
+  bool valid;
+  KD_PLACE_HAND(valid, PX_CAP, PX_O5, PX_NO_RAYS, PX_NO_RAYS)   // ---- phase A
   __syncthreads();
 
   // ---- phase B
@@ -204,26 +170,8 @@ __global__ __launch_bounds__(KD_THREADS) void k_proximity(const DevParams* __res
   const V3 o5 = v3(s_w[PX_O5 * KD_LD + lane], s_w[(PX_O5 + 1) * KD_LD + lane], s_w[(PX_O5 + 2) * KD_LD + lane]);
 
   if (K.cap_env) {
-    const bool has_box = K.box_pose != nullptr || K.box_env != 0;   // the same for every row of the call
-    V3 bc = v3(0, 0, 0);
-    Q4 bq = {0.f, 0.f, 0.f, 1.f};
-    if (K.box_pose) {
-      const float* const b = K.box_pose + (size_t)min((int)row, K.rows.k - 1) * 7;
-      bc = v3(GPTR(b)[0], GPTR(b)[1], GPTR(b)[2]);
-      bq = Q4{GPTR(b)[3], GPTR(b)[4], GPTR(b)[5], GPTR(b)[6]};
-    } else if (K.box_env) {
-      long long id = (long long)row;
-      if (K.rows.env_ids) id = GPTR(K.rows.env_ids)[min((int)row, K.rows.k - 1)];
-      const int e = valid ? (int)id : 0;
-      bc = v3(FLD(box_pos, 0), FLD(box_pos, 1), FLD(box_pos, 2));
-      bq = Q4{FLD(box_quat, 0), FLD(box_quat, 1), FLD(box_quat, 2), FLD(box_quat, 3)};
-    }
-    {   // the quaternion is normalised here (a zero quaternion is the identity): callers hand in rounded or integrated values
-      const float n2 = bq.x * bq.x + bq.y * bq.y + bq.z * bq.z + bq.w * bq.w;
-      const bool ok = n2 > 1e-30f;
-      const float in = 1.f / sqrtf(ok ? n2 : 1.f);
-      bq = Q4{ok ? bq.x * in : 0.f, ok ? bq.y * in : 0.f, ok ? bq.z * in : 0.f, ok ? bq.w * in : 1.f};
-    }
+    const bool has_box = K.box.pose != nullptr || K.box.env != 0;   // the same for every row of the call
+    KD_LOAD_BOX(bc, bq, row, valid, K.box.env)
     const M3 Rb = q2mat(bq);
     const V3 ob = o5 - bc;   // the one difference of world coordinates
     const float inf = __int_as_float(0x7f800000);
@@ -237,7 +185,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_proximity(const DevParams* __res
         V3 bn = v3(0, 0, 0), bpw = v3(0, 0, 0);
         if (has_box) {
           V3 nl, pl;
-          px_capsule_box(mulT(Rb, ob + S.p), mulT(Rb, S.d), S.r, K.hb, nl, pl, bd, bt);
+          px_capsule_box(mulT(Rb, ob + S.p), mulT(Rb, S.d), S.r, K.box.hb, nl, pl, bd, bt);
           bn = mul(Rb, nl);
           bpw = mul(Rb, pl) + bc;
         }
@@ -261,8 +209,8 @@ __global__ __launch_bounds__(KD_THREADS) void k_proximity(const DevParams* __res
 #pragma unroll
     for (int gi = 0; gi < 2; gi++) {   // finger groups 2 f, 2 f + 1
       const int g = 2 * f + gi, fa = px_group_fa(g), fb = px_group_fb(g);
-      const int capA[3] = {px_finger_cap(fa, 0), px_finger_cap(fa, 1), px_finger_cap(fa, 2)};
-      const int capB[3] = {px_finger_cap(fb, 0), px_finger_cap(fb, 1), px_finger_cap(fb, 2)};
+      const int capA[3] = {kd_finger_cap(fa, 0), kd_finger_cap(fa, 1), kd_finger_cap(fa, 2)};
+      const int capB[3] = {kd_finger_cap(fb, 0), kd_finger_cap(fb, 1), kd_finger_cap(fb, 2)};
       px_group<3>(s_w, lane, M, capA, capB, 9 * g, o5, want_pd, rec);
       if (K.self_min && valid) {
         float* const out = K.self_min + (row * DEXSIM_NPROX_GROUPS + g) * 8;
@@ -272,7 +220,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_proximity(const DevParams* __res
     }
     {   // palm group 10 + f: the palm capsules against the middle and distal link of finger f
       const int capA[3] = {0, 1, 2};
-      const int capB[3] = {px_finger_cap(f, 1), px_finger_cap(f, 2), 0};
+      const int capB[3] = {kd_finger_cap(f, 1), kd_finger_cap(f, 2), 0};
       px_group<2>(s_w, lane, M, capA, capB, 90 + 6 * f, o5, want_pd, rec);
       if (K.self_min && valid) {
         float* const out = K.self_min + (row * DEXSIM_NPROX_GROUPS + 10 + f) * 8;

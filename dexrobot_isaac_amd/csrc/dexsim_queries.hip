@@ -93,6 +93,18 @@ static int kin_rows(const char* who, dexsim_t h, const int64_t* env_ids, int k, 
   return DEXSIM_OK;
 }
 
+// The box of a geometric query (KinBox, dexsim_chain.hip.inc): the caller's (k, 7) box_pose, else the env's own box on the state path
+// of a task that has one, else none; box_size > 0 overrides cfg.box_size.  Behind kin_rows (it reads the handle); that box_size is
+// finite needs no handle and is checked by the entry points in front of it.
+static int kin_box(const char* who, dexsim_t h, const float* q, const float* box_pose, float box_size, KinBox* B) {
+  const float size = box_size > 0.f ? box_size : h->cfg.box_size;
+  B->pose = box_pose;
+  B->env = !box_pose && !q && h->cfg.has_box;
+  if ((B->pose || B->env) && !(size > 0.f)) return fail(DEXSIM_ERR_ARG, (std::string(who) + ": a box needs a positive box_size or cfg.box_size").c_str());
+  B->hb = 0.5f * size;
+  return DEXSIM_OK;
+}
+
 // a required output: non-NULL and `align`-byte aligned
 static int kin_out(const char* who, const char* name, const void* p, int align) {
   if (p && ((uintptr_t)p & (uintptr_t)(align - 1)) == 0) return DEXSIM_OK;
@@ -202,10 +214,10 @@ extern "C" int dexsim_solve_ik(dexsim_t h, const int64_t* env_ids, int k, const 
 static void px_pair(int i, int* cap_a, int* cap_b, int* group) {
   if (i < 90) {
     const int g = i / 9, r = i - 9 * g;
-    *cap_a = px_finger_cap(px_group_fa(g), r / 3); *cap_b = px_finger_cap(px_group_fb(g), r % 3); *group = g;
+    *cap_a = kd_finger_cap(px_group_fa(g), r / 3); *cap_b = kd_finger_cap(px_group_fb(g), r % 3); *group = g;
   } else {
     const int j = i - 90, f = j / 6, r = j - 6 * f;
-    *cap_a = r / 2; *cap_b = px_finger_cap(f, 1 + r % 2); *group = 10 + f;
+    *cap_a = r / 2; *cap_b = kd_finger_cap(f, 1 + r % 2); *group = 10 + f;
   }
 }
 
@@ -233,20 +245,16 @@ extern "C" int dexsim_query_proximity(dexsim_t h, const int64_t* env_ids, int k,
     if (h->model.cap_fslot[c] != (c < 3 ? DEXSIM_FSLOT_PALM : c - 3))
       return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: the model must have exactly three palm capsules (0-2) and one capsule per finger "
                                   "link (capsule 3 + s in force slot s)");
-  const float size = box_size > 0.f ? box_size : h->cfg.box_size;
-  K.box_pose = box_pose;
-  K.box_env = !box_pose && !q && h->cfg.has_box;
-  if ((K.box_pose || K.box_env) && !(size > 0.f))
-    return fail(DEXSIM_ERR_ARG, "dexsim_query_proximity: a box needs a positive box_size or cfg.box_size");
+  rc = kin_box("dexsim_query_proximity", h, q, box_pose, box_size, &K.box);
+  if (rc) return rc;
   NEED_BOUND(h);
-  K.hb = 0.5f * size;
   K.cap_env = cap_env; K.self_min = self_min; K.pair_dist = pair_dist;
   KIN_LAUNCH(k_proximity, 1, K);
   return DEXSIM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------- range sensors
-// Behind the clearances: the rows and the box of a call are theirs.
+// The rows and the box of a call as for the clearances: kin_rows, kin_box.
 // clang-format off
 #include "dexsim_raycast.hip.inc"
 // clang-format on
@@ -281,12 +289,9 @@ extern "C" int dexsim_raycast(dexsim_t h, const int64_t* env_ids, int k, const f
       if (p < 0 || p >= DEXSIM_NJ) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: DEXSIM_RAY_SKIP_PARENT needs every model.cap_parent in [0, DEXSIM_NJ)");
       K.skip[p] |= 1u << c;
     }
-  const float size = box_size > 0.f ? box_size : h->cfg.box_size;
-  K.box_pose = box_pose;
-  K.box_env = !box_pose && !q && h->cfg.has_box;
-  if ((K.box_pose || K.box_env) && !(size > 0.f)) return fail(DEXSIM_ERR_ARG, "dexsim_raycast: a box needs a positive box_size or cfg.box_size");
+  rc = kin_box("dexsim_raycast", h, q, box_pose, box_size, &K.box);
+  if (rc) return rc;
   NEED_BOUND(h);
-  K.hb = 0.5f * size;
   K.rays = rays; K.nrays = nrays;
   K.tmin = min_range; K.tmax = max_range;
   K.dist = dist; K.hits = hits;

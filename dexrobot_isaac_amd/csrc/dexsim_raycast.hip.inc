@@ -8,12 +8,12 @@
 //
 // One workgroup in the shape of dexsim_chain.hip.inc (64 rows x 5 waves, [word][row] LDS, o5-relative positions); blockIdx.y is the
 // chunk of RC_CHUNK rays.  Every workgroup repeats the walk and the chunk index says what it keeps of it, as in k_kin_fk.
-//   phase A  lanes along the rows; wave f walks the chain of finger f (kd_load_q / kd_base_walk / kd_finger_joint) and leaves the
-//            axis ends of its three capsules in LDS, waves 0-2 also one palm capsule each, wave 0 o5 (world) -- phase A of
-//            k_proximity.  While a wave stands on frame j it turns the rays of the chunk that ride on j into o5-relative origin and
-//            unit direction (rc_put_rays): its range of the sorted list is wave-uniform, from the prefix offsets the entry point
-//            hands over (the jstart of FwdKin), so no wave scans a list at a frame.  Wave 0 also takes the world rays.  The ray
-//            table is wave-uniform and read through a const __restrict__ pointer at uniform indices: scalar loads.
+//   phase A  the scene stage of dexsim_chain.hip.inc (KD_PLACE_HAND): the axis ends of the capsules relative to o5, and o5 (world),
+//            in LDS.  While a wave stands on frame j (the stage's ON_FRAME) it turns the rays of the chunk that ride on j into
+//            o5-relative origin and unit direction (rc_put_rays): its range of the sorted list is wave-uniform, from the prefix
+//            offsets the entry point hands over (the jstart of FwdKin), so no wave scans a list at a frame.  Wave 0 also takes the
+//            world rays.  The ray table is wave-uniform and read through a const __restrict__ pointer at uniform indices: scalar
+//            loads.
 //   phase B  after one __syncthreads() the lanes stay on their rows and wave w takes the rays w, w + 5, ... of the chunk: ground,
 //            box and the 18 capsules, fully unrolled -- independent chains with one strict-less minimum between them.  The loop
 //            over a wave's rays is NOT unrolled: every ray runs the same instructions wherever it stands in a call, so a ray of a
@@ -23,9 +23,10 @@
 //            of every record) as contiguous words.
 // Plain __syncthreads() only: no atomics, no spins.  A row >= k or with an id outside [0, num_envs) never writes caller memory.
 //
-// Numerics: every difference is formed between o5-relative numbers of hand size; the box enters through (o5 - centre) rotated into
-// box coordinates once per row, the ground through the world height of the origin, and the world position of o5 is added once, to
-// the hit point.  Cylinder: h = r^2 A - (d . (u x o))^2 as in k_render_rays; the end spheres the same way, h = r^2 - |d x o'|^2.
+// Numerics: every difference is formed between o5-relative numbers of hand size; the box (KD_LOAD_BOX) enters through (o5 - centre)
+// rotated into box coordinates once per row, the ground through the world height of the origin, and the world position of o5 is
+// added once, to the hit point.  Cylinder: h = r^2 A - (d . (u x o))^2 as in k_render_rays; the end spheres the same way,
+// h = r^2 - |d x o'|^2.
 //
 // Chunk size: 16 rays x 8 words + 111 words of capsules and o5 are 239 words x 65 rows x 4 bytes = 62 140 bytes of LDS.  Eight words
 // per ray (six would hold the ray) so that a record is staged in place; see profiles/ray_sensors/README.md for the alternatives.
@@ -40,9 +41,7 @@ static_assert(DEXSIM_RAY_MAX <= 65535, "the prefix offsets of the parent groups 
 
 struct RayArgs {
   KinRows rows;
-  const float* box_pose;   // (k, 7) centre xyz, quaternion xyzw, or NULL
-  int box_env;             // no box_pose: the box of the row's env (state path, cfg.has_box)
-  float hb;                // half edge of the box
+  KinBox box;
   const float* rays;       // (nrays, 6) origin and direction in the parent frame, sorted by parent
   int nrays;
   float tmin, tmax;        // the range window on t
@@ -77,6 +76,10 @@ DI void rc_put_rays(const RayArgs& K, const float* __restrict__ rays, float* s_w
   }
 }
 
+// what k_raycast runs on the frames of KD_PLACE_HAND, in its scope
+#define RC_WORLD_RAYS(o) rc_put_rays<true>(K, rays, s_w, s_par, lane, r0, nc, -1, o, Q4{0.f, 0.f, 0.f, 1.f})
+#define RC_FRAME_RAYS(j, o, q) rc_put_rays<false>(K, rays, s_w, s_par, lane, r0, nc, j, o, q)
+
 __global__ __launch_bounds__(KD_THREADS) void k_raycast(const DevParams* __restrict__ P, RayArgs K, int N, int NR) {
   __shared__ float s_w[RC_WORDS * KD_LD];
   __shared__ int s_valid[64];
@@ -86,71 +89,20 @@ __global__ __launch_bounds__(KD_THREADS) void k_raycast(const DevParams* __restr
   const DexHandModel& M = P->model;
   const float* __restrict__ const rays = K.rays;
   const int r0 = blockIdx.y * RC_CHUNK, nc = min(RC_CHUNK, K.nrays - r0);
-  bool valid;
 
-  {   // ---- phase A
-    float qb[6], qf[4];
-    valid = kd_load_q(A, K.rows, N, NR, f, qb, qf);
-    KinBase B;
-    kd_base_walk(P, qb, B);
-    const M3 R5 = q2mat(B.q[5]);
-    if (f == 0) {
-      s_valid[lane] = valid;
-      // o5 = spawn + (o_0 - spawn) + (o_5 - o_0): the first increment of the walk, then its own suffix sum
-      const V3 inc0 = mul(q2mat(q4p(M.spawn_quat)), v3p(P->jc[0].poff)) + qb[0] * B.a[0];
-      const V3 o5 = (v3p(M.spawn_pos) + inc0) - B.orel[0];
-      KD_PUT3(RC_O5, o5);
-      rc_put_rays<true>(K, rays, s_w, s_par, lane, r0, nc, -1, v3(0, 0, 0) - o5, Q4{0.f, 0.f, 0.f, 1.f});
-#pragma unroll
-      for (int j = 0; j < 6; j++) rc_put_rays<false>(K, rays, s_w, s_par, lane, r0, nc, j, B.orel[j], B.q[j]);
-    }
-    if (f < 3) {   // palm capsule f rides on joint 5 (validate_model)
-      const V3 p0 = mul(R5, v3p(M.cap_p0[f])), p1 = mul(R5, v3p(M.cap_p1[f]));
-      KD_PUT3(RC_CAP + 6 * f, p0); KD_PUT3(RC_CAP + 6 * f + 3, p1);
-    }
-    V3 of = v3(0, 0, 0);
-    Q4 qc = B.q[5];
-#pragma unroll
-    for (int l = 0; l < DEXSIM_NFJ; l++) {
-      V3 aw;
-      kd_finger_joint(P->jc[6 + 4 * f + l], qf[l], of, qc, aw);
-      rc_put_rays<false>(K, rays, s_w, s_par, lane, r0, nc, 6 + 4 * f + l, of, qc);
-      if (l >= 1) {   // link l - 1 of the finger rides on its joint l (validate_model)
-        const int c = 3 + 3 * f + l - 1;
-        const M3 Rj = q2mat(qc);
-        const V3 p0 = of + mul(Rj, v3p(M.cap_p0[c])), p1 = of + mul(Rj, v3p(M.cap_p1[c]));
-        KD_PUT3(RC_CAP + 6 * c, p0); KD_PUT3(RC_CAP + 6 * c + 3, p1);
-      }
-    }
-  }
+  bool valid;
+  // ---- phase A: the rays of frame j in front of the capsule that rides on it
+  KD_PLACE_HAND(valid, RC_CAP, RC_O5, RC_WORLD_RAYS, RC_FRAME_RAYS)
   __syncthreads();
 
   // ---- phase B
   const size_t row = (size_t)blockIdx.x * 64 + lane;
   const V3 o5 = v3(s_w[RC_O5 * KD_LD + lane], s_w[(RC_O5 + 1) * KD_LD + lane], s_w[(RC_O5 + 2) * KD_LD + lane]);
-  const bool has_box = K.box_pose != nullptr || K.box_env != 0;   // the same for every row of the call
+  const bool has_box = K.box.pose != nullptr || K.box.env != 0;   // the same for every row of the call
   M3 Rb = {{1, 0, 0, 0, 1, 0, 0, 0, 1}};
   V3 ob = v3(0, 0, 0);   // o5 - centre in box coordinates
   if (has_box) {
-    V3 bc = v3(0, 0, 0);
-    Q4 bq = {0.f, 0.f, 0.f, 1.f};
-    if (K.box_pose) {
-      const float* const b = K.box_pose + (size_t)min((int)row, K.rows.k - 1) * 7;
-      bc = v3(GPTR(b)[0], GPTR(b)[1], GPTR(b)[2]);
-      bq = Q4{GPTR(b)[3], GPTR(b)[4], GPTR(b)[5], GPTR(b)[6]};
-    } else {
-      long long id = (long long)row;
-      if (K.rows.env_ids) id = GPTR(K.rows.env_ids)[min((int)row, K.rows.k - 1)];
-      const int e = valid ? (int)id : 0;
-      bc = v3(FLD(box_pos, 0), FLD(box_pos, 1), FLD(box_pos, 2));
-      bq = Q4{FLD(box_quat, 0), FLD(box_quat, 1), FLD(box_quat, 2), FLD(box_quat, 3)};
-    }
-    {   // the quaternion is normalised here (a zero quaternion is the identity), as dexsim_query_proximity does
-      const float n2 = bq.x * bq.x + bq.y * bq.y + bq.z * bq.z + bq.w * bq.w;
-      const bool ok = n2 > 1e-30f;
-      const float in = 1.f / sqrtf(ok ? n2 : 1.f);
-      bq = Q4{ok ? bq.x * in : 0.f, ok ? bq.y * in : 0.f, ok ? bq.z * in : 0.f, ok ? bq.w * in : 1.f};
-    }
+    KD_LOAD_BOX(bc, bq, row, valid, true)
     Rb = q2mat(bq);
     ob = mulT(Rb, o5 - bc);   // the one difference of world coordinates
   }
@@ -185,7 +137,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_raycast(const DevParams* __restr
       for (int i = 0; i < 3; i++) {
         const float di = fabsf(db[i]) > 1e-30f ? db[i] : 1e-30f;
         const float m = 1.f / di;
-        const float t1 = -bev[i] * m - fabsf(m) * K.hb, t2 = -bev[i] * m + fabsf(m) * K.hb;
+        const float t1 = -bev[i] * m - fabsf(m) * K.box.hb, t2 = -bev[i] * m + fabsf(m) * K.box.hb;
         const bool later = t1 > tn;
         tn = later ? t1 : tn;
         ax = later ? i : ax;

@@ -487,6 +487,43 @@ class EnvQueries:
                 raise error(f"{what} needs the HIP engine (DexSimCore): the injected core {type(core).__name__} has no {m}()")
         return core
 
+    @staticmethod
+    def _outputs(what, outputs, names):
+        """The `outputs` of a query that returns a choice of tensors: one name or several, as a tuple of names from `names`."""
+        outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+        if not outputs or any(o not in names for o in outputs):
+            raise ValueError(f"{what}: outputs must be a non-empty subset of {names}, got {outputs}")
+        return outputs
+
+    @staticmethod
+    def _box_args(what, box_pose, box_size, k, device):
+        """(box_pose as a contiguous (k, 7) float32 device tensor or None, box_size as the float the core takes: 0.0 = the
+        configured edge length) of a geometric query."""
+        if box_pose is not None:
+            box_pose = torch.as_tensor(box_pose, dtype=torch.float32, device=device)
+            if tuple(box_pose.shape) != (k, 7):
+                raise ValueError(f"{what}: box_pose must have shape ({k}, 7), got {tuple(box_pose.shape)}")
+            box_pose = box_pose.contiguous()
+        size = 0.0
+        if box_size is not None:
+            size = float(box_size)
+            if not (size > 0.0 and size != float("inf")):
+                raise ValueError(f"{what}: box_size must be a positive finite edge length, got {box_size}")
+        return box_pose, size
+
+    def _out_buffers(self, what, outputs, shapes, out, ids, device):
+        """{name: tensor of shapes[name]} for the names in `outputs`: the caller's tensor where the dict `out` has one, else a new
+        one.  With an id list a row whose id is out of range is left as it is by the kernel: a new tensor gets a defined value, NaN."""
+        if out is not None and (not isinstance(out, dict) or any(o not in outputs for o in out)):
+            raise ValueError(f"{what}: out must be a dict of tensors keyed by the names in outputs, got {out if not isinstance(out, dict) else sorted(out)}")
+        bufs = {}
+        for o in outputs:
+            given = None if out is None else out.get(o)
+            bufs[o] = self._kindyn_out(what, given, shapes[o], device)
+            if given is None and ids is not None:
+                bufs[o].fill_(float("nan"))
+        return bufs
+
     # ------------------------------------------------------------------ save / restore / fork (dexsim_save_state and friends)
     def _state_core(self, what):
         return self._query_core(what, ("state_layout", "state_bank", "save_state", "load_state", "copy_envs", "get_step_stamp",
@@ -985,12 +1022,7 @@ class EnvQueries:
         physics."""
         what = "query_proximity"
         core, ids, q, k = self._kindyn_rows(what, "proximity", env_ids, q)
-        names = ("cap_env", "self_min", "pair_dist")
-        if isinstance(outputs, str):
-            outputs = (outputs,)
-        outputs = tuple(outputs)
-        if not outputs or any(o not in names for o in outputs):
-            raise ValueError(f"{what}: outputs must be a non-empty subset of {names}, got {outputs}")
+        outputs = self._outputs(what, outputs, ("cap_env", "self_min", "pair_dist"))
         if isinstance(box_pose, str):
             if box_pose != "env":
                 raise ValueError(f"{what}: box_pose must be a (k, 7) tensor, 'env' or None, got {box_pose!r}")
@@ -998,26 +1030,10 @@ class EnvQueries:
                 raise ValueError(f"{what}: box_pose='env' needs a q override of num_envs = {self.num_envs} rows")
             if not int(self._sim_cfg.has_box):
                 raise ValueError(f"{what}: box_pose='env' needs a task with a box")
-            box_pose = core.root_state[:, 1, :7].contiguous()
-        elif box_pose is not None:
-            box_pose = torch.as_tensor(box_pose, dtype=torch.float32, device=core.device)
-            if tuple(box_pose.shape) != (k, 7):
-                raise ValueError(f"{what}: box_pose must have shape ({k}, 7), got {tuple(box_pose.shape)}")
-            box_pose = box_pose.contiguous()
-        size = 0.0
-        if box_size is not None:
-            size = float(box_size)
-            if not (size > 0.0 and size != float("inf")):
-                raise ValueError(f"{what}: box_size must be a positive finite edge length, got {box_size}")
+            box_pose = core.root_state[:, 1, :7]
+        box_pose, size = self._box_args(what, box_pose, box_size, k, core.device)
         shapes = {"cap_env": (k, _abi.NCAP, 2, 8), "self_min": (k, _abi.NPROX_GROUPS, 8), "pair_dist": (k, _abi.NPROX_PAIRS)}
-        if out is not None and (not isinstance(out, dict) or any(o not in outputs for o in out)):
-            raise ValueError(f"{what}: out must be a dict of tensors keyed by the names in outputs, got {out if not isinstance(out, dict) else sorted(out)}")
-        bufs = {}
-        for o in outputs:
-            given = None if out is None else out.get(o)
-            bufs[o] = self._kindyn_out(what, given, shapes[o], core.device)
-            if given is None and ids is not None:   # a row whose id is out of range is left as it is by the kernel: give it a defined value
-                bufs[o].fill_(float("nan"))
+        bufs = self._out_buffers(what, outputs, shapes, out, ids, core.device)
         core.proximity(env_ids=ids, q=q, box_pose=box_pose, box_size=size, **bufs)
         if getattr(self, "_proximity_pairs", None) is None:
             self._proximity_pairs = core.proximity_pairs()                     # a host table: read once
@@ -1102,31 +1118,9 @@ class EnvQueries:
         if name not in sensors:
             raise KeyError(f"no ray sensor named '{name}' (ray sensors: {sorted(sensors)})")
         s = sensors[name]
-        names = ("dist", "hits")
-        if isinstance(outputs, str):
-            outputs = (outputs,)
-        outputs = tuple(outputs)
-        if not outputs or any(o not in names for o in outputs):
-            raise ValueError(f"{what}: outputs must be a non-empty subset of {names}, got {outputs}")
-        if box_pose is not None:
-            box_pose = torch.as_tensor(box_pose, dtype=torch.float32, device=core.device)
-            if tuple(box_pose.shape) != (k, 7):
-                raise ValueError(f"{what}: box_pose must have shape ({k}, 7), got {tuple(box_pose.shape)}")
-            box_pose = box_pose.contiguous()
-        size = 0.0
-        if box_size is not None:
-            size = float(box_size)
-            if not (size > 0.0 and size != float("inf")):
-                raise ValueError(f"{what}: box_size must be a positive finite edge length, got {box_size}")
-        shapes = {"dist": (k, s["R"]), "hits": (k, s["R"], 8)}
-        if out is not None and (not isinstance(out, dict) or any(o not in outputs for o in out)):
-            raise ValueError(f"{what}: out must be a dict of tensors keyed by the names in outputs, got {out if not isinstance(out, dict) else sorted(out)}")
-        bufs = {}
-        for o in outputs:
-            given = None if out is None else out.get(o)
-            bufs[o] = self._kindyn_out(what, given, shapes[o], core.device)
-            if given is None and ids is not None:   # a row whose id is out of range is left as it is by the kernel: give it a defined value
-                bufs[o].fill_(float("nan"))
+        outputs = self._outputs(what, outputs, ("dist", "hits"))
+        box_pose, size = self._box_args(what, box_pose, box_size, k, core.device)
+        bufs = self._out_buffers(what, outputs, {"dist": (k, s["R"]), "hits": (k, s["R"], 8)}, out, ids, core.device)
         core.raycast(rays=s["rays"], parent=s["parent"], env_ids=ids, q=q, box_pose=box_pose, box_size=size, min_range=s["min_range"],
                      max_range=s["max_range"], skip_parent=s["skip_parent"], **bufs)
         if s["unsort"] is not None:
